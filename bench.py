@@ -16,8 +16,13 @@ exchange cut-edge contributions of the Riccati recursion and the scalar reductio
 all-reduces (torch.distributed, backend nccl) - SURVEY.md 8(e).  value = MPC steps/s of that single problem.
 
 Extra fields: `roofline` for the dominant kernel (dompc_solve_kernel; HBM-bound model:
-algorithmic bytes of the derivative sweeps it executed / its HIP-event duration) and
-`cpu_baseline` (the CPU oracle, a port of the reference algorithm, timed on a bounded sample).
+algorithmic bytes of the derivative sweeps it executed / its HIP-event duration).
+
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, warms up, times the K steps and prints the line.  `--full` adds
+what takes runs of its own: `roofline.sweep_only`, the live PMC traffic (two rocprofv3 passes), `variant_b`,
+`make_step_ms_b1` and `cpu_baseline` (the CPU oracle, a port of the reference algorithm, timed on a bounded sample).
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the
+rows of the large per-problem arrays, at most DUMP_BUDGET bytes in all).
 """
 import argparse
 import json
@@ -32,6 +37,7 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0           # /opt/skills/guides/MI355X_MICROARCH.md: 8.0 TB/s spec (6.29 TB/s measured copy)
+DUMP_BUDGET = 60_000_000        # --dump-outputs: bytes of all .npy files of one run together
 
 # TEST-ONLY switch (tests/test_distributed.py): DOMPC_BENCH_BACKEND=hostemu runs the same script on the g++ host emulation of
 # the kernels (tests/hostemu.py) with gloo instead of RCCL, so that the N-rank launch path, the batch partition and the one
@@ -268,7 +274,7 @@ def live_traffic(args, B: int):
     for counter in ("FETCH_SIZE", "WRITE_SIZE"):
         d = tempfile.mkdtemp(prefix="dompc_pmc_", dir="/tmp")
         cmd = [rp, "--kernel-trace", "--pmc", counter, "--output-format", "csv", "-d", d, "--", sys.executable,
-               os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--batch", str(B), "--variant", args.variant,
+               os.path.abspath(__file__), "--steps", "1", "--warmup", "0", "--batch", str(B), "--variant", args.variant, "--full",
                "--no-cpu-baseline", "--no-traffic", "--no-b1", "--no-variant-b", "--sweep-steps", "1", "--sweep-warmup", "0"]
         env = dict(os.environ, TMPDIR="/tmp")
         try:
@@ -347,11 +353,17 @@ def parse_args(argv=None):
     ap.add_argument("--n-robust", type=int, default=5, help="--variant tree: depth of the branching part (3^n leaves)")
     ap.add_argument("--cut-level", type=int, default=0, help="--variant tree: level whose nodes are the sub-tree roots (0 = auto)")
     ap.add_argument("--shard-one-rank", action="store_true", help="--variant tree on one GPU: run the sharded code path with world = 1 (all exchanges) instead of the whole-chip mode")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traffic", action="store_true", help="skip the two rocprofv3 --pmc passes that measure roofline.traffic")
-    ap.add_argument("--no-b1", action="store_true", help="skip the single-problem make_step latency")
-    ap.add_argument("--no-variant-b", action="store_true", help="skip the extra `variant_b` key (SURVEY App. D's second reading of configs[3])")
-    ap.add_argument("--sweep-steps", type=int, default=3, help="launches of the sweep-only kernel for roofline.sweep_only (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own (variant A): roofline.sweep_only, the live PMC traffic, variant_b, "
+                         "make_step_ms_b1 and cpu_baseline; each can be left out with its --no-* switch")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64; a fixed, seeded sample of the rows of "
+                         "the per-problem iterates and multipliers)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline")
+    ap.add_argument("--no-traffic", action="store_true", help="--full: skip the two rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--no-b1", action="store_true", help="--full: skip the single-problem make_step latency")
+    ap.add_argument("--no-variant-b", action="store_true", help="--full: skip the extra `variant_b` key (SURVEY App. D's second reading of configs[3])")
+    ap.add_argument("--sweep-steps", type=int, default=3, help="--full: launches of the sweep-only kernel for roofline.sweep_only (0: skip)")
     ap.add_argument("--sweep-warmup", type=int, default=1)
     ap.add_argument("--max-soc", type=int, default=None,
                     help="measurement aid: ipopt.max_soc (default: IPOPT's 4; 0 switches the second-order correction off)")
@@ -399,6 +411,34 @@ def launch_ranks(args, argv) -> int:
                 for q in alive:             # a rank died: the others would wait at the next barrier forever
                     q.terminate()
     return rc
+
+
+def dump_outputs(path, whole, rows=None, seed=0):
+    """--dump-outputs: `whole` (name -> array) written as path/<name>.npy in float64; of the (B x n) arrays in `rows` (numpy
+    or device tensors) a fixed, seeded sample of rows - the same rows for all, their indices in sample_rows.npy - so that
+    the files together stay within DUMP_BUDGET bytes."""
+    os.makedirs(path, exist_ok=True)
+    out = {k: np.asarray(v, dtype=np.float64) for k, v in whole.items()}
+    if rows:
+        B = int(next(iter(rows.values())).shape[0])
+        per_row = sum(8 * int(np.prod(v.shape[1:])) for v in rows.values()) + 8
+        left = DUMP_BUDGET - sum(v.nbytes for v in out.values())
+        idx = np.sort(np.random.default_rng(seed).choice(B, size=max(1, min(B, left // per_row)), replace=False))
+        out["sample_rows"] = idx.astype(np.float64)
+        for k, v in rows.items():
+            if hasattr(v, "index_select"):          # device tensor: the sampled rows are gathered there
+                import torch
+                v = v.index_select(0, torch.as_tensor(idx, device=v.device)).cpu().numpy()
+            else:
+                v = np.asarray(v)[idx]
+            out[k] = np.asarray(v, dtype=np.float64)
+    for k, v in out.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
+def stats_arrays(stats) -> dict:
+    """the per-problem solver statistics of a STATS_DTYPE record array, without the wall-clock field"""
+    return {"stats_" + f: stats[f] for f in stats.dtype.names if f not in ("reserved0", "t_wall_total")}
 
 
 class _HostTimer:
@@ -519,6 +559,11 @@ def main(argv=None):
     t = resident_inputs(mpc, B)
     dt, kern_ms, stats = timed_steps(mpc, t, B, args.warmup, args.steps)
     u0 = (t["X"][:, ps.iu(0, 0):ps.iu(0, 0) + ps.nu].cpu().numpy() * mpc._u_scaling.master)
+    if args.dump_outputs and rank == 0:
+        # what a caller of solve_batch_device receives from the last timed launch (rank 0's shard): u0 of every problem,
+        # objective and statistics, and a sample of the (scaled) iterates and constraint multipliers
+        dump_outputs(args.dump_outputs, {"u0": u0, "f": t["F"].cpu().numpy(), **stats_arrays(stats)},
+                     rows={"x": t["X"], "lam_g": t["LG"]})
     n_ok_all = int(stats["success"].sum())
     if dist is not None:
         tt = torch.tensor([float(n_ok_all), float(t["hi"] - t["lo"])], dtype=torch.float64, device=dev)
@@ -536,7 +581,7 @@ def main(argv=None):
         # dompc_sweep_batch_device (same kernel symbol, mode 2) evaluates g, the per-edge Jacobian / Hessian blocks and their
         # condensed form at B iterates - here the B solutions of the timed batch with their multipliers; residuals out only.
         sweep_only = None
-        if args.sweep_steps > 0:
+        if args.full and args.sweep_steps > 0:
             tG = torch.empty((B, ps.n_g), dtype=torch.float64, device=dev)
             mk = (lambda: torch.cuda.Event(enable_timing=True)) if hip else _HostTimer
 
@@ -560,8 +605,8 @@ def main(argv=None):
                           "max_abs_residual_at_the_solutions": sw_res,      # (all rows are equalities: g(x*) = 0 up to the solver's tolerance)
                           "what": "dompc_sweep_batch_device: one model-evaluation sweep (g, per-edge Jacobian and Lagrangian-Hessian "
                                   "blocks, condensing records) of each of the B solutions, residuals copied out; dompc_solve_kernel mode 2"}
-        traffic, traffic_note = None, "not measured (--no-traffic or N > 1)"
-        if not args.no_traffic and world == 1 and hip:
+        traffic, traffic_note = None, "not measured (no --full, --no-traffic or N > 1)"
+        if args.full and not args.no_traffic and world == 1 and hip:
             traffic, sw_traffic, traffic_note = live_traffic(args, B)
             if sweep_only is not None and sw_traffic:
                 sweep_only["traffic"] = sw_traffic
@@ -596,7 +641,7 @@ def main(argv=None):
                          "kernel_ms": kern_ms, "algorithmic_bytes_per_launch": alg_bytes,
                          "sweep_bytes_per_problem": sweep_b, "sweep_only": sweep_only},
         }
-        if not args.no_variant_b and world == 1 and args.variant == "A":
+        if args.full and not args.no_variant_b and world == 1 and args.variant == "A":
             # SURVEY App. D's second reading of BASELINE configs[3] (3 combinations, n_robust = 2: the docs' figure), same batch
             try:
                 mpc_b = build("B", B)
@@ -609,12 +654,12 @@ def main(argv=None):
                 del mpc_b, tb
             except Exception as e:      # noqa: BLE001
                 out["variant_b"] = {"error": repr(e)}
-        if not args.no_b1 and world == 1 and hip:
+        if args.full and not args.no_b1 and world == 1 and hip:
             try:
                 out["make_step_ms_b1"] = make_step_b1(mpc, ex)
             except Exception as e:      # noqa: BLE001
                 out["make_step_ms_b1"] = {"error": repr(e)}
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline()
         else:
             out["cpu_baseline"] = None
@@ -658,6 +703,8 @@ def bench_closed_loop(args, ex, rank, world, local_rank, dist):
     if dist is not None:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"u0": r["u0"], "x": r["x"], "plant_status": r["plant_status"], **stats_arrays(r["stats"])})
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device=torch.device("cuda", local_rank))
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -725,6 +772,9 @@ def bench_tree(args, ex, rank, world, local_rank, dist):
     t = torch.tensor([sum(t_step)], dtype=torch.float64, device=torch.device("cuda", local_rank))
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"u0": np.ravel(u0), "opt_x": mpc.opt_x_num.master, "lam_g": mpc.lam_g_num,
+                                         "iter_count": [mpc.solver_stats["iter_count"]]})
     if rank == 0:
         sweep_b = sweep_bytes_per_problem(ps)
         n_sweeps = float(np.mean(iters)) + 1.0

@@ -80,7 +80,7 @@ def test_gpus_flag_launches_that_many_ranks_and_reports_them():
     and dropped)."""
     import json
     r = _run_bench({"DOMPC_BENCH_BACKEND": "hostemu"}, "--gpus", "2", "--batch", "2", "--steps", "1", "--warmup", "0",
-                   "--no-cpu-baseline", "--no-b1", "--no-variant-b", "--no-traffic", "--sweep-steps", "1", "--sweep-warmup", "0")
+                   "--full", "--no-cpu-baseline", "--no-b1", "--no-variant-b", "--no-traffic", "--sweep-steps", "1", "--sweep-warmup", "0")
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout

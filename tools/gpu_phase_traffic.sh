@@ -7,7 +7,7 @@ O=gpurun_out/phase_traffic.txt
 : > $O
 one() {
   if [ -n "$1" ]; then export DOMPC_DEFS="$1"; else unset DOMPC_DEFS; fi
-  python bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-variant-b --no-b1 2>/dev/null | tail -1 | python -c "
+  python bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-variant-b --no-b1 2>/dev/null | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print(json.dumps({'defs':'$1','kernel_ms':r['kernel_ms'],'traffic':r['traffic'],'iters':d['solve']['iters_mean'],'sweeps':d['solve']['sweeps_per_solve'],'trials':d['solve']['trials_per_solve'],'conv':d['solve']['converged'],'sweep_only_ms':r['sweep_only']['kernel_ms'],'sweep_only_traffic':r['sweep_only'].get('traffic')}))" | tee -a $O
