@@ -184,12 +184,9 @@ constexpr int EL_NHP = TILE_CONDENSE ? 0 : (NI * DEG > 2 ? NI * DEG : 2);
 constexpr int EL_PV = EL_QT + EL_NHP * NA * NA;                        // pivot rows (NW)
 constexpr int EL_RY = EL_PV + NW;                                      // G_y' lambda (NA), completed in phase 7
 constexpr int EL_RT = EL_RY + NA;                                      // user-defined rterm of the edge: value, gradient, Hessian (RT_LEN)
-#ifndef DOMPC_R16_NL
-#define DOMPC_R16_NL 1                 // matrix-core Riccati pass also for models with nl_cons rows / slack variables
-#endif
 // (a user-defined rterm expression is not supported by tree sharding: the cut-parent update keeps the analytic form;
 //  MPC.shard_tree refuses it)
-constexpr bool R16_ENABLED = (NYT <= 16) && (NV <= 4) && (DOMPC_R16_NL ? (NE <= 4) : (NE == 0 && NS == 0)) && (DOMPC_SHARD == 0) && !RT_CUSTOM && !FREE_ROOT;   // dompc_riccati16.h (device)
+constexpr bool R16_ENABLED = (NYT <= 16) && (NV <= 4) && (NE <= 4) && (DOMPC_SHARD == 0) && !RT_CUSTOM && !FREE_ROOT;   // dompc_riccati16.h (device)
 #ifndef DOMPC_HOST_EMU
 constexpr bool RB_IN_LDS = !R16_ENABLED;
 #else
@@ -239,23 +236,17 @@ constexpr bool QUAD_EDGE = false;
 // ... and the per-edge part of the forward pass on the same layout, the inverse G_cc^-1 formed again instead of read back (dompc_quad.h).
 // The sweep then stores the inverse only for the adjoint variant of the forward pass (last barrier levels), which still reads it:
 // lu_store_rule() - the barrier parameter of the sweep is at most one level above the adjoint threshold - and Prob::lu_ok.
-#ifndef DOMPC_QUAD_FORWARD
-#define DOMPC_QUAD_FORWARD 1
-#endif
-#ifndef DOMPC_ADJ_REFINE
-#define DOMPC_ADJ_REFINE 1
-#endif
 #ifndef DOMPC_ADJ_MU
 #define DOMPC_ADJ_MU 10.0
 #endif
-constexpr bool QUAD_FWD = QUAD_EDGE && (DOMPC_QUAD_FORWARD != 0);
+constexpr bool QUAD_FWD = QUAD_EDGE;
 // Does a sweep at barrier parameter mu store G_cc^-1 in the forward records?  Always, unless the forward pass forms it again (QUAD_FWD);
 // then only if the next forward pass may be the adjoint variant (mu <= DOMPC_ADJ_MU tol, dompc_forward.h): the barrier parameter can drop by
 // one level between a sweep and the solve that follows it (monotone update, refresh_mu), mu+ = min(kappa_mu mu, mu^theta_mu).  A drop by
 // several levels at one iterate is caught by the driver (it repeats the sweep with Prob::soc bit 2 = "store").
 DOMPC_DEV inline bool lu_store_rule(const KArgs& A, double mu, int soc) {
   if (!QUAD_FWD || (soc & 4)) return true;
-  if (!DOMPC_ADJ_REFINE || (soc & 2)) return false;
+  if (soc & 2) return false;
   const double thr = DOMPC_ADJ_MU * A.opt.tol;
   return mu > 0.0 && mu <= fmax(thr / A.opt.kappa_mu, pow(thr, 1.0 / A.opt.theta_mu));
 }
@@ -271,16 +262,14 @@ constexpr int qf_pad4(int n) { return n + ((4 - n % 16) + 16) % 16; }
 constexpr int QF_VG = qf_pad4(2 * NW + NA + DEG * NX);                        // forward pass with four edges per wavefront: dw | dy | rhs | rr per edge (4 mod 16 doubles apart: banks)
 constexpr int QF_NEED = QUAD_FWD ? QL_WB + 4 * QF_VG : 0;
 constexpr int QL_NEED = QUAD_EDGE ? el_max(QL_QV + 4 * 32, QF_NEED) : 0;
-// four scenario chains per wavefront in the backward Riccati pass (round 6, dompc_riccati4.h): four staged edge-record heads, four packed
-// value functions, four closed-loop maps
+// chain walk of the forward pass with four scenario chains per wavefront (dompc_forward.h): step vectors and operands of each chain
+constexpr int FW4_CH = ((3 * 16 + (NV * NA + NV) + 2 * (NX * NA + NX) + 1) / 2) * 2;
 #ifndef DOMPC_HOST_EMU
-constexpr bool R4_SIZES = R16_ENABLED && (DOMPC_NE == 0) && (DOMPC_NS == 0) && (NYT <= 16);
+constexpr int FW4_NEED = (NA <= 16 && NV <= 16) ? 4 * FW4_CH : 0;
 #else
-constexpr bool R4_SIZES = false;
+constexpr int FW4_NEED = 0;
 #endif
-constexpr int r4_pad4(int n) { return n + ((4 - n % 16) + 16) % 16; }
-constexpr int R4_NEED = R4_SIZES ? 4 * r4_pad4(((ES_QV + NA + 31) / 32) * 32) + 4 * r4_pad4(NA * (NA + 1) / 2 + NA) + 4 * r4_pad4(NA * NA > 64 ? NA * NA : 64) : 0;
-constexpr int EL_SIZE = ((el_max(el_max(el_max(el_max(el_max(EL_MOC + MOC_STAGE, RB_NEED), el_max(RF_IMG + MO_IMG, R16_NEED)), DAE_NEED), QL_NEED), R4_NEED) + 7) / 8) * 8;
+constexpr int EL_SIZE = ((el_max(el_max(el_max(el_max(el_max(EL_MOC + MOC_STAGE, RB_NEED), el_max(RF_IMG + MO_IMG, R16_NEED)), DAE_NEED), QL_NEED), FW4_NEED) + 7) / 8) * 8;
 
 // ---- dense image of a compact model-output record
 // dense index (MO_PT / MO_LT / MO_MT / MO_NL layout) of compact entry k
@@ -345,23 +334,15 @@ DOMPC_DEV inline int point_of_slot(int sl) {
 // The generated functions behind interfaces that say what the caller knows: the output record overlaps none of the inputs.  Without it the
 // compiler keeps every load of an input that follows a store to the record in program order BEHIND that store, and the wait for such a
 // load (s_waitcnt vmcnt is in order) is a wait for the store to reach memory.
-#ifndef DOMPC_EVAL_NOALIAS
-#define DOMPC_EVAL_NOALIAS 1          // 0: the generated functions as they are (A/B)
-#endif
-#if DOMPC_EVAL_NOALIAS
-#define DOMPC_RESTRICT __restrict__
-#else
-#define DOMPC_RESTRICT
-#endif
-DOMPC_DEV inline void dyn_c_noalias(const double* DOMPC_RESTRICT xs, const double* DOMPC_RESTRICT us, const double* DOMPC_RESTRICT tvp,
-                                    const double* DOMPC_RESTRICT pp, const double* DOMPC_RESTRICT lam, double* DOMPC_RESTRICT o) {
+DOMPC_DEV inline void dyn_c_noalias(const double* __restrict__ xs, const double* __restrict__ us, const double* __restrict__ tvp,
+                                    const double* __restrict__ pp, const double* __restrict__ lam, double* __restrict__ o) {
   dompc_dyn_c(xs, us, nullptr, tvp, pp, lam, o);
 }
-DOMPC_DEV inline void lterm_c_noalias(const double* DOMPC_RESTRICT xs, const double* DOMPC_RESTRICT us, const double* DOMPC_RESTRICT tvp,
-                                      const double* DOMPC_RESTRICT pp, double* DOMPC_RESTRICT o) {
+DOMPC_DEV inline void lterm_c_noalias(const double* __restrict__ xs, const double* __restrict__ us, const double* __restrict__ tvp,
+                                      const double* __restrict__ pp, double* __restrict__ o) {
   dompc_lterm_c(xs, us, nullptr, tvp, pp, o);
 }
-DOMPC_DEV inline void mterm_c_noalias(const double* DOMPC_RESTRICT xs, const double* DOMPC_RESTRICT tvp, const double* DOMPC_RESTRICT pp, double* DOMPC_RESTRICT o) {
+DOMPC_DEV inline void mterm_c_noalias(const double* __restrict__ xs, const double* __restrict__ tvp, const double* __restrict__ pp, double* __restrict__ o) {
   dompc_mterm_c(xs, tvp, pp, o);
 }
 // Thread-parallel evaluation of the lowered model functions at the current iterate: one thread per

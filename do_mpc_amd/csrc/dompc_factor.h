@@ -21,52 +21,12 @@
 // Natural pivot order (the diagonal of G_cc = h J - C (x) I carries the collocation coefficients); a failed threshold test
 // returns 1 and the caller repeats the factorisation with the register-resident elimination and partial pivoting.
 // Out: W | w0 (collocation rows; the caller derives the continuity rows) in LDS, G_cc^-1 in the forward record.
-#ifndef DOMPC_MFMA_GJ
-#define DOMPC_MFMA_GJ 1
-#endif
-#ifndef DOMPC_GJ_SKIP
-#define DOMPC_GJ_SKIP 1             // blocked elimination: skip the updates of tile columns whose unit columns are still untouched (0: update everything)
-#endif
-#ifndef DOMPC_DUAL_VALU
-#define DOMPC_DUAL_VALU 1           // dual-residual products of the factorisation on the vector ALU (0: on the matrix cores, multipliers in one row of the A operand)
-#endif
-#ifndef DOMPC_GJ_PRIO
-#define DOMPC_GJ_PRIO 3             // wavefront priority (s_setprio) while the factorisation of an edge runs: its dependent chains then win the
-                                    // issue arbitration against the partner wavefront's memory instructions (+1.3 %); 0: off
-#endif
-#ifndef DOMPC_MM_PRIO
-#define DOMPC_MM_PRIO 0             // ... while the tile condensing of the sweep / the matrix part of a Riccati node runs (measured: nothing on top)
-#endif
-#if DOMPC_MM_PRIO && !defined(DOMPC_HOST_EMU)
-#define DOMPC_PRIO_UP() __builtin_amdgcn_s_setprio(DOMPC_MM_PRIO)
-#define DOMPC_PRIO_DOWN() __builtin_amdgcn_s_setprio(0)
-#else
-#define DOMPC_PRIO_UP()
-#define DOMPC_PRIO_DOWN()
-#endif
 #ifndef DOMPC_GJ_U
 #define DOMPC_GJ_U 0.01              // threshold of the pivot test of the blocked elimination (|a_kk| >= u max|a_ik|); a huge value sends every
 #endif                               // edge through the out-of-line factorisation with partial pivoting (test of that fallback)
-#ifndef DOMPC_GJ_ADJ
-#define DOMPC_GJ_ADJ 0                // 1: inverse of the 4 x 4 pivot block from its adjugate instead of LU in uniform arithmetic + two triangular solves (measured: +-0)
-#endif
-#ifndef DOMPC_GJ_LTEST
-#define DOMPC_GJ_LTEST 1            // 1: the threshold test of the 4 x 4 pivot blocks on the multipliers l_ik = a_ik / a_kk (|l_ik| <= 1 / u) instead of on the
-#endif                              // column entries before the division: 10 instead of 18 uniform instructions per step, same decisions (+0.3 %)
-#if DOMPC_GJ_LTEST && DOMPC_GJ_ADJ
-#error "DOMPC_GJ_LTEST belongs to the LU variant of the pivot block"
-#endif
-#ifndef DOMPC_GJ_SB
-#define DOMPC_GJ_SB 0               // 1: scheduling barriers at the step boundaries of the blocked elimination (measurement aid)
-#endif
-#if DOMPC_GJ_SB
-#define GJ_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define GJ_SB()
-#endif
 constexpr int GJ_R = DEG * NX, GJ_RP = ((GJ_R + 3) / 4) * 4, GJ_NRHS = NA + 1;
 constexpr int GJ_NC = GJ_RP + GJ_NRHS + GJ_R;                      // columns: [G_cc padded | G_y r | I]
-constexpr bool MFMA_GJ = (NI == 1) && (DEG >= 1) && !DENSE_EDGE && (GJ_RP <= 32) && (GJ_NC <= 64) && (DOMPC_MFMA_GJ != 0);
+constexpr bool MFMA_GJ = (NI == 1) && (DEG >= 1) && !DENSE_EDGE && (GJ_RP <= 32) && (GJ_NC <= 64);
 constexpr int GJ_MT = (GJ_RP + 15) / 16, GJ_NT = (GJ_NC + 15) / 16;
 static_assert(!MFMA_GJ || GJ_RP * 4 + 256 <= EL_T1 - EL_MX, "the panel buffer and the dual-residual row share the W | w0 region of the edge working set");
 
@@ -134,18 +94,12 @@ __device__ inline double gj_element(const ldsd* mol, const ldsd* Ld, int row, in
 // in the tile registers whose rows and columns overlap (T[mi][mi][.], the packed register of tile column 1); their table entries
 // carry the index of -C[j][j] in the three low bits (offsets are multiples of 8).  The build is then one 16-bit and one 64-bit LDS
 // read per element.  Same values as gj_element() up to the sign of a zero.
-#ifndef DOMPC_GJ_TABLE
-#define DOMPC_GJ_TABLE 1
-#endif
-#ifndef DOMPC_GJ_TABLE_CHECK
-#define DOMPC_GJ_TABLE_CHECK 0        // 1: build every tile both ways and trap on a difference (GPU check of the table)
-#endif
 constexpr int GJ_NEL = GJ_MTF * 4 * GJ_NT + (GJ_PACK ? GJ_NT : 0);      // tile registers of a lane
 constexpr int GJ_NPOOL = 2 + (DEG + 1) * DEG;                           // 0, 1, -C[s][j] (s = 0..DEG, j = 1..DEG)
 constexpr int GJ_TAB = ((EL_MOC + MOC_STAGE + 1) / 2) * 2;
 constexpr int GJ_POOL = GJ_TAB + (GJ_NEL * 64 * 2 + 7) / 8;
 constexpr int GJ_DPOOL = GJ_POOL + GJ_NPOOL;                            // 0, -C[1][1], ..., -C[DEG][DEG]
-constexpr bool GJ_TABLE = MFMA_GJ && (DOMPC_GJ_TABLE != 0) && (GJ_DPOOL + DEG + 1 <= EL_SIZE) && (EL_SIZE <= 2048) && (DEG <= 7);
+constexpr bool GJ_TABLE = MFMA_GJ && (GJ_DPOOL + DEG + 1 <= EL_SIZE) && (EL_SIZE <= 2048) && (DEG <= 7);
 typedef __attribute__((address_space(3))) unsigned short ldsu16;
 typedef __attribute__((address_space(3))) char ldsc;
 // table entry of element (row, column lc of tile column ni): mirrors gj_element()
@@ -217,9 +171,9 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
 #define GJ_PH(i)
 #endif
   const int lr = lane >> 4, lc = lane & 15;
-#if DOMPC_GJ_PRIO
-  __builtin_amdgcn_s_setprio(DOMPC_GJ_PRIO);
-#endif
+  // raised wavefront priority while the factorisation runs: its dependent chains then win the issue arbitration against the partner
+  // wavefront's memory instructions (+1.3 %)
+  __builtin_amdgcn_s_setprio(3);
   d4 T[MT][NT];
   d4 X = {0.0, 0.0, 0.0, 0.0};                    // GJ_PACK: register ni = rows 16..19 of tile column ni
   // ---- tiles of [G_cc | G_y r | I]
@@ -242,20 +196,6 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
 #pragma unroll
       for (int ni = 0; ni < NT; ++ni, ++el) X[ni] = elem(el, ni == 1);
     }
-#if DOMPC_GJ_TABLE_CHECK
-#pragma unroll
-    for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          if (T[mi][ni][r] != ((16 * mi + 4 * r >= RP) ? 0.0 : gj_element(mol, Ld, 16 * mi + 4 * r + lr, ni, lc))) __builtin_trap();
-    if constexpr (GJ_PACK) {
-#pragma unroll
-      for (int ni = 0; ni < NT; ++ni)
-        if (X[ni] != gj_element(mol, Ld, 16 + lr, ni, lc)) __builtin_trap();
-    }
-#endif
   } else {
 #pragma unroll
   for (int mi = 0; mi < MT; ++mi)
@@ -271,15 +211,12 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
   }
   GJ_PH(25)
   {
-    // ---- dual-residual pieces: lambda' [G_cc | G_y] on the matrix cores.  A operand: the multipliers of the collocation rows
-    // in row 0 of a 16 x 4 block per k-block; B operand: the tile registers themselves (register r of tile row mi = rows
-    // 16 mi + 4 r ...).  Row 0 of the result tiles goes through LDS to the lanes that own the columns (dual_from).
+    // ---- dual-residual pieces lambda' [G_cc | G_y] on the vector ALU: this lane's rows of its columns (register r of tile row mi =
+    // rows 16 mi + 4 r ...; 4 per full tile row + 1 packed) times their multipliers.  The four lane groups of a column leave their
+    // partial sums in four rows of the buffer; they go through LDS to the lanes that own the columns (dual_from), which add them.
+    // (An MFMA with the multipliers in one row of the A operand does the same at 1/16 of its throughput: 15 instructions of 64 cycles.)
     constexpr int NDT = (RP + NA + 15) / 16 < NT ? (RP + NA + 15) / 16 : NT;
     ldsd* du = Ld + EL_MX + 4 * RP;                 // (behind the panel buffer; the W | w0 region is written after the last step)
-#if DOMPC_DUAL_VALU
-    // on the vector ALU: this lane's rows of its columns (4 per full tile row + 1 packed) times their multipliers; the four lane
-    // groups of a column leave their partial sums in four rows of the buffer, the reader adds them (an MFMA with the multipliers
-    // in one row of the A operand does the same at 1/16 of its throughput: 15 instructions of 64 cycles)
     {
       double lamr[MT][4], lamx = 0.0;
 #pragma unroll
@@ -301,26 +238,6 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
         du[64 * lr + 16 * ni + lc] = t;
       }
     }
-#else
-    d4 acc[NDT];
-#pragma unroll
-    for (int ni = 0; ni < NDT; ++ni) acc[ni] = d4{0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kb = 0; kb < RP / 4; ++kb) {
-      const int row = 4 * kb + lr;
-      const double lam = Ld[EL_T0 + (row < R ? row : 0)];
-      const double a = (lc == 0 && row < R) ? lam : 0.0;
-#pragma unroll
-      for (int ni = 0; ni < NDT; ++ni) {
-        const double b = (GJ_PACK && kb >= 4) ? X[ni] : T[(GJ_PACK && kb >= 4) ? 0 : kb / 4][ni][kb % 4];
-        acc[ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, acc[ni], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int ni = 0; ni < NDT; ++ni) {              // (same buffer layout as the vector-ALU variant: row 0 holds the sums)
-      du[64 * lr + 16 * ni + lc] = (lr == 0) ? acc[ni][0] : 0.0;
-    }
-#endif
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     dual_from((const ldsd*)du);
@@ -332,7 +249,6 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
   // ---- RP / 4 steps of four pivots
 #pragma unroll
   for (int p = 0; p < RP / 4; ++p) {
-    GJ_SB();
     const int mip = p / 4, rp = p % 4, nip = p / 4, c0 = 4 * (p % 4);
     const bool prow_x = GJ_PACK && mip == 1;       // (the panel rows live in the packed tile)
     // panel columns -> LDS
@@ -356,56 +272,16 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
 #pragma unroll
       for (int j = 0; j < 4; ++j) a_[i][j] = pan[(4 * p + i) * 4 + j];
     double x_[4];
-#if DOMPC_GJ_ADJ
-    // column lr of P^-1 from the adjugate (2 x 2 minors of the row pairs (0,1) and (2,3), Laplace expansion): a dependent chain of
-    // ~12 instructions instead of ~43 through the LU factors and the two triangular solves - a dependent FP64 instruction costs
-    // ~16 cycles here, and this chain sits in front of the matrix-core instructions of every step.  Accepted if the determinant
-    // lost less than four digits to cancellation (|det| >= 1e-4 sum |terms|); otherwise the caller repeats the factorisation with
-    // partial pivoting like after a failed threshold test of the LU variant.
-    {
-      const int rho = 4 * p + (lr ^ 1);                         // column j of the adjugate is built from row j ^ 1 and the minors of the OTHER row pair
-      const double r0 = pan[rho * 4 + 0], r1 = pan[rho * 4 + 1], r2 = pan[rho * 4 + 2], r3 = pan[rho * 4 + 3];
-      double sm[6], cm[6];
-      constexpr int MA[6] = {0, 0, 0, 1, 1, 2}, MB[6] = {1, 2, 3, 2, 3, 3};      // column pairs of the minors
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        sm[k] = fma(a_[0][MA[k]], a_[1][MB[k]], -(a_[1][MA[k]] * a_[0][MB[k]]));
-        cm[k] = fma(a_[2][MA[k]], a_[3][MB[k]], -(a_[3][MA[k]] * a_[2][MB[k]]));
-      }
-      const double t0 = sm[0] * cm[5], t1 = sm[1] * cm[4], t2 = sm[2] * cm[3], t3 = sm[3] * cm[2], t4 = sm[4] * cm[1], t5 = sm[5] * cm[0];
-      const double det = ((t0 - t1) + (t2 + t3)) + (t5 - t4);
-      const double mag = ((fabs(t0) + fabs(t1)) + (fabs(t2) + fabs(t3))) + (fabs(t5) + fabs(t4));
-      viol = fmax(viol, fma(1e-4, mag, -fabs(det)));            // > 0: cancellation
-      pmin = fmin(pmin, fabs(det));
-      double m_[6];
-#pragma unroll
-      for (int k = 0; k < 6; ++k) m_[k] = (lr < 2) ? cm[k] : sm[k];
-      const double idet = fast_rcp((fabs(det) > 1e-300) ? det : 1.0);
-      const double sg = (lr & 1) ? -idet : idet;
-      x_[0] = sg * fma(r1, m_[5], fma(-r2, m_[4], r3 * m_[3]));
-      x_[1] = sg * fma(-r0, m_[5], fma(r2, m_[2], -(r3 * m_[1])));
-      x_[2] = sg * fma(r0, m_[4], fma(-r1, m_[2], r3 * m_[0]));
-      x_[3] = sg * fma(-r0, m_[3], fma(r1, m_[1], -(r2 * m_[0])));
-    }
-#else
     // P, LU in uniform arithmetic
     double iu[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-#if !DOMPC_GJ_LTEST
-      double m = 0.0;
-#pragma unroll
-      for (int i = k + 1; i < 4; ++i) m = fmax(m, fabs(a_[i][k]));
-      viol = fmax(viol, fma(GJ_U, m, -fabs(a_[k][k])));      // > 0: |a_kk| < GJ_U max|a_ik|
-#endif
       pmin = fmin(pmin, fabs(a_[k][k]));
       iu[k] = fast_rcp(a_[k][k]);
 #pragma unroll
       for (int i = k + 1; i < 4; ++i) {
         a_[i][k] *= iu[k];
-#if DOMPC_GJ_LTEST
-        viol = fmax(viol, fabs(a_[i][k]));                  // the same test on the multipliers: |l_ik| <= 1 / GJ_U
-#endif
+        viol = fmax(viol, fabs(a_[i][k]));                  // threshold test on the multipliers: |l_ik| <= 1 / GJ_U
 #pragma unroll
         for (int j = k + 1; j < 4; ++j) a_[i][j] = fma(-a_[i][k], a_[k][j], a_[i][j]);
       }
@@ -425,8 +301,6 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
       for (int j = i + 1; j < 4; ++j) t = fma(-a_[i][j], x_[j], t);
       x_[i] = t * iu[i];
     }
-#endif
-    GJ_SB();             // (the LU factors are dead: do not hoist the loads below above them)
     // this lane's entries of -(C~ P^-1): row lc of every full tile row (packed rows: row 16 + (lc & 3)), column lr
     auto cprime = [&](int row) {
       const int rowc = row < RP ? row : 0;
@@ -455,21 +329,15 @@ __device__ inline int edge_factor_mfma(const Prob& Q, int e, int lane, ldsd* Ld,
       if (16 * (ni + 1) <= 4 * (p + 1)) continue;
       // a tile column that holds only unit columns e_b (and padding) with b >= 4 (p + 1): their entries in the panel rows are still
       // zero - the update would add nothing (industrial_poly: tile column 3 during the first three steps, 6 of 36 MFMAs)
-      if (DOMPC_GJ_SKIP && 16 * ni >= RP + GJ_NRHS && 16 * ni - (RP + GJ_NRHS) >= 4 * (p + 1)) continue;
+      if (16 * ni >= RP + GJ_NRHS && 16 * ni - (RP + GJ_NRHS) >= 4 * (p + 1)) continue;
 #pragma unroll
       for (int mi = 0; mi < MT; ++mi) T[mi][ni] = __builtin_amdgcn_mfma_f64_16x16x4f64(cp[mi], Rb[ni], T[mi][ni], 0, 0, 0);
       if constexpr (GJ_PACK) X = __builtin_amdgcn_mfma_f64_16x16x4f64(((lc >> 2) == ni) ? cpx : 0.0, Rb[ni], X, 0, 0, 0);
     }
   }
   GJ_PH(26)
-#if DOMPC_GJ_PRIO
   __builtin_amdgcn_s_setprio(0);
-#endif
-#if DOMPC_GJ_LTEST
   if (!(viol <= 1.0 / GJ_U && pmin > 1e-300)) return 1;  // (NaN-safe: a failed test or a vanishing pivot)
-#else
-  if (!(viol <= 0.0 && pmin > 1e-300)) return 1;        // (NaN-safe: a failed test or a vanishing pivot)
-#endif
   // ---- W | w0 (collocation rows) -> LDS, G_cc^-1 -> forward record
   auto put = [&](int row, int ni, double v) {
     const GjCol c = gj_col(ni, lc);
@@ -787,15 +655,8 @@ DOMPC_DEV inline int run_edge_factor(const Thr& T, const Prob& Q, int e, double 
 #ifndef DOMPC_HOST_EMU
   if constexpr (EF_CPX == 1) {
     (void)lane; (void)GS; (void)Ld;
-#ifndef DOMPC_EF_INLINE
-#define DOMPC_EF_INLINE 0          // 1: the matrix-core factorisation inside the sweep function (no call, no callee-saved registers to save per edge)
-#endif
-    int rc;
-    if constexpr (MFMA_GJ && DOMPC_EF_INLINE)
-      rc = edge_factor_body<1>(Q, e, mu, lane, GS, Ld, vx, ex, nu_a);
-    else
-      rc = phase_edge_factor(T.kp, Q.slot, e, Q.soc, Q.sf, mu, vx[0][0], vx[0][1], vx[0][2], vx[0][3], vx[0][4],
-                             ex[0], ex[1], ex[2], ex[3], ex[4], nu_a);
+    int rc = phase_edge_factor(T.kp, Q.slot, e, Q.soc, Q.sf, mu, vx[0][0], vx[0][1], vx[0][2], vx[0][3], vx[0][4],
+                               ex[0], ex[1], ex[2], ex[3], ex[4], nu_a);
     if (MFMA_GJ && __builtin_amdgcn_readfirstlane(rc) == 2)          // (threshold test of the blocked elimination failed: rare)
       rc = phase_edge_factor_pivot(T.kp, Q.slot, e, Q.soc, Q.sf, mu, vx[0][0], vx[0][1], vx[0][2], vx[0][3], vx[0][4],
                                    ex[0], ex[1], ex[2], ex[3], ex[4], nu_a);
@@ -828,10 +689,6 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
   const KArgs& A = *Q.A;
   const bool act = e >= 0;
   const int ee = act ? e : 0;
-#ifndef DOMPC_EDGE_PACK
-#define DOMPC_EDGE_PACK 1           // the indices of an edge from its packed record (KArgs::edge_pack); 0: from the separate tables
-#endif
-#if DOMPC_EDGE_PACK
   const auto* ep = A.edge_pack + ee * EP_N;             // (the edge's indices side by side: one scalar load, dompc_kargs.h)
   const int n = ep[EP_PARENT], cn = ep[EP_CHILD], k = ep[EP_LEVEL];
   const double* xn = Q.x + ep[EP_XOFF_PARENT];
@@ -842,17 +699,6 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
   const double* pp = Q.P + A.p_off_p + ep[EP_PIDX] * NP;
   const int row0 = ep[EP_ROW0];
   const double om = __builtin_bit_cast(double, ((unsigned long long)(unsigned)ep[EP_OMEGA_HI] << 32) | (unsigned long long)(unsigned)ep[EP_OMEGA_LO]) * Q.sf;
-#else
-  const int n = A.edge_parent[ee], cn = A.edge_child[ee], k = A.edge_level[ee];
-  const double* xn = Q.x + A.node_x_off[n];
-  const double* un = Q.x + A.node_u_off[n];
-  const double* xc = Q.x + A.node_x_off[cn];
-  const int woff = A.edge_w_off[ee];
-  const int eps_off_n = NSE > 0 ? A.node_eps_off[n] : 0;
-  const double* pp = Q.P + A.p_off_p + A.edge_pidx[ee] * NP;
-  const int row0 = A.edge_row0[ee];
-  const double om = A.edge_omega[ee] * Q.sf;
-#endif
   (void)eps_off_n;
   const double* w = Q.x + woff;
   const double* tvp = Q.P + A.p_off_tvp + k * NTVP;
@@ -900,7 +746,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
   for (int q = 0; q < PF_N; ++q) pf_tok[q] = 0u;
 #endif
 #ifndef DOMPC_HOST_EMU
-  if (MO_LDS && act && staged_e != e && !(DOMPC_KO & 32)) { stage_mo(Q, e, lane, Ld); staged_e = e; }
+  if (MO_LDS && act && staged_e != e) { stage_mo(Q, e, lane, Ld); staged_e = e; }
 #endif
   (void)staged_e;
   long long pc0 = prof_clock();
@@ -991,23 +837,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
       // NX lanes) and the Jacobian columns: requested up front, together with the loads of the residual rows
       double vx[CPX][5], ex[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
       double nu_a = 0.0;
-      if (act && (DOMPC_KO & 16)) {
-#pragma unroll
-        for (int q = 0; q < CPX; ++q) { vx[q][0] = 1.0; vx[q][1] = 0.0; vx[q][2] = 2.0; vx[q][3] = 1.0; vx[q][4] = 1.0; }
-        ex[0] = 1.0; ex[2] = 2.0; ex[3] = 1.0; ex[4] = 1.0; nu_a = 0.5;
-#pragma unroll
-        for (int q = 0; q < RPL; ++q) {
-          pf_xn[q] = 1.0; pf_wend[q] = 1.0; pf_xc[q] = 1.0; pf_lam[q] = 0.5; pf_c[q] = 0.0; pf_cend[q] = 0.0;
-#pragma unroll
-          for (int r = 1; r <= DEG; ++r) pf_w[q][r - 1] = 1.0;
-        }
-#ifndef DOMPC_HOST_EMU
-        if (MO_LDS && !(DOMPC_KO & 32)) {
-          asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-          mo_expand(Ld + EL_MOS, (const ldsd*)(Ld + EL_MOC), mm, lane, GS);
-        }
-#endif
-      } else if (act) {
+      if (act) {
 #pragma unroll
         for (int q = 0; q < CPX; ++q) {
           const unsigned cx = ul + (unsigned)q * ugs;
@@ -1023,7 +853,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
         }
         fetch_rest();
 #ifndef DOMPC_HOST_EMU
-        if (MO_LDS && !(DOMPC_KO & 32)) {
+        if (MO_LDS) {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the staged record (and everything above) has landed
           mo_expand(Ld + EL_MOS, (const ldsd*)(Ld + EL_MOC), mm, lane, GS);
         }
@@ -1070,13 +900,13 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
       DOMPC_PH(5)
       T.gsync();
       DOMPC_PH(6)
-      if (act && !(DOMPC_KO & 1)) fail |= run_edge_factor(T, Q, e, mu, lane, GS, Ld, vx, ex, nu_a);
+      if (act) fail |= run_edge_factor(T, Q, e, mu, lane, GS, Ld, vx, ex, nu_a);
       T.gsync();
 #ifndef DOMPC_HOST_EMU
       // the compact record of the edge this wavefront handles next: on its way into the staging buffer (free since the
       // expansion above) during the condensing phases and the stores of this edge.  Not earlier: the out-of-line
       // factorisation waits for every outstanding memory operation at its entry (calling convention).
-      if (MO_LDS && e_next >= 0 && !(DOMPC_KO & 32)) { stage_mo(Q, e_next, lane, Ld); staged_e = e_next; }
+      if (MO_LDS && e_next >= 0) { stage_mo(Q, e_next, lane, Ld); staged_e = e_next; }
 #endif
     } else {
     // ---- the batch of global loads of the edge (see GP above)
@@ -1377,8 +1207,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
     //      - 38 MFMAs instead of the LDS-staged products of the generic path below (H_ww W, H_uw W, W'T1, ...).
     if constexpr (TILE_CONDENSE) {
 #ifndef DOMPC_HOST_EMU
-      if (act && !(DOMPC_KO & 2)) {
-        DOMPC_PRIO_UP();
+      if (act) {
         constexpr int KB_A = (NA + 3) / 4, KB_X = (NX + 3) / 4;
         const int g = lane >> 4, j = lane & 15;
         auto Wm = [&](int row, int col) -> double { return Ld[EL_MX + row * MX_LD + MX_W + col]; };
@@ -1445,7 +1274,6 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
           if constexpr (VCOL) { if (i < NA && (j == NA || j == NA + 1)) Ld[EL_QV + (j - NA) * NA + i] = QTt[r]; }
           else { if (i < NA && j < 2) Ld[EL_QV + j * NA + i] = qv0[r]; }
         }
-        DOMPC_PRIO_DOWN();
       }
 #endif
       DOMPC_PH(7)
@@ -1579,7 +1407,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
       }
     }
 #endif
-    if (act && !(DOMPC_KO & 4)) {
+    if (act) {
       if constexpr (GP) {
 #pragma unroll
         for (int q = 0; q < G_CVL; ++q) {
@@ -1614,7 +1442,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
     T.gsync();
     if (act) edge_rterm_store(Ld + EL_RT, S_, lane, GS);
   }
-  if (act && !(DOMPC_KO & 4)) {
+  if (act) {
     if constexpr (PF) {                    // (operands in registers since the first load batch of the edge)
 #pragma unroll
       for (int q = 0; q < APL; ++q) {

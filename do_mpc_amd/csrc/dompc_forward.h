@@ -6,15 +6,12 @@
 
 // Forward sweep: steps for node variables, then per edge the collocation steps and multipliers.
 // One group of lanes per node (level by level), then one group per edge.
-#ifndef DOMPC_ADJ_REFINE
-#define DOMPC_ADJ_REFINE 1            // adjoint recovery of the continuity multipliers (0: the steps of round 4, d nu = P dx + p everywhere)
-#endif
 #ifndef DOMPC_ADJ_MU
 #define DOMPC_ADJ_MU 10.0             // used from mu <= DOMPC_ADJ_MU * tol on: the last one or two levels of the barrier parameter (default tolerance:
 #endif                                // 2.5e-9 and 9.1e-10), where Sigma reaches 1e9 ... 1e11 (measured: the same iteration counts from 1e-8 to 1e-3, half the cost of 1e-5)
 // (its own instantiation of the forward pass - on the device its own outlined phase: the per-edge part of the other one keeps its registers)
 DOMPC_DEV inline bool forward_adjoint(const Prob& Q, double mu) {
-  constexpr bool ok = DOMPC_ADJ_REFINE && NI == 1 && M > 0 && DEG > 0 && !DENSE_EDGE && !RT_CUSTOM && !FREE_ROOT && !EPS_GLOBAL;
+  constexpr bool ok = NI == 1 && M > 0 && DEG > 0 && !DENSE_EDGE && !RT_CUSTOM && !FREE_ROOT && !EPS_GLOBAL;
   return ok && !sh_on(*Q.A) && !(Q.soc & 2) && mu > 0.0 && mu <= DOMPC_ADJ_MU * Q.A->opt.tol;
 }
 template <bool ADJ>
@@ -171,16 +168,14 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
     T.sync();
   }
 #ifndef DOMPC_HOST_EMU
-#ifndef DOMPC_FW4
-#define DOMPC_FW4 1                 // chain walk of the forward pass: four scenario chains per wavefront (0: one)
-#endif
   // Chain walk, FOUR scenario chains per wavefront: a chain step keeps at most NA (<= 16) lanes busy and is a sequence of four LDS round
   // trips with dependent sums in between - latency, not work.  Lane group c = lane >> 4 walks chain s0 + c with its own step vectors and
   // operand area in LDS; the same arithmetic per entry and the same order of every sum as chain_step() (bitwise the same steps), a quarter
   // of the sequential steps per wavefront.  On the chain levels node (k, s) = level_node_start[k] + s has the one child edge
   // node_child_start[level_node_start[k]] + s leading to node (k + 1, s) (checked by the runtime when it sets chain_level).
-  constexpr int FW4_CH = ((3 * 16 + FW_N + 1) / 2) * 2, FW4_PL = (FW_N + 15) / 16;
-  constexpr bool FW4 = (DOMPC_FW4 != 0) && NA <= 16 && NV <= 16 && 4 * FW4_CH <= EL_SIZE;
+  constexpr int FW4_PL = (FW_N + 15) / 16;
+  constexpr bool FW4 = FW4_NEED > 0;
+  static_assert(!FW4 || (FW4_CH == ((3 * 16 + FW_N + 1) / 2) * 2 && 4 * FW4_CH <= EL_SIZE), "four chains must fit the wavefront's LDS region");
   if (FW4 && GS == 64) {
     const int S = A.level_node_start[A.N + 1] - A.level_node_start[A.N];
     const int c4 = lane >> 4, ll = lane & 15;
@@ -192,10 +187,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
     // operands, requested one step ahead, take 4 k cycles to arrive while the step itself takes 600.  The three idle lane groups are put
     // to use as PREFETCH DEPTH: lane group q requests and holds the operands of the steps k = cl + q (mod 4), four steps are in flight,
     // and the steps are executed one after the other by "their" lane group on one shared set of step vectors (same arithmetic, same bits).
-#ifndef DOMPC_FW_DEEP
-#define DOMPC_FW_DEEP 1
-#endif
-    const bool deep = DOMPC_FW_DEEP && cw == 1;
+    const bool deep = cw == 1;
     const int kstep = deep ? 4 : 1;
     for (int s0 = cw * gid; s0 < S && cl < A.N; s0 += cw * ng) {
       const bool here = deep || (c4 < cw && s0 + c4 < S);
@@ -352,7 +344,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
                                        (__attribute__((address_space(3))) void*)(Ld + RF_MOC + 128 * q), 16, 0, 0);
   };
 #endif
-  // ---- adjoint recovery of the continuity multipliers (round 5, DOMPC_ADJ_REFINE).  The chain walk forms the step of the multipliers
+  // ---- adjoint recovery of the continuity multipliers (round 5).  The chain walk forms the step of the multipliers
   // of a node's incoming continuity rows as d nu = P dx + p.  Near the solution P carries the Sigma entries of active bounds further
   // down the chain (1e9 ... 1e11) in rank-one terms a a' whose contribution a (a' dx) is tiny in exact arithmetic: a' dx is a sum of
   // terms of size 1e-3 that cancel to 1e-11 and keeps an absolute error of 1e-19, times 2e11 = 2e-8 - the floor of the dual
@@ -381,9 +373,6 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
     T.sync();
   }
 #ifndef DOMPC_HOST_EMU
-#ifndef DOMPC_FE2
-#define DOMPC_FE2 1                 // per-edge part of the forward pass: two edges per wavefront (0: one)
-#endif
   // Two edges per wavefront.  The per-edge part keeps NW (<= 32) lanes busy - one row of the edge's block each - and is a sequence of
   // memory round trips and dependent sums like the chain walk above; lanes 0-31 now handle edge 2 p, lanes 32-63 edge 2 p + 1 of a pair,
   // each half with its own step vectors and staging buffer in LDS (the same arithmetic per row and the same order of every sum).
@@ -392,7 +381,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
   // (position in the compact record, or in a small pool of the model's constants kept in the slack of the staging buffer).
   constexpr int FE_HV = 128, FE_DY = 0, FE_DNU = 16, FE_G = 32, FE_DW = 64, FE_RHS = 96;      // step vectors of a half
   constexpr int FE_SS = EW_STAGE + MOC_STAGE, FE_STG = 2 * FE_HV, FE_POOL = EW_STAGE + MOC_SIZE, FE_TAB = FE_STG + 2 * FE_SS;
-  constexpr bool FE2 = (DOMPC_FE2 != 0) && MO_LDS && M > 0 && NI == 1 && DEG > 0 && !DENSE_EDGE && DOMPC_SHARD == 0 && NW <= 32 && NA <= 16 &&
+  constexpr bool FE2 = MO_LDS && M > 0 && NI == 1 && DEG > 0 && !DENSE_EDGE && DOMPC_SHARD == 0 && NW <= 32 && NA <= 16 &&
                        NA + NU <= 16 && NE <= 32 && (MOC_STAGE - MOC_SIZE >= 1 + DOMPC_DYN_NC) && (FE_TAB + 128 <= EL_SIZE) &&
                        (PT_STRIDE <= 2 * FE_SS) && LU_N < NW;
   if (QUAD_FWD && GS == 64 && !adj) {
@@ -444,14 +433,9 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
     struct EdgeU { int n, cn, row0, woff, uo; bool chain; };
     auto edge_u = [&](int e) {
       EdgeU u;
-#if DOMPC_EDGE_PACK
       const auto* ep = A.edge_pack + e * EP_N;
       u.n = ep[EP_PARENT]; u.cn = ep[EP_CHILD]; u.row0 = ep[EP_ROW0]; u.woff = ep[EP_WOFF];
       u.uo = ep[EP_UOFF_PARENT]; u.chain = ep[EP_LEVEL] >= cl;
-#else
-      u.n = A.edge_parent[e]; u.cn = A.edge_child[e]; u.row0 = A.edge_row0[e]; u.woff = A.edge_w_off[e];
-      u.uo = A.node_u_off[u.n]; u.chain = A.edge_level[e] >= cl;
-#endif
       return u;
     };
     auto stage2 = [&](int ea, int eb) {          // both edges of a pair: forward record + compact model-output record (exact size: the pool stays)

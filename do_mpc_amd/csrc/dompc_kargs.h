@@ -54,7 +54,7 @@ struct KArgs {
   // (16 uints apart), reduction partials ([2][wide][12] doubles) and shared flags (8 ints)
   int32_t wide;
   int32_t pool_doubles;      // doubles in the dynamic LDS pool of a workgroup: max(waves * EL_SIZE, RED_MAX * threads)
-  uint32_t* wide_bar;        // WIDE_BAR_STRIDE words per slot: [0] arrival counter, [1] XCD mask, [2] verdict, [8 + x] / [16 + x] / [24 + x]: arrival counter, release word and workgroup count of XCD x (two-level barrier)
+  uint32_t* wide_bar;        // WIDE_BAR_STRIDE words per slot: [0] arrival counter, [1] XCD mask, [2] verdict
   double* wide_partials;
   int32_t* wide_flags;
   // sweep (mode 2)

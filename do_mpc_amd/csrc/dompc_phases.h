@@ -103,7 +103,7 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
   LogAcc La{1.0, 0, 0};
   double lin = 0.0;                  // distances to the single bound of the one-sided variables (damping term, KAPPA_D)
   {                                  // trial point and its barrier terms in one pass
-    double x_[DOMPC_FW3], d_[DOMPC_FW3], l_[DOMPC_FW3], u2_[DOMPC_FW3];
+    double x_[DOMPC_FW], d_[DOMPC_FW], l_[DOMPC_FW], u2_[DOMPC_FW];
 #define L_(u, g) x_[u] = Q.x[g]; d_[u] = Q.dx[g]; l_[u] = Q.lb[g]; u2_[u] = Q.ub[g];
 #define B_(u, g)                                                                               \
     if (mk_x(A, g)) {                                                                      \
@@ -115,7 +115,7 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
         if (KAPPA_D != 0.0) { const double os_ = one_sided(l_[u], u2_[u]); lin += os_ > 0.0 ? xt_ - l_[u] : (os_ < 0.0 ? u2_[u] - xt_ : 0.0); } \
       }                                                                                    \
     }
-    DOMPC_FORN(DOMPC_FW3, nX, L_, B_)
+    DOMPC_FOR4(nX, L_, B_)
 #undef L_
 #undef B_
   }
@@ -130,10 +130,10 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
   r3[0] += trial_edges<FINE>(T, Q);
   T.sync();
   {
-    double c_[DOMPC_FW1];
+    double c_[DOMPC_FW];
 #define L_(u, g) c_[u] = Q.ct[g];
 #define B_(u, g) if (sh_cnt(A, mk_g(A, g))) r3[1] += fabs(c_[u]);
-    DOMPC_FORN(DOMPC_FW1, A.n_g, L_, B_)
+    DOMPC_FOR4(A.n_g, L_, B_)
 #undef L_
 #undef B_
   }
@@ -207,10 +207,10 @@ DOMPC_DEV inline Comp accept_pass(const Thr& T, const Prob& Q, double alpha, dou
     }
   }
   {
-    double y_[DOMPC_FW1], dy_[DOMPC_FW1];
+    double y_[DOMPC_FW], dy_[DOMPC_FW];
 #define L_(u, g) y_[u] = Q.lam[g]; dy_[u] = Q.dlam[g];
 #define B_(u, g) if (mk_g(A, g)) Q.lam[g] = y_[u] + alpha * dy_[u];
-    DOMPC_FORN(DOMPC_FW1, A.n_g, L_, B_)
+    DOMPC_FOR4(A.n_g, L_, B_)
 #undef L_
 #undef B_
   }
@@ -222,7 +222,6 @@ struct PhaseRet3 { unsigned gen, nred, xseq; double v0, v1, v2; };
 #define DOMPC_PHASE_PROLOGUE                                                        \
   const KArgs A = kernel_args(kp);                                                  \
   Thr T = make_thr(A);                                                              \
-  hier_setup(T);                                                                    \
   T.kp = kp;                                                                        \
   T.gen = ufl(gen); T.nred = ufl(nred); T.xseq = ufl(xseq);                         \
   Prob Q = make_prob(A, ufl(slot), A.p + (int64_t)ufl(b) * A.n_opt_p);              \

@@ -26,7 +26,6 @@
 // Measured effect: DESIGN.md section 4 / profiles/r06_*.
 #if !defined(DOMPC_HOST_EMU) && DOMPC_DEG >= 1 && DOMPC_M >= 1 && DOMPC_NI == 1 && DOMPC_NX + DOMPC_NU + 2 <= 16 && DOMPC_DEG * DOMPC_DEG * DOMPC_NX <= 64      // (array sizes and lane numbers below; the rest of the conditions: QUAD_EDGE, dompc_edge.h)
 
-#define DOMPC_HAVE_QUAD_HELPERS 1      // rbc / sfor / pin / QD_SB exist (dompc_riccati4.h)
 extern "C" __device__ double dompc_dpp_f64(double old, double src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) __asm("llvm.amdgcn.update.dpp.f64");
 // value of `v` in lane L of this lane's row of 16 lanes (v_mov_b64_dpp row_newbcast:L)
 template <int L>
@@ -41,16 +40,9 @@ __device__ inline void pin(int& v) { asm volatile("" : "+v"(v)); }
 // d += (value of `src` in lane L of the row of 16) * mul in ONE instruction: v_fmac_f64_dpp with the broadcast as the DPP operand.  The compiler
 // has the instruction but never folds a v_mov_b64_dpp into it, and an inline-asm DPP read is outside its hazard recogniser: the caller
 // guarantees that `src` was not written by one of the two preceding vector instructions (gfx9 DPP hazard: two wait states).
-#ifndef DOMPC_QUAD_FMAC_DPP
-#define DOMPC_QUAD_FMAC_DPP 1
-#endif
 template <int L>
 __device__ inline void fmac_rbc(double& d, const double& src, double mul) {
-#if DOMPC_QUAD_FMAC_DPP
   asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(d) : "v"(src), "v"(mul), "n"(L));
-#else
-  d = fma(rbc<L>(src), mul, d);
-#endif
 }
 template <class F, int... I>
 __device__ inline void sfor_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -109,14 +101,9 @@ __device__ inline void stage_quad(const Prob& Q, int e0, int lane, ldsd* Ld, int
 #ifndef DOMPC_QUAD_PROFILE
 #define DOMPC_QUAD_PROFILE DOMPC_PROFILE
 #endif
-#ifndef DOMPC_QUAD_SB
-#define DOMPC_QUAD_SB 1            // scheduling barriers between the pieces of a quad and between the pivots of its elimination: without them the
-#endif                             // machine scheduler stretches live ranges over the whole 9 000-instruction body and spills hundreds of registers
-#if DOMPC_QUAD_SB
+// scheduling barriers between the pieces of a quad and between the pivots of its elimination: without them the machine scheduler stretches
+// live ranges over the whole 9 000-instruction body and spills hundreds of registers
 #define QD_SB() __builtin_amdgcn_sched_barrier(0)
-#else
-#define QD_SB()
-#endif
 
 // Derivative evaluation, factorisation and condensing of the edges e0 .. e0 + 3 (edge e0 + (lane >> 4) on each row of 16 lanes; rows
 // beyond the last edge repeat it and store nothing).  `bank`: where stage_quad() put their compact records; `e0n`: first edge of the
@@ -360,10 +347,6 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
     for (int r = 0; r < R; ++r) bc[s][r] *= sig[s];
   QD_SB();
   if (__ballot(bad) != 0ull) return 2;
-#ifdef QD_CUT
-  if (st_x) { double t = 0; for (int s = 0; s < DEG; ++s) for (int r = 0; r < R; ++r) t += bc[s][r]; Q.ew[(int64_t)e * EW_SIZE + (int)b] = t + RWv[0] + SGv[1] + ry + rc + ce; }
-  return 0;
-#endif
   QD_PH(2)
   QD_SB();
   // now: lane b < NX, slot s: column (s, b) of G_cc^-1;  lanes NX .. NA-1, slot 0: G_cc^-1 J_u;  lane NA, slot 0: G_cc^-1 r

@@ -218,7 +218,6 @@ __device__ inline int node(const Prob& Q, int n, double mu, double delta, int la
   d4 qt_s, F, cvr;
   double fu, qv_s;
   staged_tiles(Ls, lane, qt_s, F, cvr, fu, qv_s);
-  DOMPC_PRIO_UP();
   R16_PN(12)
   // ---- own quadratic: per-variable terms in column layout (lane: z-entry j)
   double dg = 0.0, gv = 0.0;
@@ -415,7 +414,6 @@ __device__ inline int node(const Prob& Q, int n, double mu, double delta, int la
   // node (LDS-DMA copy, register prefetch): on gfx9 stores count in vmcnt like loads, so a wait for data issued after
   // a store also waits for the store's ~2 us round trip - waiting first and storing afterwards keeps the stores of
   // this node in flight during the whole update of the next one.
-  DOMPC_PRIO_DOWN();
   R16_PN(24)
   staged_ready();
   R16_PN(25)
@@ -432,11 +430,6 @@ __device__ inline int node(const Prob& Q, int n, double mu, double delta, int la
   return bad;
 }
 
-}  // namespace r16
-}  // namespace dompc
-#include "dompc_riccati4.h"      // four scenario chains per wavefront (uses NodeIn / load_node above)
-namespace dompc {
-namespace r16 {
 // Backward recursion of one problem (all wavefronts of the problem take part; same protocol as riccati_backward).
 __device__ inline int backward(const Thr& T, const Prob& Q, double mu, double delta) {
   const KArgs& A = *Q.A;
@@ -444,46 +437,40 @@ __device__ inline int backward(const Thr& T, const Prob& Q, double mu, double de
   ldsd* Ld = T.edge_lds + (int64_t)(T.ltid / 64) * EL_SIZE;      // this wavefront's LDS region: two staging buffers
   const int FSET = T.flag_begin(0);
   const int cl = A.chain_level < A.N ? A.chain_level : A.N;
-  if constexpr (r4::ENABLED) {
-    if (r4::chains(T, Q, mu, delta, cl)) T.fset(0, FSET);
-    T.sync();
-    if ((T.fget(0) == FSET)) return 1;
-  } else {
-    const int S = A.level_node_start[A.N + 1] - A.level_node_start[A.N];
-    for (int s_ = gid; s_ < S; s_ += ng) {
-      NodeIn in;
-      int buf = 0;
-      if (A.N - 1 >= cl) {
-        const int n1 = A.level_node_start[A.N - 1] + s_;
-        load_node(Q, n1, lane, in);
-        stage_edge(Q, A.node_child_start[n1], lane, Ld);
-      }
-      Val V = leaf(Q, A.level_node_start[A.N] + s_, mu, delta, lane);
-      store_val(Q, A.level_node_start[A.N] + s_, V, lane);
-      staged_ready();              // the staged record of the first node has landed (later ones: waited for inside node())
-      for (int k = A.N - 1; k >= cl; --k) {
-        NodeIn nx;                 // the parent's operands: in flight while this node is updated
-#if DOMPC_PROFILE
-        const long long pcl = prof_clock();
-#endif
-        if (k > cl) {
-          const int np = A.level_node_start[k - 1] + s_;
-          load_node(Q, np, lane, nx);
-          stage_edge(Q, A.node_child_start[np], lane, Ld + (buf ^ 1) * ES_STAGE);
-        }
-#if DOMPC_PROFILE
-        if (threadIdx.x == 0) lds_prof[27] += prof_clock() - pcl;
-#endif
-        Val Vn;
-        if (node(Q, A.level_node_start[k] + s_, mu, delta, lane, in, Ld + buf * ES_STAGE, &V, Vn)) { T.fset(0, FSET); break; }
-        V = Vn;
-        if (k > cl) in = nx;
-        buf ^= 1;
-      }
+  const int S = A.level_node_start[A.N + 1] - A.level_node_start[A.N];
+  for (int s_ = gid; s_ < S; s_ += ng) {
+    NodeIn in;
+    int buf = 0;
+    if (A.N - 1 >= cl) {
+      const int n1 = A.level_node_start[A.N - 1] + s_;
+      load_node(Q, n1, lane, in);
+      stage_edge(Q, A.node_child_start[n1], lane, Ld);
     }
-    T.sync();
-    if ((T.fget(0) == FSET)) return 1;
+    Val V = leaf(Q, A.level_node_start[A.N] + s_, mu, delta, lane);
+    store_val(Q, A.level_node_start[A.N] + s_, V, lane);
+    staged_ready();              // the staged record of the first node has landed (later ones: waited for inside node())
+    for (int k = A.N - 1; k >= cl; --k) {
+      NodeIn nx;                 // the parent's operands: in flight while this node is updated
+#if DOMPC_PROFILE
+      const long long pcl = prof_clock();
+#endif
+      if (k > cl) {
+        const int np = A.level_node_start[k - 1] + s_;
+        load_node(Q, np, lane, nx);
+        stage_edge(Q, A.node_child_start[np], lane, Ld + (buf ^ 1) * ES_STAGE);
+      }
+#if DOMPC_PROFILE
+      if (threadIdx.x == 0) lds_prof[27] += prof_clock() - pcl;
+#endif
+      Val Vn;
+      if (node(Q, A.level_node_start[k] + s_, mu, delta, lane, in, Ld + buf * ES_STAGE, &V, Vn)) { T.fset(0, FSET); break; }
+      V = Vn;
+      if (k > cl) in = nx;
+      buf ^= 1;
+    }
   }
+  T.sync();
+  if ((T.fget(0) == FSET)) return 1;
   for (int k = cl - 1; k >= 0; --k) {
     const int n0 = A.level_node_start[k], n1 = A.level_node_start[k + 1];
     for (int n = n0 + gid; n < n1; n += ng) {

@@ -1,5 +1,5 @@
 """Pre-build the industrial_poly code objects of several DOMPC_DEFS sets (bench and profile variants) so that one GPU call
-can A/B them:  python tools/ab_prebuild.py "DOMPC_MFMA_GJ=0" "DOMPC_EF_INLINE=1" ...   ('' = the product build)"""
+can A/B them:  python tools/ab_prebuild.py "DOMPC_QUAD=0" "DOMPC_GJ_U=1e9" ...   ('' = the product build)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import __graft_entry__ as g

@@ -1,5 +1,5 @@
 """Members of the timed batch (B = 16384) against oracle solves, for a list of DOMPC_DEFS build variants: iteration counts per member,
-batch mean, kernel time.   python tools/gpu_timed_members.py "" "DOMPC_ADJ_REFINE=1" ..."""
+batch mean, kernel time.   python tools/gpu_timed_members.py "" "DOMPC_FW=16" ..."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
