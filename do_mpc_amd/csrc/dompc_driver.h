@@ -69,8 +69,9 @@ DOMPC_DEV inline void epsg_residual(const Thr& T, const Prob& Q, const double* v
 }
 
 // ================================================================================================
-DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slot) {
+DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slot0) {
   const dompc_options& O = A.opt;
+  int slot = slot0;      // (+ SLOT_PARITY while the live iterate is in the second copy, inside the loop below)
   Prob Q = make_prob(A, slot, A.p + (int64_t)b * A.n_opt_p);
   const double* x0 = A.x0 + (int64_t)b * A.n_opt_x;
   const int nX = A.n_opt_x, nSl = A.n_edges * NE;
@@ -397,6 +398,13 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
   double wd_theta = 0.0, wd_phi = 0.0, wd_dphi = 0.0, wd_alpha = 0.0, wd_amax = 0.0, wd_az = 0.0, wd_delta = 0.0, wd_delta_last = 0.0, wd_bar = 0.0;
   Errs wd_E = E;
   double delta = 0.0, a_max = 1.0, a_z = 1.0, dphi = 0.0;
+  // both copies of the iterate start out equal: the trial evaluation writes the entries that move (this rank's variables, multipliers of
+  // finite bounds), all others - zero multipliers of absent bounds, unused variables that were taken out - keep these values in both
+  for (int g = T.tid; g < nX; g += T.nt) { Q.xt[g] = Q.x[g]; Q.zlt[g] = Q.zl[g]; Q.zut[g] = Q.zu[g]; }
+  for (int g = T.tid; g < A.n_g; g += T.nt) Q.lamt[g] = Q.lam[g];
+  for (int g = T.tid; g < nSl; g += T.nt) { Q.st[g] = Q.s[g]; Q.zslt[g] = Q.zsl[g]; Q.zsut[g] = Q.zsu[g]; }
+  T.sync();
+  Comp Cp{-INFINITY, INFINITY, 0.0};      // complementarity partials of the last evaluated trial point (this thread's share)
 
   while (true) {
     bool skip_first = false;
@@ -513,9 +521,10 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     else if (dphi < 0.0) a_min = gamma_alpha * fmin(gamma_theta, gamma_phi * theta / (-dphi));
     else a_min = gamma_alpha * gamma_theta;
     a_min = fmax(a_min, 1e-14);
-    // objective, constraint violation and barrier sum of the trial point x + al * dx (left in Q.xt / Q.st, constraint values in Q.ct)
-    auto eval_trial = [&](double al, double& obj_o, double& th_o, double& bar_o) {
-      run_eval_trial(T, Q, b, slot, al, obj_o, th_o, bar_o);
+    // objective, constraint violation and barrier sum of the trial point x + al * dx; the point itself, with the multipliers it would have as
+    // the next iterate (bound multipliers: step az), is left in the second copy of the iterate, its constraint values in Q.ct
+    auto eval_trial = [&](double al, double az, double& obj_o, double& th_o, double& bar_o) {
+      run_eval_trial(T, Q, b, slot, al, az, mu, obj_o, th_o, bar_o, Cp);
       ++n_trials;
     };
     // filter / sufficient-decrease tests of a trial point reached with step size al (IPOPT eqs. (18)-(20))
@@ -572,7 +581,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
       wd_theta = theta; wd_phi = phi; wd_dphi = dphi; wd_alpha = a_max;
     }
     if (in_wd) {
-      eval_trial(alpha, obj_t, th_t, bar_t);
+      eval_trial(alpha, a_z, obj_t, th_t, bar_t);
       bool armijo_case = false;
       if (acceptable_ref(th_t, obj_t + mu * bar_t, wd_alpha, armijo_case, wd_theta, wd_phi, wd_dphi)) {
         accepted = true; armijo_used = armijo_case; wd_done = true; wd_augment_ref = true;
@@ -588,7 +597,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
       }
     }
     while (!wd_done) {
-      eval_trial(alpha, obj_t, th_t, bar_t);
+      eval_trial(alpha, a_z, obj_t, th_t, bar_t);
       stale = false;
       bool armijo_case = false;
       if (acceptable(th_t, obj_t + mu * bar_t, alpha, armijo_case)) { accepted = true; armijo_used = armijo_case; break; }
@@ -612,13 +621,14 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
           double q5[5];
           step_rules(q5);
           const double a_s = (q5[0] > tau) ? tau / q5[0] : 1.0;
+          const double az_s = (q5[1] > tau) ? tau / q5[1] : 1.0;      // (the corrected step brings its own multiplier step size)
           double obj_s = 0.0, th_s = 0.0, bar_s = 0.0;
-          eval_trial(a_s, obj_s, th_s, bar_s);
+          eval_trial(a_s, az_s, obj_s, th_s, bar_s);
           bool arm_s = false;
           if (acceptable(th_s, obj_s + mu * bar_s, a_s, arm_s)) {
             accepted = true; armijo_used = arm_s; soc_ok = true;
             alpha = a_s;
-            a_z = (q5[1] > tau) ? tau / q5[1] : 1.0;
+            a_z = az_s;
             obj_t = obj_s; th_t = th_s; bar_t = bar_s;
             break;
           }
@@ -628,14 +638,14 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
         }
         if (soc_ok) break;
         keep_direction(true);                             // back to the Newton direction of this iterate
-        stale = true;                                     // (Q.xt / Q.st / Q.ct hold the last corrected trial point)
+        stale = true;                                     // (the second copy of the iterate and Q.ct hold the last corrected trial point)
       }
-      if (!(alpha * 0.5 >= a_min)) break;  // xt/st/ct stay at the last evaluated alpha (also leaves on a NaN step size)
+      if (!(alpha * 0.5 >= a_min)) break;  // the trial point stays at the last evaluated alpha (also leaves on a NaN step size)
       alpha *= 0.5;
       ++n_ls;
     }
     if (bad) { if (in_wd) { bad = 0; wd_resume = true; in_wd = false; wd_count = 0; continue; } status = 3; break; }      // (same rule as at the top of the loop)
-    if (!accepted && stale) eval_trial(alpha, obj_t, th_t, bar_t);
+    if (!accepted && stale) eval_trial(alpha, a_z, obj_t, th_t, bar_t);
     if (!wd_done) wd_count = n_ls > 0 ? wd_count + 1 : 0;         // consecutive iterations with a shortened step
     if (!accepted) {
       // no restoration phase: take the smallest trial step and reset the filter
@@ -650,18 +660,17 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
       if (n_filt < MAX_FILTER) ++n_filt;
       T.lsync();
     }
-    bar_sum = bar_t;                  // xt of the last evaluated trial becomes the iterate
+    bar_sum = bar_t;                  // the last evaluated trial point becomes the iterate
     c_ls += prof_clock() - c_t; g_ls += T.gen - g_t;
-    // ---- accept the trial point
+    // ---- accept the trial point: it is complete (eval_trial_pass), its copy becomes the live one
     c_t = prof_clock(); g_t = T.gen;
-    const Comp Cp = run_accept(T, Q, b, slot, alpha, a_z, mu);
+    prob_flip(Q); slot = Q.slot;
     if (A.trace && b == 0 && T.tid == 0 && it < A.trace_cap) {
       double* tr = A.trace + 8 * it;
       tr[0] = it; tr[1] = mu; tr[2] = E0; tr[3] = E.e_p; tr[4] = E.e_d; tr[5] = accepted ? alpha : -alpha;
       tr[6] = delta; tr[7] = E.obj / Q.sf;
     }
-    if (T.tid == 0) T.fset(6, abort_requested(A));
-    T.sync();
+    if (T.tid == 0) T.fset(6, abort_requested(A));      // (read at the top of the loop, behind the barriers of the sweep)
     c_acc += prof_clock() - c_t; g_acc += T.gen - g_t;
     ++it;
     c_t = prof_clock(); g_t = T.gen; bad = run_sweep(T, Q, b, slot, mu, 0, singular0 ? delta_after(delta_last) : 0.0); c_sweep += prof_clock() - c_t; g_sweep += T.gen - g_t;
@@ -671,6 +680,14 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     c_t = prof_clock(); g_t = T.gen; E = measure(T, Q, &Cp); c_meas += prof_clock() - c_t; g_meas += T.gen - g_t;
   }
 
+  // ---- nothing outside this loop knows about the two copies: the final iterate goes to the primary arrays
+  if (slot & SLOT_PARITY) {
+    for (int g = T.tid; g < nX; g += T.nt) { Q.xt[g] = Q.x[g]; Q.zlt[g] = Q.zl[g]; Q.zut[g] = Q.zu[g]; }
+    for (int g = T.tid; g < A.n_g; g += T.nt) Q.lamt[g] = Q.lam[g];
+    for (int g = T.tid; g < nSl; g += T.nt) { Q.st[g] = Q.s[g]; Q.zslt[g] = Q.zsl[g]; Q.zsut[g] = Q.zsu[g]; }
+    T.sync();
+    prob_flip(Q); slot = Q.slot;
+  }
   // ---- outputs (unscaled multipliers, CasADi sign convention)
   if (A.trace && b == 0 && T.tid == 0 && A.trace_cap > 8) { double* tr = A.trace + 8 * (A.trace_cap - 1); tr[0] = (double)c_sweep; tr[1] = (double)c_bwd; tr[2] = (double)c_fwd; tr[3] = (double)c_ls; tr[4] = (double)c_meas; tr[5] = (double)(prof_clock() - c_start); tr[6] = (double)c_ftb; tr[7] = (double)c_acc; if (T.prof) { double* t2 = A.trace + 8 * (A.trace_cap - 2); for (int i = 0; i < 8; ++i) t2[i] = (double)T.prof[i]; double* t3 = A.trace + 8 * (A.trace_cap - 3); for (int i = 0; i < 8; ++i) t3[i] = (double)T.prof[8 + i]; double* t4 = A.trace + 8 * (A.trace_cap - 4); for (int i = 0; i < 8; ++i) t4[i] = (double)T.prof[16 + i]; if (A.trace_cap > 12) { double* t5 = A.trace + 8 * (A.trace_cap - 5); for (int i = 0; i < 8; ++i) t5[i] = (double)T.prof[24 + i]; double* t6 = A.trace + 8 * (A.trace_cap - 6); t6[0] = g_sweep; t6[1] = g_bwd; t6[2] = g_fwd; t6[3] = g_ls; t6[4] = g_meas; t6[5] = T.gen - g_start; t6[6] = g_ftb; t6[7] = g_acc; } } }
   const double isf = 1.0 / Q.sf;

@@ -224,6 +224,7 @@ struct WsLayout {
   int64_t s, zsl, zsu, sl, su, ds, st, ds_sv;
   int64_t ew, es, nd, mo, gsc, total;
   int64_t x_wd, zl_wd, zu_wd, lam_wd, s_wd, zsl_wd, zsu_wd, dlam_e, sgn;      // watchdog: the iterate it started from; EPS_GLOBAL: scratch multiplier steps
+  int64_t zlt, zut, lamt, zslt, zsut;                                          // second copy of the multipliers (xt / st are the ones of x / s): SLOT_PARITY
 };
 
 DOMPC_HD inline WsLayout ws_layout(int n_opt_x, int n_g, int n_edges, int e_pad, int n_nodes) {
@@ -247,6 +248,7 @@ DOMPC_HD inline WsLayout ws_layout(int n_opt_x, int n_g, int n_edges, int e_pad,
   L.s_wd = take(nsl); L.zsl_wd = take(nsl); L.zsu_wd = take(nsl);
   L.dlam_e = take(EPS_GLOBAL ? n_g : 0);
   L.sgn = take(nsl);              // scaling factors of the nl_cons rows (IPOPT's gradient-based constraint scaling, solve_problem)
+  L.zlt = take(n_opt_x); L.zut = take(n_opt_x); L.lamt = take(n_g); L.zslt = take(nsl); L.zsut = take(nsl);
   o += 256;                       // slack: block-granular staging reads of the last records may run past their end
   L.total = o;
   return L;
@@ -654,6 +656,7 @@ struct Prob {
   double *s, *zsl, *zsu, *sl, *su, *ds, *st, *ds_sv;
   double *ew, *es, *nd, *mo, *gsc;
   double *x_wd, *zl_wd, *zu_wd, *lam_wd, *s_wd, *zsl_wd, *zsu_wd, *dlam_e, *sgn;
+  double *zlt, *zut, *lamt, *zslt, *zsut;            // multipliers of the trial point (x, s: xt, st above), written by the trial evaluation
   int e_pad;
   double sf;                                         // objective scaling
   double mu;
@@ -664,7 +667,7 @@ struct Prob {
   double dsw;                                        // inertia correction that the sweep has already folded into the condensed blocks
                                                      // (Sigma_w + dsw in Q~, q~ and in the stored Sigma_w): the Riccati passes add
                                                      // only delta - dsw on the eliminated variables (0 in the common case)
-  int slot;                                          // workspace slot of the problem (rebuilds this view inside outlined functions)
+  int slot;                                          // workspace slot of the problem, with SLOT_PARITY (rebuilds this view inside outlined functions)
   int rp_soc; double rp_mu;                          // DOMPC_REPEAT_PHASE (measurement builds): arguments of the last sweep
   int lu_ok;                                         // QUAD_FWD: the forward records hold G_cc^-1 (the last sweep stored it: lu_store_rule)
   DOMPC_DEV double& EW(int e, int i) const { return ew[(int64_t)e * EW_SIZE + i]; }
@@ -673,9 +676,21 @@ struct Prob {
   DOMPC_DEV double* MO(int e) const { return mo + (int64_t)e * MO_REC; }
 };
 
+// The iterate (x, s, bound and constraint multipliers) has two copies per slot.  The trial evaluation of the line search writes the complete
+// trial point - multipliers included - into the copy that is not live, and accepting it flips the bit SLOT_PARITY of the `slot` value
+// that travels to every outlined phase: no pass copies a trial point into the iterate.  Bit clear: the live iterate is in the primary
+// arrays (always the case outside the interior-point loop of solve_problem).
+constexpr int SLOT_PARITY = 1 << 30;
+template <class T_> DOMPC_DEV inline void swap_ptr(T_*& a, T_*& b) { T_* t = a; a = b; b = t; }
+// the trial point becomes the iterate and the other way round
+DOMPC_DEV inline void prob_flip(Prob& p) {
+  swap_ptr(p.x, p.xt); swap_ptr(p.zl, p.zlt); swap_ptr(p.zu, p.zut); swap_ptr(p.lam, p.lamt);
+  swap_ptr(p.s, p.st); swap_ptr(p.zsl, p.zslt); swap_ptr(p.zsu, p.zsut);
+  p.slot ^= SLOT_PARITY;
+}
 DOMPC_DEV inline Prob make_prob(const KArgs& A, int slot, const double* P) {
   WsLayout L = ws_layout(A.n_opt_x, A.n_g, A.n_edges, A.e_pad, A.n_nodes);
-  double* w = A.ws + (int64_t)slot * A.ws_stride;
+  double* w = A.ws + (int64_t)(slot & ~SLOT_PARITY) * A.ws_stride;
   Prob p;
   p.A = &A; p.P = P;
   p.x = w + L.x; p.zl = w + L.zl; p.zu = w + L.zu; p.lb_own = w + L.lb; p.ub_own = w + L.ub; p.dx = w + L.dx;
@@ -687,7 +702,9 @@ DOMPC_DEV inline Prob make_prob(const KArgs& A, int slot, const double* P) {
   p.ew = w + L.ew; p.es = w + L.es; p.nd = w + L.nd; p.mo = w + L.mo; p.gsc = w + L.gsc;
   p.x_wd = w + L.x_wd; p.zl_wd = w + L.zl_wd; p.zu_wd = w + L.zu_wd; p.lam_wd = w + L.lam_wd;
   p.s_wd = w + L.s_wd; p.zsl_wd = w + L.zsl_wd; p.zsu_wd = w + L.zsu_wd; p.dlam_e = w + L.dlam_e; p.sgn = w + L.sgn;
-  p.e_pad = A.e_pad; p.sf = 1.0; p.mu = 0.0; p.soc = 0; p.dsw = 0.0; p.slot = slot; p.lu_ok = 1; p.rp_soc = 0; p.rp_mu = 0.0;
+  p.zlt = w + L.zlt; p.zut = w + L.zut; p.lamt = w + L.lamt; p.zslt = w + L.zslt; p.zsut = w + L.zsut;
+  p.e_pad = A.e_pad; p.sf = 1.0; p.mu = 0.0; p.soc = 0; p.dsw = 0.0; p.slot = slot & ~SLOT_PARITY; p.lu_ok = 1; p.rp_soc = 0; p.rp_mu = 0.0;
+  if (slot & SLOT_PARITY) prob_flip(p);
   return p;
 }
 // Bounds the phases read: ONE copy for all problems of the launch (KArgs::lb_sh / ub_sh) - except while the least-squares multiplier

@@ -1,6 +1,6 @@
 // dompc_phases.h - structured interior-point solver, part of dompc_kernel.h (included there, inside namespace dompc, in this order:
 // dompc_edge.h, dompc_factor.h, dompc_node.h, dompc_riccati.h, dompc_forward.h, dompc_sweep.h, dompc_phases.h, dompc_driver.h).
-// Contents: thread-parallel vector passes (error measures, step rules, line search, accept) and the outlined phases of the device build.
+// Contents: thread-parallel vector passes (error measures, step rules, line search) and the outlined phases of the device build.
 // Sizes, record layouts, the thread context `Thr`, reductions and the small dense products are in dompc_kernel.h.
 
 // ================================================================================================
@@ -94,25 +94,48 @@ DOMPC_DEV inline void step_rules_pass(const Thr& T, const Prob& Q, double mu, do
   const int ops[5] = {R_MAX, R_MAX, R_SUM, R_SUM, R_SUM};
   wg_reduce(T, r5, ops);
 }
-// objective, constraint violation and barrier sum of the trial point x + al * dx (left in Q.xt / Q.st, constraint values in Q.ct)
+// objective, constraint violation and barrier sum of the trial point x + al * dx, and the trial point itself in full: x, s (Q.xt / Q.st),
+// bound multipliers (step a_z, safeguarded: Q.zlt / Q.zut / Q.zslt / Q.zsut) and constraint multipliers (step al: Q.lamt), constraint
+// values in Q.ct.  Accepting the point is a flip of the slot's parity (prob_flip, solve_problem); a rejected one is overwritten by the
+// next trial.  Cp: this thread's complementarity statistics of the trial point (consumed by measure() after the sweep of the new iterate).
 template <bool FINE>
-DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, double& obj_o, double& th_o, double& bar_o) {
+DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, double a_z, double mu, double& obj_o, double& th_o, double& bar_o, Comp& Cp) {
   const KArgs& A = *Q.A;
   const int nX = A.n_opt_x, nSl = A.n_edges * NE;
+  const double ks = 1e10;
   double r3[3] = {0.0, 0.0, 0.0};    // obj, theta, barrier
   LogAcc La{1.0, 0, 0};
   double lin = 0.0;                  // distances to the single bound of the one-sided variables (damping term, KAPPA_D)
-  {                                  // trial point and its barrier terms in one pass
-    double x_[DOMPC_FW], d_[DOMPC_FW], l_[DOMPC_FW], u2_[DOMPC_FW];
-#define L_(u, g) x_[u] = Q.x[g]; d_[u] = Q.dx[g]; l_[u] = Q.lb[g]; u2_[u] = Q.ub[g];
+  Cp = Comp{-INFINITY, INFINITY, 0.0};
+  {                                  // trial point, its bound multipliers and its barrier terms in one pass
+    double x_[DOMPC_FW], d_[DOMPC_FW], l_[DOMPC_FW], u2_[DOMPC_FW], zl_[DOMPC_FW], zu_[DOMPC_FW];
+#define L_(u, g) x_[u] = Q.x[g]; d_[u] = Q.dx[g]; l_[u] = Q.lb[g]; u2_[u] = Q.ub[g]; zl_[u] = Q.zl[g]; zu_[u] = Q.zu[g];
 #define B_(u, g)                                                                               \
     if (mk_x(A, g)) {                                                                      \
       const double xt_ = x_[u] + al * d_[u];                                               \
+      const double xv = xt_, l = l_[u], ub_ = u2_[u];                                      \
+      const bool cnt_ = sh_cnt(A, mk_x(A, g));                                             \
       Q.xt[g] = xt_;                                                                       \
-      if (sh_cnt(A, mk_x(A, g))) {                                                         \
+      if (cnt_) {                                                                          \
         if (l_[u] > -INFINITY) logacc_add(La, xt_ - l_[u]);                                \
         if (u2_[u] < INFINITY) logacc_add(La, u2_[u] - xt_);                               \
         if (KAPPA_D != 0.0) { const double os_ = one_sided(l_[u], u2_[u]); lin += os_ > 0.0 ? xt_ - l_[u] : (os_ < 0.0 ? u2_[u] - xt_ : 0.0); } \
+      }                                                                                    \
+      if (l > -INFINITY) {                                                                 \
+        const double ro = fast_rcp(x_[u] - l);                     /* dz_lo with 1/(x - l) */  \
+        const double z = zl_[u] + a_z * (mu * ro - zl_[u] - zl_[u] * ro * d_[u]);          \
+        const double dd = xv - l, mr = mu * fast_rcp(dd);                                  \
+        const double zn = fmax(fmin(z, ks * mr), mr * (1.0 / ks));                         \
+        Q.zlt[g] = zn;                                                                     \
+        if (cnt_) comp_add(Cp, dd * zn, zn);                                               \
+      }                                                                                    \
+      if (ub_ < INFINITY) {                                                                \
+        const double ro = fast_rcp(ub_ - x_[u]);                                           \
+        const double z = zu_[u] + a_z * (mu * ro - zu_[u] + zu_[u] * ro * d_[u]);          \
+        const double dd = ub_ - xv, mr = mu * fast_rcp(dd);                                \
+        const double zn = fmax(fmin(z, ks * mr), mr * (1.0 / ks));                         \
+        Q.zut[g] = zn;                                                                     \
+        if (cnt_) comp_add(Cp, dd * zn, zn);                                               \
       }                                                                                    \
     }
     DOMPC_FOR4(nX, L_, B_)
@@ -122,7 +145,31 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
   for (int g = T.tid; g < nSl; g += T.nt) {
     if (!mk_e(A, g / NE1)) continue;
     const int si = (g / NE1) * NE1 + g % NE1;
-    Q.st[si] = Q.s[si] + al * Q.ds[si];
+    const double so = Q.s[si], dsv = Q.ds[si];
+    const double sv = so + al * dsv;
+    const bool cnt_ = sh_cnt(A, mk_e(A, g / NE1));
+    Q.st[si] = sv;
+    const double l = Q.sl[si], u = Q.su[si];
+    if (l > -INFINITY) {
+      const double z = Q.zsl[si] + a_z * dz_lo(so, l, Q.zsl[si], dsv, mu);
+      const double zn = fmax(fmin(z, ks * mu / (sv - l)), mu / (ks * (sv - l)));
+      Q.zslt[si] = zn;
+      if (cnt_) comp_add(Cp, (sv - l) * zn, zn);
+    }
+    if (u < INFINITY) {
+      const double z = Q.zsu[si] + a_z * dz_up(so, u, Q.zsu[si], dsv, mu);
+      const double zn = fmax(fmin(z, ks * mu / (u - sv)), mu / (ks * (u - sv)));
+      Q.zsut[si] = zn;
+      if (cnt_) comp_add(Cp, (u - sv) * zn, zn);
+    }
+  }
+  {
+    double y_[DOMPC_FW], dy_[DOMPC_FW];
+#define L_(u, g) y_[u] = Q.lam[g]; dy_[u] = Q.dlam[g];
+#define B_(u, g) if (mk_g(A, g)) Q.lamt[g] = y_[u] + al * dy_[u];
+    DOMPC_FOR4(A.n_g, L_, B_)
+#undef L_
+#undef B_
   }
   T.sync();
   for (int g = T.tid; g < NX; g += T.nt) Q.ct[g] = FREE_ROOT ? 0.0 : Q.xt[A.node_x_off[0] + g] - Q.P[g] / DOMPC_SX[g];
@@ -150,74 +197,9 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
   wg_reduce(T, r3, ops);
   obj_o = r3[0]; th_o = r3[1]; bar_o = r3[2];
 }
-// the trial point becomes the iterate: x, s, bound multipliers (step a_z, safeguarded) and constraint multipliers (step alpha);
-// returns this thread's complementarity statistics of the new iterate (consumed by measure() after the sweep)
-DOMPC_DEV inline Comp accept_pass(const Thr& T, const Prob& Q, double alpha, double a_z, double mu) {
-  const KArgs& A = *Q.A;
-  const int nX = A.n_opt_x, nSl = A.n_edges * NE;
-  const double ks = 1e10;
-  Comp Cp{-INFINITY, INFINITY, 0.0};       // complementarity statistics of the new iterate (consumed by measure() after the sweep)
-  {
-    double xt_[DOMPC_FW], x_[DOMPC_FW], d_[DOMPC_FW], l_[DOMPC_FW], u2_[DOMPC_FW], zl_[DOMPC_FW], zu_[DOMPC_FW];
-#define L_(u, g) xt_[u] = Q.xt[g]; x_[u] = Q.x[g]; d_[u] = Q.dx[g]; l_[u] = Q.lb[g]; u2_[u] = Q.ub[g]; zl_[u] = Q.zl[g]; zu_[u] = Q.zu[g];
-#define B_(u, g)                                                                               \
-    if (mk_x(A, g)) {                                                                        \
-      const double xv = xt_[u], l = l_[u], ub_ = u2_[u];                                     \
-      const bool cnt_ = sh_cnt(A, mk_x(A, g));                                               \
-      Q.x[g] = xv;                                                                           \
-      if (l > -INFINITY) {                                                                   \
-        const double ro = fast_rcp(x_[u] - l);                     /* dz_lo with 1/(x - l) */  \
-        const double z = zl_[u] + a_z * (mu * ro - zl_[u] - zl_[u] * ro * d_[u]);            \
-        const double dd = xv - l, mr = mu * fast_rcp(dd);                                    \
-        const double zn = fmax(fmin(z, ks * mr), mr * (1.0 / ks));                           \
-        Q.zl[g] = zn;                                                                        \
-        if (cnt_) comp_add(Cp, dd * zn, zn);                                                 \
-      }                                                                                      \
-      if (ub_ < INFINITY) {                                                                  \
-        const double ro = fast_rcp(ub_ - x_[u]);                                             \
-        const double z = zu_[u] + a_z * (mu * ro - zu_[u] + zu_[u] * ro * d_[u]);            \
-        const double dd = ub_ - xv, mr = mu * fast_rcp(dd);                                  \
-        const double zn = fmax(fmin(z, ks * mr), mr * (1.0 / ks));                           \
-        Q.zu[g] = zn;                                                                        \
-        if (cnt_) comp_add(Cp, dd * zn, zn);                                                 \
-      }                                                                                      \
-    }
-    DOMPC_FOR4(nX, L_, B_)
-#undef L_
-#undef B_
-  }
-  for (int g = T.tid; g < nSl; g += T.nt) {
-    if (!mk_e(A, g / NE1)) continue;
-    const int si = (g / NE1) * NE1 + g % NE1;
-    const double sv = Q.st[si], so = Q.s[si], dsv = Q.ds[si];
-    const bool cnt_ = sh_cnt(A, mk_e(A, g / NE1));
-    Q.s[si] = sv;
-    const double l = Q.sl[si], u = Q.su[si];
-    if (l > -INFINITY) {
-      const double z = Q.zsl[si] + a_z * dz_lo(so, l, Q.zsl[si], dsv, mu);
-      const double zn = fmax(fmin(z, ks * mu / (sv - l)), mu / (ks * (sv - l)));
-      Q.zsl[si] = zn;
-      if (cnt_) comp_add(Cp, (sv - l) * zn, zn);
-    }
-    if (u < INFINITY) {
-      const double z = Q.zsu[si] + a_z * dz_up(so, u, Q.zsu[si], dsv, mu);
-      const double zn = fmax(fmin(z, ks * mu / (u - sv)), mu / (ks * (u - sv)));
-      Q.zsu[si] = zn;
-      if (cnt_) comp_add(Cp, (u - sv) * zn, zn);
-    }
-  }
-  {
-    double y_[DOMPC_FW], dy_[DOMPC_FW];
-#define L_(u, g) y_[u] = Q.lam[g]; dy_[u] = Q.dlam[g];
-#define B_(u, g) if (mk_g(A, g)) Q.lam[g] = y_[u] + alpha * dy_[u];
-    DOMPC_FOR4(A.n_g, L_, B_)
-#undef L_
-#undef B_
-  }
-  return Cp;
-}
 struct PhaseRet { unsigned gen, nred, xseq; int rc; };
 struct PhaseRet3 { unsigned gen, nred, xseq; double v0, v1, v2; };
+struct PhaseRet6 { unsigned gen, nred, xseq; double v0, v1, v2, c0, c1, c2; };      // c*: thread-local Comp partials
 #ifndef DOMPC_HOST_EMU
 #define DOMPC_PHASE_PROLOGUE                                                        \
   const KArgs A = kernel_args(kp);                                                  \
@@ -268,22 +250,19 @@ __device__ __attribute__((noinline)) PhaseRet3 phase_step_rules(const void* kp, 
   step_rules_pass(T, Q, ufl(mu), r5);
   return PhaseRet3{T.gen, T.nred, T.xseq, r5[0], r5[1], r5[2]};
 }
-__device__ __attribute__((noinline)) PhaseRet3 phase_eval_trial(const void* kp, int b, int slot, double sf, double al, unsigned gen, unsigned nred, unsigned xseq) {
+__device__ __attribute__((noinline)) PhaseRet6 phase_eval_trial(const void* kp, int b, int slot, double sf, double al, double a_z, double mu, unsigned gen, unsigned nred, unsigned xseq) {
   DOMPC_PHASE_PROLOGUE
   double o = 0.0, th = 0.0, br = 0.0;
-  eval_trial_pass<false>(T, Q, ufl(al), o, th, br);
-  return PhaseRet3{T.gen, T.nred, T.xseq, o, th, br};
+  Comp C;
+  eval_trial_pass<false>(T, Q, ufl(al), ufl(a_z), ufl(mu), o, th, br, C);
+  return PhaseRet6{T.gen, T.nred, T.xseq, o, th, br, C.smax, C.smin, C.sum_z};
 }
-__device__ __attribute__((noinline)) PhaseRet3 phase_eval_trial_fine(const void* kp, int b, int slot, double sf, double al, unsigned gen, unsigned nred, unsigned xseq) {
+__device__ __attribute__((noinline)) PhaseRet6 phase_eval_trial_fine(const void* kp, int b, int slot, double sf, double al, double a_z, double mu, unsigned gen, unsigned nred, unsigned xseq) {
   DOMPC_PHASE_PROLOGUE
   double o = 0.0, th = 0.0, br = 0.0;
-  eval_trial_pass<true>(T, Q, ufl(al), o, th, br);
-  return PhaseRet3{T.gen, T.nred, T.xseq, o, th, br};
-}
-__device__ __attribute__((noinline)) PhaseRet3 phase_accept(const void* kp, int b, int slot, double sf, double alpha, double a_z, double mu, unsigned gen, unsigned nred, unsigned xseq) {
-  DOMPC_PHASE_PROLOGUE
-  const Comp C = accept_pass(T, Q, ufl(alpha), ufl(a_z), ufl(mu));
-  return PhaseRet3{T.gen, T.nred, T.xseq, C.smax, C.smin, C.sum_z};
+  Comp C;
+  eval_trial_pass<true>(T, Q, ufl(al), ufl(a_z), ufl(mu), o, th, br, C);
+  return PhaseRet6{T.gen, T.nred, T.xseq, o, th, br, C.smax, C.smin, C.sum_z};
 }
 #undef DOMPC_PHASE_PROLOGUE
 #define DOMPC_PHASE_CALL(fn, ...)                                                   \
@@ -343,24 +322,15 @@ DOMPC_DEV inline void run_step_rules(const Thr& T, const Prob& Q, int b, int slo
   step_rules_pass(T, Q, mu, r5);
 #endif
 }
-DOMPC_DEV inline void run_eval_trial(const Thr& T, const Prob& Q, int b, int slot, double al, double& obj_o, double& th_o, double& bar_o) {
+DOMPC_DEV inline void run_eval_trial(const Thr& T, const Prob& Q, int b, int slot, double al, double a_z, double mu, double& obj_o, double& th_o, double& bar_o, Comp& Cp) {
 #ifndef DOMPC_HOST_EMU
-  if (fine_items(T, *Q.A)) { DOMPC_PHASE_CALL(phase_eval_trial_fine, al) obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); return; }
-  if (DOMPC_REPEAT_PHASE & 8) { DOMPC_PHASE_CALL(phase_eval_trial, al) }
-  DOMPC_PHASE_CALL(phase_eval_trial, al)
-  obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2);
+  if (fine_items(T, *Q.A)) { DOMPC_PHASE_CALL(phase_eval_trial_fine, al, a_z, mu) obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); Cp = Comp{r_.c0, r_.c1, r_.c2}; return; }
+  if (DOMPC_REPEAT_PHASE & 8) { DOMPC_PHASE_CALL(phase_eval_trial, al, a_z, mu) }
+  DOMPC_PHASE_CALL(phase_eval_trial, al, a_z, mu)
+  obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); Cp = Comp{r_.c0, r_.c1, r_.c2};
 #else
   (void)b; (void)slot;
-  if (fine_items(T, *Q.A)) eval_trial_pass<true>(T, Q, al, obj_o, th_o, bar_o); else eval_trial_pass<false>(T, Q, al, obj_o, th_o, bar_o);
-#endif
-}
-DOMPC_DEV inline Comp run_accept(const Thr& T, const Prob& Q, int b, int slot, double alpha, double a_z, double mu) {
-#ifndef DOMPC_HOST_EMU
-  DOMPC_PHASE_CALL(phase_accept, alpha, a_z, mu)
-  return Comp{r_.v0, r_.v1, r_.v2};
-#else
-  (void)b; (void)slot;
-  return accept_pass(T, Q, alpha, a_z, mu);
+  if (fine_items(T, *Q.A)) eval_trial_pass<true>(T, Q, al, a_z, mu, obj_o, th_o, bar_o, Cp); else eval_trial_pass<false>(T, Q, al, a_z, mu, obj_o, th_o, bar_o, Cp);
 #endif
 }
 DOMPC_DEV inline void run_forward(const Thr& T, const Prob& Q, int b, int slot, double mu, double delta) {

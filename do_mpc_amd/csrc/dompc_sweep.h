@@ -175,7 +175,7 @@ DOMPC_DEV inline double comp_err(const Comp& C, double mu) { return C.smax >= C.
   }
 
 // error measures (IPOPT eq. (5)/(6)) + objective + theta at the current iterate.  `pre`: thread-local complementarity
-// partials already accumulated by the caller (the accept pass has the updated x, z in registers), or null.
+// partials already accumulated by the caller (the trial evaluation that produced this iterate had x, z in registers), or null.
 struct Errs { double e_d, e_p, sum_y, obj, theta; Comp C; };
 DOMPC_PHASE Errs measure(const Thr& T, const Prob& Q, const Comp* pre) {
   const KArgs& A = *Q.A;

@@ -35,5 +35,5 @@ acc_ms=acc_tr=0.0
 for m in sorted(d):
     ms,tr,r=d[m]; acc_ms+=ms; acc_tr+=tr
     print('%-52s %7.1f ms %5.1f %%   %6.3f TB %5.1f %%   %6.0f doubles per edge and iteration   (iters %.3f conv %d)' % (names[m], ms, 100*ms/b_ms, tr/1e12, 100*tr/b_tr, tr/8/B/180/it, r['iters'], r['conv']))
-print('%-52s %7.1f ms %5.1f %%   %6.3f TB %5.1f %%   %6.0f doubles per edge and iteration' % ('rest (measure, accept, driver, adjoint forward)', b_ms-acc_ms, 100*(b_ms-acc_ms)/b_ms, (b_tr-acc_tr)/1e12, 100*(b_tr-acc_tr)/b_tr, (b_tr-acc_tr)/8/B/180/it))
+print('%-52s %7.1f ms %5.1f %%   %6.3f TB %5.1f %%   %6.0f doubles per edge and iteration' % ('rest (measure, driver, adjoint forward)', b_ms-acc_ms, 100*(b_ms-acc_ms)/b_ms, (b_tr-acc_tr)/1e12, 100*(b_tr-acc_tr)/b_tr, (b_tr-acc_tr)/8/B/180/it))
 PY
