@@ -104,7 +104,8 @@ def runtime_library(force: bool = False) -> str:
         if not force and _fresh(out, stamp, dig):       # another process built it while we waited
             return out
         cmd = [_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
-               os.path.join(CSRC, "dompc_runtime.cpp"), os.path.join(CSRC, "dompc_plant_runtime.cpp"), "-ldl"]
+               os.path.join(CSRC, "dompc_runtime.cpp"), os.path.join(CSRC, "dompc_plant_runtime.cpp"),
+               os.path.join(CSRC, "dompc_ekf_runtime.cpp"), "-ldl"]
         _compile_to(cmd, out, "building libdompc_ipm.so")
         _write_atomic(stamp, dig)
     return out
@@ -197,5 +198,36 @@ def plant_code_object(header_text: str, model_hash: str, force: bool = False) ->
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "--genco", f"-DDOMPC_PLANT_HEADER=\"{hdr}\"", "-I", CSRC,
                os.path.join(CSRC, "dompc_plant.hip")]
         _compile_to(cmd, out, f"lowering plant {model_hash} to {ARCH}")
+        _write_atomic(stamp, dig)
+    return out
+
+
+def ekf_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
+    """gfx950 code object of the batched extended Kalman filter (csrc/dompc_ekf.hip) for one lowered model.
+    remarks=True: compile again with -Rpass-analysis=kernel-resource-usage and return (path, compiler output) - registers, scratch and
+    LDS of the kernels (profiles/ekf_resource_usage.txt)."""
+    d = model_dir("ekf_" + model_hash)
+    hdr = os.path.join(d, "ekf_gen.h")
+    out = os.path.join(d, f"dompc_ekf_{ARCH}.hsaco")
+    stamp = out + ".stamp"
+    dig = _sources_digest() + hashlib.sha256(header_text.encode()).hexdigest()[:12]
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "--genco", f"-DDOMPC_EKF_HEADER=\"{hdr}\"", "-I", CSRC,
+           os.path.join(CSRC, "dompc_ekf.hip")]
+    if not force and not remarks and _fresh(out, stamp, dig):
+        return out
+    with _locked(d):
+        if not force and not remarks and _fresh(out, stamp, dig):
+            return out
+        if not (os.path.exists(hdr) and open(hdr).read() == header_text):
+            _write_atomic(hdr, header_text)
+        if remarks:
+            tmp = f"{out}.{os.getpid()}.remarks.tmp"
+            try:
+                text = _run(cmd + ["-Rpass-analysis=kernel-resource-usage", "-o", tmp], f"resource usage of filter {model_hash}")
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+            return out, text
+        _compile_to(cmd, out, f"lowering filter {model_hash} to {ARCH}")
         _write_atomic(stamp, dig)
     return out

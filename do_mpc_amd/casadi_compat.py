@@ -79,6 +79,7 @@ def install(force: bool = False):
         m_est = types.ModuleType("do_mpc.estimator")
         m_est.StateFeedback = StateFeedback
         m_est.MHE, m_est.MHESettings = estimator.MHE, estimator.MHESettings
+        m_est.EKF = estimator.EKF
         m_diff = types.ModuleType("do_mpc.differentiator")
         m_diff.DoMPCDifferentiator = differentiator.DoMPCDifferentiator
         m_samp = types.ModuleType("do_mpc.sampling")

@@ -258,3 +258,135 @@ class BatchClosedLoopMHE:
         est = np.frombuffer(self.e_stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
         return {"mpc_stats": cs, "mhe_stats": est, "plant_status": (self.pstat.cpu().numpy() & 1), "plant_implicit": ((self.pstat.cpu().numpy() >> 1) & 1), "u0": self.U.cpu().numpy(),
                 "x_true": self.X.cpu().numpy(), "y": self.Y.cpu().numpy(), "x_est": self.x_est.cpu().numpy(), "p_est": self.p_est.cpu().numpy()}
+
+
+class BatchClosedLoopEKF:
+    """B closed loops controller -> plant -> extended Kalman filter -> controller advancing together, everything resident in HBM: per
+    control step ONE batched solve of the controller, ONE batched plant step (states and measurements) and ONE batched filter step
+    (do_mpc_amd/ekf.py: estimates and covariances updated in place), plus index arithmetic on device tensors.  The per-sample loop of
+    the reference is `u0 = mpc.make_step(x0)`, `y = simulator.make_step(u0)`, `x0 = ekf.make_step(y, u0, Q, R)`
+    (/root/reference/examples/triple_tank_ekf/main.py:191-200 for the plant and the filter).
+    X0_true: [B][nx] plant states; x0_est: [nx] or [B][nx]; P0: [nx][nx] or [B][nx][nx]; Q, R: one matrix or one per loop;
+    V: measurement noise of the plant, None, [B][nv] (the same in every step) or a callable k -> [B][nv]."""
+
+    def __init__(self, mpc, simulator, ekf, X0_true, x0_est, P0, Q, R, V=None, device: int = 0):
+        import torch
+        self.torch = torch
+        self.mpc, self.sim, self.ekf = mpc, simulator, ekf
+        m = simulator.model
+        ps = self.ps = mpc.structure
+        if getattr(ps, "open_loop_stack", False):
+            raise NotImplementedError("structured HIP backend: the device-resident closed loop with open_loop and several scenarios")
+        if getattr(mpc.S, "row_mapped", False):
+            raise NotImplementedError("structured HIP backend: the device-resident closed loop with rows appended to nlp_cons")
+        me = ekf.model
+        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
+        assert (me.n_x, me.n_u, me.n_y) == (m.n_x, m.n_u, m.n_y), "plant and filter must share states, inputs and measurements"
+        X0_true = np.asarray(X0_true, dtype=float).reshape(-1, m.n_x)
+        self.B = B = X0_true.shape[0]
+        dev = self.dev = torch.device("cuda", device)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
+        nx, nu, ny = m.n_x, m.n_u, m.n_y
+        self.nx, self.nu, self.ny = nx, nu, ny
+        x_est = np.broadcast_to(np.asarray(x0_est, float).reshape(-1, nx), (B, nx)).copy()
+        P0 = np.asarray(P0, float)
+        Pcov = np.broadcast_to(P0.reshape(-1, nx, nx), (B, nx, nx)).copy()
+        Q, R = np.asarray(Q, float), np.asarray(R, float)
+        assert Q.shape in ((nx, nx), (B, nx, nx)) and R.shape in ((ny, ny), (B, ny, ny)), "Q / R: one matrix or one per loop"
+        self.mask = 2 | 4 | (8 if Q.ndim == 2 else 0) | (16 if R.ndim == 2 else 0)
+        self.Q, self.R = t(Q), t(R)
+        # ---- controller: opt_p rows, initial guess (set_initial_guess semantics), bounds
+        t0 = float(mpc._t0[0])
+        Pc = np.tile(mpc.opt_p_num.master, (B, 1))
+        Pc[:, :nx] = x_est
+        Pc[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(t0).master
+        Pc[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(t0).master
+        Pc[:, ps.p_off_uprev:] = 0.0
+        Gc = np.zeros((B, ps.n_opt_x))
+        Gc[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (x_est / mpc._x_scaling.master)[:, None, :]
+        self.Pc, self.Gc = t(Pc), t(Gc)
+        self.c_lbx, self.c_ubx = t(mpc._lb_opt_x.master), t(mpc._ub_opt_x.master)
+        self.c_lbg, self.c_ubg = t(mpc._nlp_cons_lb), t(mpc._nlp_cons_ub)
+        self.c_sol = torch.empty((B, ps.n_opt_x), dtype=torch.float64, device=dev)
+        self.c_f = torch.empty(B, dtype=torch.float64, device=dev)
+        self.c_stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.us = t(mpc._u_scaling.master)
+        # ---- plant
+        self.X = t(X0_true)
+        self.Xn = torch.empty_like(self.X)
+        self.U = torch.empty((B, nu), dtype=torch.float64, device=dev)
+        self.Y = torch.empty((B, max(ny, 1)), dtype=torch.float64, device=dev)
+        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
+        ts = float(simulator._t0[0])
+        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
+        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
+        self._V = V
+        self.V = torch.zeros((B, max(m.n_v, 1)), dtype=torch.float64, device=dev)
+        # ---- filter
+        te = float(ekf._t0[0])
+        self.x_est, self.Pcov = t(x_est), t(Pcov)
+        self.p_ekf = t(ekf.p_fun(te).master if me.n_p else np.zeros(1))
+        self.tvp_ekf = t(ekf.tvp_fun(te).master if me.n_tvp else np.zeros(1))
+        self.estat = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.t_mpc0, self.dt = t0, float(mpc.settings.t_step)
+        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
+        self.t_ekf0, self.dt_ekf = te, float(ekf.settings.t_step)
+        self._pc_row = Pc[0].copy()
+        self.k = 0
+
+    def _refresh_time_varying(self):
+        """_tvp / _p of controller, plant and filter at the current loop time -> device (same values for every loop): the per-sample
+        loop re-evaluates all of them in every make_step (_mpc.py:1009-1019, simulator.py:790-800, _ekf.py:268-270)"""
+        torch, ps, m, me = self.torch, self.ps, self.sim.model, self.ekf.model
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
+        tm, ts, te = self.t_mpc0 + self.k * self.dt, self.t_sim0 + self.k * self.dt_sim, self.t_ekf0 + self.k * self.dt_ekf
+        if ps.ntvp or ps.np_:
+            row = self._pc_row
+            row[ps.p_off_tvp:ps.p_off_p] = self.mpc.tvp_fun(tm).master
+            row[ps.p_off_p:ps.p_off_uprev] = self.mpc.p_fun(tm).master
+            self.Pc[:, ps.p_off_tvp:ps.p_off_uprev] = up(row[ps.p_off_tvp:ps.p_off_uprev].copy())
+        if m.n_p:
+            self.p_plant.copy_(up(self.sim.p_fun(ts).master))
+        if m.n_tvp:
+            self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
+        if me.n_p:
+            self.p_ekf.copy_(up(self.ekf.p_fun(te).master))
+        if me.n_tvp:
+            self.tvp_ekf.copy_(up(self.ekf.tvp_fun(te).master))
+
+    def step(self) -> dict:
+        torch, ps, B, nx, nu = self.torch, self.ps, self.B, self.nx, self.nu
+        stream = torch.cuda.current_stream()
+        if self.k > 0:
+            self._refresh_time_varying()
+        nv = self.sim.model.n_v
+        if self._V is not None and nv:
+            v = self._V(self.k) if callable(self._V) else self._V
+            self.V.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(v, float).reshape(B, nv))).to(self.dev))
+        # 1. controller
+        self.mpc.S.solve_batch_device(B, self.Gc.data_ptr(), self.c_lbx.data_ptr(), self.c_ubx.data_ptr(), self.c_lbg.data_ptr(),
+                                      self.c_ubg.data_ptr(), self.Pc.data_ptr(), self.c_sol.data_ptr(), 0, 0, 0, self.c_f.data_ptr(),
+                                      self.c_stats.data_ptr(), stream=stream.cuda_stream)
+        iu = ps.iu(0, 0)
+        torch.mul(self.c_sol[:, iu:iu + nu], self.us, out=self.U)
+        # 2. plant: next true state and its measurement
+        self.sim.step_batch_device(B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
+                                   self.Xn.data_ptr(), self.Y.data_ptr(), self.pstat.data_ptr(),
+                                   v=(self.V.data_ptr() if (self._V is not None and nv) else 0), shared_mask=2 | 4 | 8,
+                                   stream=stream.cuda_stream)
+        self.X, self.Xn = self.Xn, self.X
+        # 3. filter: estimate and covariance in place
+        self.ekf.step_batch_device(B, self.x_est.data_ptr(), self.Pcov.data_ptr(), self.Y.data_ptr(), self.U.data_ptr(),
+                                   self.tvp_ekf.data_ptr(), self.p_ekf.data_ptr(), self.Q.data_ptr(), self.R.data_ptr(),
+                                   status=self.estat.data_ptr(), shared_mask=self.mask, stream=stream.cuda_stream)
+        # 4. next controller problem: x0 <- estimate, u_prev <- applied input, initial guess <- previous solution
+        self.Pc[:, :nx] = self.x_est
+        self.Pc[:, ps.p_off_uprev:] = self.U
+        self.Gc.copy_(self.c_sol)
+        self.k += 1
+        torch.cuda.synchronize()
+        cs = np.frombuffer(self.c_stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
+        est = self.estat.cpu().numpy()
+        return {"mpc_stats": cs, "plant_status": (self.pstat.cpu().numpy() & 1), "ekf_status": est & 0xFF, "u0": self.U.cpu().numpy(),
+                "x_true": self.X.cpu().numpy(), "y": self.Y[:, :self.ny].cpu().numpy(), "x_est": self.x_est.cpu().numpy(),
+                "P": self.Pcov.cpu().numpy()}

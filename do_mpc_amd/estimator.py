@@ -37,6 +37,7 @@ import numpy as np
 
 from . import sym
 from .controller import MPC, MPCData, _Indexed
+from .ekf import EKF, EKFSettings  # noqa: F401  (do_mpc.estimator.EKF: the batched extended Kalman filter, do_mpc_amd/ekf.py)
 from .model import Model, VarGroup
 from .structs import Entry, Layout, NumStruct
 

@@ -470,3 +470,62 @@ def lower_plant(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discre
     text = "\n".join(hdr) + "\n" + "\n".join(parts)
     digest = hashlib.sha256(text.encode()).hexdigest()[:16]
     return text + f"\n#define PLANT_MODEL_HASH \"{digest}\"\n"
+
+
+def lower_ekf(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discrete, name="ekf", z_sym=(), alg=()) -> str:
+    """Header for the batched extended Kalman filter (csrc/dompc_ekf.hip), in PHYSICAL units like lower_plant:
+    `ekf_rhs`, `ekf_meas` (measurement function with v = 0), `ekf_lin` (A = d rhs / d x and C = d y / d x, row-major; only their
+    structural non-zeros are written, the tables EKF_A_NZ / EKF_C_NZ say which) and `ekf_jac` (A alone: the stages of the covariance
+    integration).  Noise symbols are zero, as in the reference's get_linear_system_matrices (/root/reference/do_mpc/model/_model.py:1126-1128)
+    and in EKF.make_step (/root/reference/do_mpc/estimator/_ekf.py:273-274)."""
+    nx, ny = len(x_sym), len(meas)
+    if len(z_sym) or len(alg):
+        raise NotImplementedError("structured HIP backend: an extended Kalman filter for a model with algebraic states "
+                                  "(the reference asserts the same: 'EKF with algebraic equations not ready for use!')")
+    if nx > 16 or ny > 16:
+        raise NotImplementedError(f"structured HIP backend: an extended Kalman filter with more than 16 states or more than 16 measurements "
+                                  f"(this model: n_x = {nx}, n_y = {ny}; the kernel maps one filter to a row of 16 lanes)")
+    groups = [("x", x_sym), ("u", u_sym), ("tvp", tvp_sym), ("p", p_sym)]
+    binds: Dict[int, str] = {}
+    for cname, syms in groups:
+        for i, s in enumerate(syms):
+            binds[s.idx] = f"{cname}[{i}]"
+    noise = list(w_sym) + list(v_sym)
+    A = sym.forward_jacobian(list(rhs), list(x_sym))
+    C = sym.forward_jacobian(list(meas), list(x_sym))
+    for what, Mx in (("A = d rhs / d x", A), ("C = d y / d x", C)):
+        if sym.depends_on([e for row in Mx for e in row], noise + list(z_sym)):
+            raise NotImplementedError(f"structured HIP backend: an extended Kalman filter whose linearisation {what} depends on _w, _v or _z")
+    zero = {s.idx: sym.ZERO for s in noise}
+    rhs0 = sym.substitute_nodes(list(rhs), zero)
+    meas0 = sym.substitute_nodes(list(meas), zero)
+    for what, nodes in (("rhs", rhs0), ("meas", meas0)):
+        free = [s for s in sym.free_symbols(list(nodes)) if s.idx not in binds]
+        if free:
+            raise Exception(f"{what} depends on symbols outside (_x,_u,_tvp,_p,_w,_v): {free}")
+    nz = lambda n: not (n.op == "const" and n.val == 0.0)      # noqa: E731
+    a_outs = [(f"A[{i * nx + j}]", A[i][j]) for i in range(nx) for j in range(nx) if nz(A[i][j])]
+    c_outs = [(f"C[{i * nx + j}]", C[i][j]) for i in range(ny) for j in range(nx) if nz(C[i][j])]
+    sig = "const double* x, const double* u, const double* tvp, const double* p"
+    parts = []
+    body = sym.emit_c([(f"f[{i}]", e) for i, e in enumerate(rhs0)], binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_rhs({sig}, double* f) {{\n{body}\n}}\n")
+    body = sym.emit_c([(f"y[{i}]", e) for i, e in enumerate(meas0)], binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_meas({sig}, double* y) {{\n{body}\n}}\n")
+    body = sym.emit_c(a_outs, binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_jac({sig}, double* A) {{\n{body}\n}}\n")
+    body = sym.emit_c(a_outs + c_outs, binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_lin({sig}, double* A, double* C) {{\n{body}\n}}\n")
+
+    def table(tname, Mx, rows):
+        vals = [1 if nz(Mx[i][j]) else 0 for i in range(rows) for j in range(nx)] or [0]
+        return f"static constexpr int {tname}[{len(vals)}] = {{{', '.join(str(v) for v in vals)}}};"
+    hdr = ["// GENERATED by do_mpc_amd/lowering.py:lower_ekf - do not edit.", "#pragma once", "#include <math.h>",
+           f"#define EKF_MODEL_NAME \"{name}\"",
+           f"#define EKF_NX {nx}", f"#define EKF_NU {len(u_sym)}", f"#define EKF_NP {len(p_sym)}",
+           f"#define EKF_NTVP {len(tvp_sym)}", f"#define EKF_NY {ny}", f"#define EKF_DISCRETE {1 if discrete else 0}",
+           "// structure of A (NX x NX) and C (NY x NX), row-major: 1 = written by ekf_lin / ekf_jac, 0 = zero for every argument",
+           table("EKF_A_NZ", A, nx), table("EKF_C_NZ", C, ny), ""]
+    text = "\n".join(hdr) + "\n" + "\n".join(parts)
+    digest = hashlib.sha256(text.encode()).hexdigest()[:16]
+    return text + f"\n#define EKF_MODEL_HASH \"{digest}\"\n"

@@ -232,3 +232,37 @@ class Model:
             if free:
                 raise Exception(f"{what} depends on symbols that are not model variables: {free}")
         self.flags["setup"] = True
+
+    # ---------------------------------------------------------------- linearisation
+    def get_linear_system_matrices(self, xss=None, uss=None, z=None, tvp=None, p=None):
+        """(A, B, C, D) of the system linearised around (xss, uss, z, tvp, p): A = d rhs / d x, B = d rhs / d u, C = d y / d x,
+        D = d y / d u (/root/reference/do_mpc/model/_model.py:1008-1011, 1090-1144).  Every argument is optional: a group that is
+        not given stays symbolic, and a matrix that still depends on symbols is returned as `sym.SX`; otherwise as a numpy array.
+        The noise symbols `_w` / `_v` are zero."""
+        assert self.flags["setup"] is True, "Model was not setup. Call model.setup() first."
+        if getattr(self, "_lin_expr", None) is None:
+            self._lin_expr = (sym.jacobian(self._rhs, self._x.cat), sym.jacobian(self._rhs, self._u.cat),
+                              sym.jacobian(self._y.cat, self._x.cat), sym.jacobian(self._y.cat, self._u.cat))
+        mapping = {}
+        for grp, val in ((self._x, xss), (self._u, uss), (self._z, z), (self._tvp, tvp), (self._p, p), (self._w, 0.0), (self._v, 0.0)):
+            nodes = grp.cat.nodes()
+            if val is None or isinstance(val, VarGroup) or not nodes:
+                continue
+            if isinstance(val, sym.SX):
+                new = val.nodes()
+            else:
+                a = np.asarray(val.master if hasattr(val, "master") else (val.arr if hasattr(val, "arr") else val), dtype=float).reshape(-1)
+                new = [sym.const(float(v)) for v in (np.full(len(nodes), a[0]) if a.size == 1 else a)]
+            assert len(new) == len(nodes), f"{grp.kind} has {len(nodes)} elements, got {len(new)}"
+            mapping.update({s.idx: n for s, n in zip(nodes, new)})
+        out = []
+        for Mx in self._lin_expr:
+            data = sym.substitute_nodes(Mx.data, mapping) if mapping else list(Mx.data)
+            if sym.free_symbols(data):
+                out.append(sym.SX(data, Mx.shape))
+            else:
+                if getattr(self, "_lin_dummy", None) is None:
+                    self._lin_dummy = sym.SX.sym("lin_dummy")         # (sym.Function wants at least one input)
+                vals = sym.Function("lin", [self._lin_dummy], [sym.SX(data, Mx.shape)]).eval(0.0)[0] if data else np.zeros(0)
+                out.append(np.asarray(vals, float).reshape(Mx.shape, order="F"))
+        return tuple(out)

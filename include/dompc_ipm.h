@@ -299,6 +299,38 @@ int dompc_plant_step_batch_device(dompc_plant* h, int32_t B, const double* x, co
                                   const double* p, const double* w, const double* v, int32_t shared_mask, double* x_next,
                                   double* y, int32_t* status, void* stream);
 
+/* ---- batched extended Kalman filter (do_mpc.estimator.EKF) ----------------------------------------------------------
+ * One filter step - prediction and measurement update - for B independent filters per launch, in physical units:
+ *   A_k, C_k at the prior estimate;  discrete models x- = rhs(x, u), P- = A P A' + Q;  continuous models [x; P] integrated over
+ *   t_step with dP/dt = A(x) P + P A(x)' + Q (explicit Dormand-Prince 5(4), step-size control per filter, no implicit method);
+ *   S = C P- C' + R, L = P- C' S^-1, x = x- + L (y - meas(x-, u)), P = (I - L C) P-.
+ * The model functions come from a per-model gfx950 code object (do_mpc_amd/lowering.py:lower_ekf); at most 16 states and 16
+ * measurements, no algebraic states.  Layout: x [B][nx], P [B][nx][nx] row-major, y [B][ny]; u / tvp / p / Q (nx*nx) / R (ny*ny)
+ * are [B][n] or, with their bit of shared_mask set (bit 0/1/2/3/4 = u/tvp/p/Q/R), ONE row shared by all filters.
+ * status[b]: bit 0 = the integration did not reach t_step (step limit, NaN right-hand side); bit 1 = S singular or not finite - the
+ * a-priori x-, P- are returned, never NaN; integration steps taken = status[b] >> 8. */
+typedef struct dompc_ekf dompc_ekf;
+typedef struct dompc_ekf_desc {
+  int32_t nx, nu, np, ntvp, ny;
+  int32_t discrete;                  /* 1: x- = rhs(x, u, tvp, p) (no integration)                             */
+  const char* code_object_path;      /* gfx950 code object built from the lowered filter                       */
+  const char* model_hash;            /* must equal the hash embedded in the code object (NULL = no check)      */
+  int32_t device;
+  int32_t max_steps;                 /* integration steps per filter and call; 0 = 200000                      */
+  double t_step, reltol, abstol;
+} dompc_ekf_desc;
+int  dompc_ekf_create(const dompc_ekf_desc* desc, dompc_ekf** out);
+void dompc_ekf_destroy(dompc_ekf* h);
+const char* dompc_ekf_last_error(const dompc_ekf* h);         /* h may be NULL: error of the last failed create */
+/* host buffers; status may be NULL.  x_out / P_out may alias x / P. */
+int dompc_ekf_step_batch(dompc_ekf* h, int32_t B, const double* x, const double* P, const double* y, const double* u,
+                         const double* tvp, const double* p, const double* Q, const double* R, int32_t shared_mask,
+                         double* x_out, double* P_out, int32_t* status);
+/* DEVICE buffers, x and P updated IN PLACE, asynchronous on `stream` (hipStream_t as void*) */
+int dompc_ekf_step_batch_device(dompc_ekf* h, int32_t B, double* x, double* P, const double* y, const double* u,
+                                const double* tvp, const double* p, const double* Q, const double* R, int32_t shared_mask,
+                                int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
