@@ -181,38 +181,17 @@ def model_code_object(header_text: str, model_hash: str, force: bool = False, op
     return out
 
 
-def plant_code_object(header_text: str, model_hash: str, force: bool = False) -> str:
-    """gfx950 code object of the batched plant integrator (csrc/dompc_plant.hip) for one lowered plant model."""
-    d = model_dir("plant_" + model_hash)
-    hdr = os.path.join(d, "plant_gen.h")
-    out = os.path.join(d, f"dompc_plant_{ARCH}.hsaco")
+def _kernel_code_object(prefix: str, source: str, header_macro: str, header_name: str, what: str, header_text: str, model_hash: str,
+                        force: bool, remarks: bool = False):
+    """gfx950 code object of csrc/`source` for one lowered model: `_build/models/<prefix>_<hash>/dompc_<prefix>_gfx950.hsaco`, the
+    generated header next to it and named to the kernel by -D`header_macro`."""
+    d = model_dir(prefix + "_" + model_hash)
+    hdr = os.path.join(d, header_name)
+    out = os.path.join(d, f"dompc_{prefix}_{ARCH}.hsaco")
     stamp = out + ".stamp"
     dig = _sources_digest() + hashlib.sha256(header_text.encode()).hexdigest()[:12]
-    if not force and _fresh(out, stamp, dig):
-        return out
-    with _locked(d):
-        if not force and _fresh(out, stamp, dig):
-            return out
-        if not (os.path.exists(hdr) and open(hdr).read() == header_text):
-            _write_atomic(hdr, header_text)
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "--genco", f"-DDOMPC_PLANT_HEADER=\"{hdr}\"", "-I", CSRC,
-               os.path.join(CSRC, "dompc_plant.hip")]
-        _compile_to(cmd, out, f"lowering plant {model_hash} to {ARCH}")
-        _write_atomic(stamp, dig)
-    return out
-
-
-def ekf_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
-    """gfx950 code object of the batched extended Kalman filter (csrc/dompc_ekf.hip) for one lowered model.
-    remarks=True: compile again with -Rpass-analysis=kernel-resource-usage and return (path, compiler output) - registers, scratch and
-    LDS of the kernels (profiles/ekf_resource_usage.txt)."""
-    d = model_dir("ekf_" + model_hash)
-    hdr = os.path.join(d, "ekf_gen.h")
-    out = os.path.join(d, f"dompc_ekf_{ARCH}.hsaco")
-    stamp = out + ".stamp"
-    dig = _sources_digest() + hashlib.sha256(header_text.encode()).hexdigest()[:12]
-    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "--genco", f"-DDOMPC_EKF_HEADER=\"{hdr}\"", "-I", CSRC,
-           os.path.join(CSRC, "dompc_ekf.hip")]
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "--genco", f"-D{header_macro}=\"{hdr}\"", "-I", CSRC,
+           os.path.join(CSRC, source)]
     if not force and not remarks and _fresh(out, stamp, dig):
         return out
     with _locked(d):
@@ -223,11 +202,23 @@ def ekf_code_object(header_text: str, model_hash: str, force: bool = False, rema
         if remarks:
             tmp = f"{out}.{os.getpid()}.remarks.tmp"
             try:
-                text = _run(cmd + ["-Rpass-analysis=kernel-resource-usage", "-o", tmp], f"resource usage of filter {model_hash}")
+                text = _run(cmd + ["-Rpass-analysis=kernel-resource-usage", "-o", tmp], f"resource usage of {what} {model_hash}")
             finally:
                 if os.path.exists(tmp):
                     os.remove(tmp)
             return out, text
-        _compile_to(cmd, out, f"lowering filter {model_hash} to {ARCH}")
+        _compile_to(cmd, out, f"lowering {what} {model_hash} to {ARCH}")
         _write_atomic(stamp, dig)
     return out
+
+
+def plant_code_object(header_text: str, model_hash: str, force: bool = False) -> str:
+    """gfx950 code object of the batched plant integrator (csrc/dompc_plant.hip) for one lowered plant model."""
+    return _kernel_code_object("plant", "dompc_plant.hip", "DOMPC_PLANT_HEADER", "plant_gen.h", "plant", header_text, model_hash, force)
+
+
+def ekf_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
+    """gfx950 code object of the batched extended Kalman filter (csrc/dompc_ekf.hip) for one lowered model.
+    remarks=True: compile again with -Rpass-analysis=kernel-resource-usage and return (path, compiler output) - registers, scratch and
+    LDS of the kernels (profiles/ekf_resource_usage.txt)."""
+    return _kernel_code_object("ekf", "dompc_ekf.hip", "DOMPC_EKF_HEADER", "ekf_gen.h", "filter", header_text, model_hash, force, remarks)

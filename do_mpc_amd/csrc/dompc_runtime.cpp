@@ -9,20 +9,14 @@
 //   test    : g++ -DDOMPC_HOST_EMU dompc_runtime.cpp dompc_device.hip(as C++) -> tests/_hostemu/*.so
 //             ("device" memory = host memory, a workgroup = the calling thread).  Never shipped.
 #include <chrono>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
 #include <dlfcn.h>
 #include <cmath>
-#include <string>
 #include <thread>
-#include <vector>
 
+#include "dompc_host.h"
 #include "dompc_kargs.h"
 
-#ifndef DOMPC_HOST_EMU
-#include <hip/hip_runtime.h>
-#else
+#ifdef DOMPC_HOST_EMU
 extern "C" void dompc_hostemu_model_info(const int32_t* in, int64_t* out, char* hash);
 extern "C" void dompc_hostemu_run(const dompc::KArgs* A);
 #endif
@@ -30,9 +24,8 @@ extern "C" void dompc_hostemu_run(const dompc::KArgs* A);
 static thread_local std::string g_create_error;
 static const int BATCH_ONE_WAVE = 4096;     // batch size from which a problem gets one wavefront instead of four (see dompc_create)
 
-struct dompc_handle {
+struct dompc_handle : dompc_host::Context {
   dompc_problem_desc d;
-  std::string error;
   std::string code_path;
   int32_t e_pad = 0, n_slots = 0, block = 256, occupancy = 0, n_leaves = 1;
   bool batch_object_stale = false;       // a `_batch` sibling exists but was built from other sources / another model: not used
@@ -40,7 +33,6 @@ struct dompc_handle {
   int32_t slots64 = 0, slots256 = 0;   // resident workgroups at 64 / 256 threads
   int64_t ws_stride = 0, sweep_block = 0, el_size = 0, edges_per_wave = 1;
   dompc::KArgs base;       // tables + workspace filled in, I/O pointers zero
-  std::vector<void*> dev_allocs;
   // staging for host-pointer calls
   double *s_x0 = nullptr, *s_lbx = nullptr, *s_ubx = nullptr, *s_lbg = nullptr, *s_ubg = nullptr, *s_p = nullptr;
   double *s_x = nullptr, *s_g = nullptr, *s_lamx = nullptr, *s_lamg = nullptr, *s_f = nullptr;
@@ -69,51 +61,14 @@ struct dompc_handle {
   const char* (*nccl_error_string)(int) = nullptr;
   void* rccl_comm = nullptr;
   hipStream_t rccl_stream = nullptr;
-#endif
-#ifndef DOMPC_HOST_EMU
   hipModule_t module = nullptr, module_batch = nullptr;
   hipFunction_t fn_solve = nullptr, fn_info = nullptr, fn_solve_batch = nullptr;
-  hipStream_t stream = nullptr;
   hipStream_t shard_stream = nullptr;    // lowest priority: never shares a hardware queue with the collective's kernels
 #endif
 };
 
 // ------------------------------------------------------------------------------------------------
 #ifndef DOMPC_HOST_EMU
-#define HIPCHK(h, expr)                                                                     \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) {                                                                 \
-      (h)->error = std::string(#expr) + ": " + hipGetErrorString(_e);                       \
-      return 1;                                                                             \
-    }                                                                                       \
-  } while (0)
-
-static int dev_alloc(dompc_handle* h, void** p, size_t bytes) {
-  if (bytes == 0) bytes = 8;
-  HIPCHK(h, hipMalloc(p, bytes));
-  h->dev_allocs.push_back(*p);
-  return 0;
-}
-static void dev_release(dompc_handle* h, void* p) {
-  if (!p) return;
-  for (size_t i = 0; i < h->dev_allocs.size(); ++i)
-    if (h->dev_allocs[i] == p) { h->dev_allocs.erase(h->dev_allocs.begin() + i); hipFree(p); return; }
-}
-static int h2d(dompc_handle* h, void* dst, const void* src, size_t bytes) {
-  if (!bytes) return 0;
-  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, h->stream));
-  return 0;
-}
-static int d2h(dompc_handle* h, void* dst, const void* src, size_t bytes) {
-  if (!bytes) return 0;
-  HIPCHK(h, hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h->stream));
-  return 0;
-}
-static int dev_sync(dompc_handle* h) {
-  HIPCHK(h, hipStreamSynchronize(h->stream));
-  return 0;
-}
 // Wait for `st` with the watchdog: after watchdog_s the stop request is raised (the kernel leaves its IPM loops with
 // status 6); if the stream still has not drained after a grace period the call fails instead of blocking forever.
 // The limit is per ROUND over the resident problem slots (a batch of B problems on n_slots slots takes ceil(B / n_slots) rounds): a
@@ -151,22 +106,6 @@ static int dev_zero(dompc_handle* h, void* p, size_t bytes, hipStream_t s) {
   HIPCHK(h, hipMemsetAsync(p, 0, bytes, s));
   return 0;
 }
-#else
-static int dev_alloc(dompc_handle* h, void** p, size_t bytes) {
-  if (bytes == 0) bytes = 8;
-  *p = calloc(1, bytes);
-  if (!*p) { h->error = "out of memory"; return 1; }
-  h->dev_allocs.push_back(*p);
-  return 0;
-}
-static void dev_release(dompc_handle* h, void* p) {
-  if (!p) return;
-  for (size_t i = 0; i < h->dev_allocs.size(); ++i)
-    if (h->dev_allocs[i] == p) { h->dev_allocs.erase(h->dev_allocs.begin() + i); free(p); return; }
-}
-static int h2d(dompc_handle*, void* dst, const void* src, size_t bytes) { if (bytes) memcpy(dst, src, bytes); return 0; }
-static int d2h(dompc_handle*, void* dst, const void* src, size_t bytes) { if (bytes) memcpy(dst, src, bytes); return 0; }
-static int dev_sync(dompc_handle*) { return 0; }
 #endif
 
 extern "C" int dompc_abort(dompc_handle* h, int32_t stop) {
@@ -178,9 +117,9 @@ extern "C" int dompc_abort(dompc_handle* h, int32_t stop) {
 template <typename Tp>
 static int upload(dompc_handle* h, const Tp** dst, const Tp* src, size_t n) {
   void* p = nullptr;
-  if (dev_alloc(h, &p, n * sizeof(Tp))) return 1;
+  if (h->alloc(&p, n * sizeof(Tp))) return 1;
   if (n && !src) { h->error = "null table pointer in problem description"; return 1; }
-  if (h2d(h, p, src, n * sizeof(Tp))) return 1;
+  if (h->h2d(p, src, n * sizeof(Tp))) return 1;
   *dst = (const Tp*)p;
   return 0;
 }
@@ -213,19 +152,14 @@ extern "C" const char* dompc_last_error(const dompc_handle* h) { return h ? h->e
 
 extern "C" void dompc_destroy(dompc_handle* h) {
   if (!h) return;
+  h->close();
 #ifndef DOMPC_HOST_EMU
-  hipSetDevice(h->d.device);
-  for (void* p : h->dev_allocs) hipFree(p);
-  if (h->module) hipModuleUnload(h->module);
-  if (h->module_batch) hipModuleUnload(h->module_batch);
-  if (h->stream) hipStreamDestroy(h->stream);
   if (h->x_words) hipHostFree(h->x_words);
   if (h->abort_word) hipHostFree(h->abort_word);
   if (h->shard_stream) hipStreamDestroy(h->shard_stream);
   if (h->rccl_comm && h->nccl_comm_destroy) h->nccl_comm_destroy(h->rccl_comm);
   if (h->rccl_stream) hipStreamDestroy(h->rccl_stream);
 #else
-  for (void* p : h->dev_allocs) free(p);
   free(h->abort_word);
 #endif
   delete h;
@@ -234,37 +168,19 @@ extern "C" void dompc_destroy(dompc_handle* h) {
 static int ensure_staging(dompc_handle* h, int B) {
   if (B <= h->cap_batch) return 0;
   const dompc_problem_desc& d = h->d;
-  // (re)allocate for the larger batch; the superseded per-batch buffers are released now
-  if (dev_sync(h)) return 1;
-  for (void* old : {(void*)h->s_x0, (void*)h->s_p, (void*)h->s_x, (void*)h->s_g, (void*)h->s_lamx, (void*)h->s_lamg,
-                    (void*)h->s_f, (void*)h->s_stats})
-    dev_release(h, old);
-  if (dev_alloc(h, (void**)&h->s_x0, sizeof(double) * (size_t)B * d.n_opt_x)) return 1;
-  if (dev_alloc(h, (void**)&h->s_p, sizeof(double) * (size_t)B * d.n_opt_p)) return 1;
-  if (dev_alloc(h, (void**)&h->s_x, sizeof(double) * (size_t)B * d.n_opt_x)) return 1;
-  if (dev_alloc(h, (void**)&h->s_g, sizeof(double) * (size_t)B * d.n_g)) return 1;
-  if (dev_alloc(h, (void**)&h->s_lamx, sizeof(double) * (size_t)B * d.n_opt_x)) return 1;
-  if (dev_alloc(h, (void**)&h->s_lamg, sizeof(double) * (size_t)B * d.n_g)) return 1;
-  if (dev_alloc(h, (void**)&h->s_f, sizeof(double) * (size_t)B)) return 1;
-  if (dev_alloc(h, (void**)&h->s_stats, sizeof(dompc_stats) * (size_t)B)) return 1;
-  if (!h->s_lbx) {
-    if (dev_alloc(h, (void**)&h->s_lbx, sizeof(double) * d.n_opt_x)) return 1;
-    if (dev_alloc(h, (void**)&h->s_ubx, sizeof(double) * d.n_opt_x)) return 1;
-    if (dev_alloc(h, (void**)&h->s_lbg, sizeof(double) * d.n_g)) return 1;
-    if (dev_alloc(h, (void**)&h->s_ubg, sizeof(double) * d.n_g)) return 1;
+  const size_t D = sizeof(double);
+  if (!h->s_ubg) {      // per problem, not per batch row: allocated once
+    if (h->alloc((void**)&h->s_lbx, D * d.n_opt_x) || h->alloc((void**)&h->s_ubx, D * d.n_opt_x) ||
+        h->alloc((void**)&h->s_lbg, D * d.n_g) || h->alloc((void**)&h->s_ubg, D * d.n_g))
+      return 1;
   }
-  h->cap_batch = B;
-  return 0;
+  // (re)allocate for the larger batch; the superseded per-batch buffers are released now
+  if (h->sync()) return 1;
+  return h->grow_staging(&h->cap_batch, B, {{(void**)&h->s_x0, D * d.n_opt_x}, {(void**)&h->s_p, D * d.n_opt_p}, {(void**)&h->s_x, D * d.n_opt_x},
+                                            {(void**)&h->s_g, D * d.n_g}, {(void**)&h->s_lamx, D * d.n_opt_x}, {(void**)&h->s_lamg, D * d.n_g},
+                                            {(void**)&h->s_f, D}, {(void**)&h->s_stats, sizeof(dompc_stats)}});
 }
 
-static void* main_stream(dompc_handle* h) {      // the stream of the staging copies
-#ifndef DOMPC_HOST_EMU
-  return (void*)h->stream;
-#else
-  (void)h;
-  return nullptr;
-#endif
-}
 static void* own_stream(dompc_handle* h) {
 #ifndef DOMPC_HOST_EMU
   return (void*)((h->sharded && h->shard_stream) ? h->shard_stream : h->stream);
@@ -290,23 +206,22 @@ static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* s
   if (dev_zero(h, A.work_counter, sizeof(int32_t), st)) return 1;
   const int64_t per_wave = (int64_t)(block / 64) * h->el_size, red = h->xlayout[0] * (int64_t)block;
   A.pool_doubles = (int32_t)(per_wave > red ? per_wave : red);
-  size_t sz = sizeof(A);
-  void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &A, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
   // (batch launches of the solver with one 64-thread workgroup per problem, not sharded, run the build of the kernels that is compiled for
   //  exactly that shape when it was loaded: build.py batch_only)
   hipFunction_t fn = (h->fn_solve_batch && (A.mode == 0 || A.mode == 2) && A.wide <= 1 && block == 64 && !h->sharded) ? h->fn_solve_batch : h->fn_solve;
-  HIPCHK(h, hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, (unsigned)(A.pool_doubles * sizeof(double)), st, nullptr, cfg));
+  return h->launch(fn, grid, block, (unsigned)(A.pool_doubles * sizeof(double)), st, &A, sizeof(A));
 #else
-  (void)grid; (void)block; (void)stream_v;
+  (void)h; (void)grid; (void)block; (void)stream_v;
   dompc_hostemu_run(&A);
-#endif
   return 0;
+#endif
 }
 
 extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) {
   if (!desc || !out) { g_create_error = "null argument"; return 1; }
   dompc_handle* h = new dompc_handle();
   h->d = *desc;
+  h->device = desc->device;
   auto fail = [&](int) { g_create_error = h->error; dompc_destroy(h); *out = nullptr; return 1; };
   const dompc_problem_desc& d = h->d;
   if (d.n_edges <= 0 || d.n_nodes <= 0 || d.n_opt_x <= 0) { h->error = "empty problem description"; return fail(1); }
@@ -320,21 +235,14 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   if (const char* be = getenv("DOMPC_BLOCK")) { h->block = atoi(be); h->block_auto = false; }   // tuning aid (64/128/256)
   if (h->block != 64 && h->block != 128 && h->block != 256) { h->error = "block_threads must be 64, 128 or 256"; return fail(1); }
 #ifndef DOMPC_HOST_EMU
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-    h->error = "no HIP device available: the dompc IPM backend requires an AMD GPU (gfx950)";
-    return fail(1);
-  }
-  if (hipSetDevice(d.device) != hipSuccess) { h->error = "hipSetDevice failed"; return fail(1); }
-  if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { h->error = "hipStreamCreate failed"; return fail(1); }
+  if (h->open_device("IPM backend")) return fail(1);
   if (hipHostMalloc((void**)&h->abort_word, 64, hipHostMallocMapped) != hipSuccess) { h->error = "hipHostMalloc failed"; return fail(1); }
   *h->abort_word = 0;
   if (!d.code_object_path) { h->error = "code_object_path is null"; return fail(1); }
   h->code_path = d.code_object_path;
-  if (hipModuleLoad(&h->module, h->code_path.c_str()) != hipSuccess) {
-    h->error = "hipModuleLoad failed for " + h->code_path;
+  if (h->load_module(h->code_path.c_str(), &h->module, {{"dompc_solve_kernel", &h->fn_solve}, {"dompc_model_info_kernel", &h->fn_info}},
+                     "code object lacks dompc kernels: " + h->code_path))
     return fail(1);
-  }
   {
     // optional sibling `<name>_batch.hsaco` (build.py: batch_only): the same kernels compiled for "one 64-thread workgroup per problem" only
     std::string bp = h->code_path;
@@ -344,18 +252,10 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
       FILE* f = fopen(bp.c_str(), "rb");
       if (f) {
         fclose(f);
-        if (hipModuleLoad(&h->module_batch, bp.c_str()) != hipSuccess ||
-            hipModuleGetFunction(&h->fn_solve_batch, h->module_batch, "dompc_solve_kernel") != hipSuccess) {
-          h->error = "hipModuleLoad failed for " + bp;
+        if (h->load_module(bp.c_str(), &h->module_batch, {{"dompc_solve_kernel", &h->fn_solve_batch}}, "hipModuleLoad failed for " + bp))
           return fail(1);
-        }
       }
     }
-  }
-  if (hipModuleGetFunction(&h->fn_solve, h->module, "dompc_solve_kernel") != hipSuccess ||
-      hipModuleGetFunction(&h->fn_info, h->module, "dompc_model_info_kernel") != hipSuccess) {
-    h->error = "code object lacks dompc kernels: " + h->code_path;
-    return fail(1);
   }
 #else
   h->block = 1;
@@ -370,17 +270,13 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
 #ifndef DOMPC_HOST_EMU
   auto query_info = [&](hipFunction_t fn, int64_t* info_o, char* hash_o) -> int {
     int32_t* in_d; int64_t* out_d; char* hash_d;
-    if (dev_alloc(h, (void**)&in_d, sizeof(in_h)) || dev_alloc(h, (void**)&out_d, sizeof(info)) ||
-        dev_alloc(h, (void**)&hash_d, sizeof(hash))) return 1;
-    if (h2d(h, in_d, in_h, sizeof(in_h))) return 1;
+    if (h->alloc((void**)&in_d, sizeof(in_h)) || h->alloc((void**)&out_d, sizeof(info)) ||
+        h->alloc((void**)&hash_d, sizeof(hash))) return 1;
+    if (h->h2d(in_d, in_h, sizeof(in_h))) return 1;
     if (dev_zero(h, out_d, sizeof(info), h->stream)) return 1;
     struct { const int32_t* a; int64_t* b; char* c; } args = {in_d, out_d, hash_d};
-    size_t sz = sizeof(args);
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    if (hipModuleLaunchKernel(fn, 1, 1, 1, 64, 1, 1, 0, h->stream, nullptr, cfg) != hipSuccess) {
-      h->error = "launch of dompc_model_info_kernel failed"; return 1;
-    }
-    if (d2h(h, info_o, out_d, sizeof(info)) || d2h(h, hash_o, hash_d, sizeof(hash)) || dev_sync(h)) return 1;
+    if (h->launch(fn, 1, 64, 0, h->stream, &args, sizeof(args))) { h->error = "launch of dompc_model_info_kernel failed"; return 1; }
+    if (h->d2h(info_o, out_d, sizeof(info)) || h->d2h(hash_o, hash_d, sizeof(hash)) || h->sync()) return 1;
     return 0;
   };
   if (query_info(h->fn_info, info, hash)) return fail(1);
@@ -396,7 +292,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
     for (int i = 0; same && i < 20; ++i) same = info_b[i] == info[i];
     same = same && strncmp(hash, hash_b, 63) == 0;
     if (!same) {
-      hipModuleUnload(h->module_batch);
+      h->unload_module(h->module_batch);
       h->module_batch = nullptr;
       h->fn_solve_batch = nullptr;
       h->batch_object_stale = true;
@@ -407,19 +303,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   dompc_hostemu_model_info(in_h, info, hash);
 #endif
   const int64_t want[9] = {d.nx, d.nu, d.np, d.ntvp, d.ne, d.ns, d.M == 0 ? 0 : d.deg, d.M == 0 ? 1 : d.ni, d.M};
-  for (int i = 0; i < 9; ++i)
-    if (info[i] != want[i]) {
-      char buf[256];
-      snprintf(buf, sizeof(buf), "code object was built for different model dimensions (field %d: %lld vs %lld)", i,
-               (long long)info[i], (long long)want[i]);
-      h->error = buf;
-      return fail(1);
-    }
-  if (info[11] != (int64_t)sizeof(dompc::KArgs)) { h->error = "KArgs layout mismatch between runtime and code object"; return fail(1); }
-  if (d.model_hash && strncmp(d.model_hash, hash, 63) != 0) {
-    h->error = std::string("model hash mismatch: code object ") + hash + " vs description " + d.model_hash;
-    return fail(1);
-  }
+  if (h->check_info("", info, want, 9, 11, sizeof(dompc::KArgs), hash, d.model_hash)) return fail(1);
   h->ws_stride = info[9];
   h->sweep_block = info[10];
   for (int i = 0; i < 4; ++i) h->xlayout[i] = info[12 + i];
@@ -531,31 +415,31 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
 #else
   A.abort_flag = h->abort_word;
 #endif
-  if (dev_alloc(h, (void**)&A.ws, sizeof(double) * (size_t)h->ws_stride * h->n_slots)) return fail(1);
+  if (h->alloc((void**)&A.ws, sizeof(double) * (size_t)h->ws_stride * h->n_slots)) return fail(1);
 #ifndef DOMPC_HOST_EMU
   if (const char* fill = getenv("DOMPC_WS_FILL")) {      // debugging aid: poison the workspace (uninitialised reads)
     if (hipMemset(A.ws, atoi(fill), sizeof(double) * (size_t)h->ws_stride * h->n_slots) != hipSuccess) { h->error = "hipMemset failed"; return fail(1); }
   }
 #endif
-  if (dev_alloc(h, (void**)&A.work_counter, 64)) return fail(1);
+  if (h->alloc((void**)&A.work_counter, 64)) return fail(1);
   A.lb_sh = A.ub_sh = nullptr;
   {
     const char* sb = getenv("DOMPC_SHARED_BOUNDS");      // (measurement aid: 0 = per-slot copies of the bounds)
     if (!sb || atoi(sb) != 0) {
-      if (dev_alloc(h, (void**)&A.lb_sh, sizeof(double) * (size_t)d.n_opt_x)) return fail(1);
-      if (dev_alloc(h, (void**)&A.ub_sh, sizeof(double) * (size_t)d.n_opt_x)) return fail(1);
+      if (h->alloc((void**)&A.lb_sh, sizeof(double) * (size_t)d.n_opt_x)) return fail(1);
+      if (h->alloc((void**)&A.ub_sh, sizeof(double) * (size_t)d.n_opt_x)) return fail(1);
     }
   }
   // wide mode (small batches): up to 64 slots x 32 workgroups
-  if (dev_alloc(h, (void**)&A.wide_bar, sizeof(uint32_t) * dompc::WIDE_BAR_STRIDE * 64)) return fail(1);
-  if (dev_alloc(h, (void**)&A.wide_flags, sizeof(int32_t) * 8 * 64)) return fail(1);
-  if (dev_alloc(h, (void**)&A.wide_partials, sizeof(double) * 64 * 2 * 32 * 12)) return fail(1);
+  if (h->alloc((void**)&A.wide_bar, sizeof(uint32_t) * dompc::WIDE_BAR_STRIDE * 64)) return fail(1);
+  if (h->alloc((void**)&A.wide_flags, sizeof(int32_t) * 8 * 64)) return fail(1);
+  if (h->alloc((void**)&A.wide_partials, sizeof(double) * 64 * 2 * 32 * 12)) return fail(1);
   for (int i = 0; i < 8; ++i)
-    if (dev_alloc(h, (void**)&h->s_dbg[i], sizeof(double) * (size_t)(d.n_opt_x > d.n_g ? d.n_opt_x : d.n_g))) return fail(1);
-  if (dev_alloc(h, (void**)&h->s_trace, sizeof(double) * 8 * h->trace_cap)) return fail(1);
+    if (h->alloc((void**)&h->s_dbg[i], sizeof(double) * (size_t)(d.n_opt_x > d.n_g ? d.n_opt_x : d.n_g))) return fail(1);
+  if (h->alloc((void**)&h->s_trace, sizeof(double) * 8 * h->trace_cap)) return fail(1);
   A.trace = h->s_trace; A.trace_cap = h->trace_cap;
   if (const char* xt = getenv("DOMPC_EXTRA_TRAFFIC")) A.trace_pad = atoi(xt);    // measurement aid, see sweep()
-  if (dev_sync(h)) return fail(1);
+  if (h->sync()) return fail(1);
   // the description's table pointers are not valid after return
   h->d.level_node_start = nullptr;
   *out = h;
@@ -645,9 +529,7 @@ extern "C" int dompc_set_sharding(dompc_handle* h, const dompc_shard_desc* s) {
 #else
   if (!s->allreduce) { h->error = "the host emulation needs an allreduce callback"; return 1; }
 #endif
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipSetDevice(d.device));
-#endif
+  if (h->set_device()) return 1;
   if (s->xbuf_doubles < dompc_exchange_doubles(h, s->world, s->n_cut)) { h->error = "exchange buffer too small (dompc_exchange_doubles)"; return 1; }
   int rc = 0;
   rc |= upload(h, &A.x_mask, s->x_mask, d.n_opt_x);
@@ -679,7 +561,7 @@ extern "C" int dompc_set_sharding(dompc_handle* h, const dompc_shard_desc* s) {
 #else
   A.x_callback = s->allreduce; A.x_ctx = s->ctx;
 #endif
-  if (dev_sync(h)) return 1;
+  if (h->sync()) return 1;
   h->sharded = true;
   return 0;
 }
@@ -747,9 +629,7 @@ extern "C" int dompc_solve_batch_device(dompc_handle* h, int32_t B, const double
   if (!h) return 1;
   if (B <= 0) return 0;
   if (!x0 || !lbx || !ubx || !lbg || !ubg || !p) { h->error = "null input pointer"; return 1; }
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipSetDevice(h->d.device));
-#endif
+  if (h->set_device()) return 1;
   dompc::KArgs A = h->base;
   A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.lbg = lbg; A.ubg = ubg; A.p = p;
   A.x_out = x; A.g_out = g; A.lam_x_out = lam_x; A.lam_g_out = lam_g; A.f_out = f; A.stats = stats;
@@ -846,22 +726,20 @@ extern "C" int dompc_solve_batch(dompc_handle* h, int32_t B, const double* x0, c
   if (B <= 0) return 0;
   if (!x0 || !lbx || !ubx || !lbg || !ubg || !p) { h->error = "null input pointer"; return 1; }
   auto t0 = std::chrono::steady_clock::now();
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipSetDevice(h->d.device));
-#endif
+  if (h->set_device()) return 1;
   const dompc_problem_desc& d = h->d;
   if (ensure_staging(h, B)) return 1;
   int rc = 0;
-  rc |= h2d(h, h->s_x0, x0, sizeof(double) * (size_t)B * d.n_opt_x);
-  rc |= h2d(h, h->s_p, p, sizeof(double) * (size_t)B * d.n_opt_p);
-  rc |= h2d(h, h->s_lbx, lbx, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_ubx, ubx, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_lbg, lbg, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_ubg, ubg, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_x0, x0, sizeof(double) * (size_t)B * d.n_opt_x);
+  rc |= h->h2d(h->s_p, p, sizeof(double) * (size_t)B * d.n_opt_p);
+  rc |= h->h2d(h->s_lbx, lbx, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_ubx, ubx, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_lbg, lbg, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_ubg, ubg, sizeof(double) * d.n_g);
   if (rc) return 1;
   static const bool timing = getenv("DOMPC_TIMING") != nullptr;       // measurement aid: where the wall time of a host-buffer call goes (stderr)
   auto t1 = std::chrono::steady_clock::now();
-  if (h->sharded && dev_sync(h)) return 1;      // the sharded solve runs on its own stream: inputs must have landed
+  if (h->sharded && h->sync()) return 1;      // the sharded solve runs on its own stream: inputs must have landed
   if (dompc_solve_batch_device(h, B, h->s_x0, h->s_lbx, h->s_ubx, h->s_lbg, h->s_ubg, h->s_p, h->s_x, h->s_g, h->s_lamx,
                                h->s_lamg, h->s_f, h->s_stats, own_stream(h)))
     return 1;
@@ -873,13 +751,13 @@ extern "C" int dompc_solve_batch(dompc_handle* h, int32_t B, const double* x0, c
   auto t2 = std::chrono::steady_clock::now();
 #endif
   auto t3 = std::chrono::steady_clock::now();
-  if (x) rc |= d2h(h, x, h->s_x, sizeof(double) * (size_t)B * d.n_opt_x);
-  if (g) rc |= d2h(h, g, h->s_g, sizeof(double) * (size_t)B * d.n_g);
-  if (lam_x) rc |= d2h(h, lam_x, h->s_lamx, sizeof(double) * (size_t)B * d.n_opt_x);
-  if (lam_g) rc |= d2h(h, lam_g, h->s_lamg, sizeof(double) * (size_t)B * d.n_g);
-  if (f) rc |= d2h(h, f, h->s_f, sizeof(double) * (size_t)B);
-  if (stats) rc |= d2h(h, stats, h->s_stats, sizeof(dompc_stats) * (size_t)B);
-  if (rc || dev_sync(h)) return 1;
+  if (x) rc |= h->d2h(x, h->s_x, sizeof(double) * (size_t)B * d.n_opt_x);
+  if (g) rc |= h->d2h(g, h->s_g, sizeof(double) * (size_t)B * d.n_g);
+  if (lam_x) rc |= h->d2h(lam_x, h->s_lamx, sizeof(double) * (size_t)B * d.n_opt_x);
+  if (lam_g) rc |= h->d2h(lam_g, h->s_lamg, sizeof(double) * (size_t)B * d.n_g);
+  if (f) rc |= h->d2h(f, h->s_f, sizeof(double) * (size_t)B);
+  if (stats) rc |= h->d2h(stats, h->s_stats, sizeof(dompc_stats) * (size_t)B);
+  if (rc || h->sync()) return 1;
   if (timing) {
     auto t4 = std::chrono::steady_clock::now();
     auto us = [](auto a, auto b) { return std::chrono::duration<double, std::micro>(b - a).count(); };
@@ -904,9 +782,7 @@ extern "C" int dompc_sweep_batch_device(dompc_handle* h, int32_t B, const double
   if (!h) return 1;
   if (B <= 0) return 0;
   if (!x || !lam || !p || !g) { h->error = "null pointer"; return 1; }      // (blocks may be null: residuals only - the timing of the sweep itself, bench.py)
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipSetDevice(h->d.device));
-#endif
+  if (h->set_device()) return 1;
   dompc::KArgs A = h->base;
   A.p = p; A.sw_x = x; A.sw_lam = lam; A.sw_g = g; A.sw_blocks = blocks;
   A.batch = B; A.mode = 2;
@@ -922,22 +798,20 @@ static int newton_step_impl(dompc_handle* h, const double* x, const double* lam_
                             const double* ubg, const double* p, double mu, double delta_w, double* dx,
                             double* dlam, double* rd, double* c, int at_solution) {
   if (!h) return 1;
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipSetDevice(h->d.device));
-#endif
+  if (h->set_device()) return 1;
   const dompc_problem_desc& d = h->d;
   if (h->sharded) { h->error = "dompc_debug_newton_step is not available on a sharded handle (call dompc_set_sharding(h, NULL) first)"; return 1; }
   if (ensure_staging(h, 1)) return 1;
   int rc = 0;
-  rc |= h2d(h, h->s_x0, x, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_p, p, sizeof(double) * d.n_opt_p);
-  rc |= h2d(h, h->s_lbx, lbx, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_ubx, ubx, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_lbg, lbg, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_ubg, ubg, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_dbg[0], lam_g, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_dbg[1], zl, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_dbg[2], zu, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_x0, x, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_p, p, sizeof(double) * d.n_opt_p);
+  rc |= h->h2d(h->s_lbx, lbx, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_ubx, ubx, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_lbg, lbg, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_ubg, ubg, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_dbg[0], lam_g, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_dbg[1], zl, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_dbg[2], zu, sizeof(double) * d.n_opt_x);
   if (rc) return 1;
   dompc::KArgs A = h->base;
   A.x0 = h->s_x0; A.lbx = h->s_lbx; A.ubx = h->s_ubx; A.lbg = h->s_lbg; A.ubg = h->s_ubg; A.p = h->s_p;
@@ -945,12 +819,12 @@ static int newton_step_impl(dompc_handle* h, const double* x, const double* lam_
   A.dbg_dx = h->s_dbg[3]; A.dbg_dlam = h->s_dbg[4]; A.dbg_rd = h->s_dbg[5]; A.dbg_c = h->s_dbg[6];
   A.dbg_mu = mu; A.dbg_delta = delta_w;
   A.batch = 1; A.mode = 1; A.dbg_at_solution = at_solution;
-  if (launch(h, A, 1, fit_block(h, 256), main_stream(h))) return 1;
-  if (dx) rc |= d2h(h, dx, h->s_dbg[3], sizeof(double) * d.n_opt_x);
-  if (dlam) rc |= d2h(h, dlam, h->s_dbg[4], sizeof(double) * d.n_g);
-  if (rd) rc |= d2h(h, rd, h->s_dbg[5], sizeof(double) * d.n_opt_x);
-  if (c) rc |= d2h(h, c, h->s_dbg[6], sizeof(double) * d.n_g);
-  if (rc || dev_sync(h)) return 1;
+  if (launch(h, A, 1, fit_block(h, 256), h->stream_ptr())) return 1;
+  if (dx) rc |= h->d2h(dx, h->s_dbg[3], sizeof(double) * d.n_opt_x);
+  if (dlam) rc |= h->d2h(dlam, h->s_dbg[4], sizeof(double) * d.n_g);
+  if (rd) rc |= h->d2h(rd, h->s_dbg[5], sizeof(double) * d.n_opt_x);
+  if (c) rc |= h->d2h(c, h->s_dbg[6], sizeof(double) * d.n_g);
+  if (rc || h->sync()) return 1;
   return 0;
 }
 
@@ -971,9 +845,7 @@ extern "C" int dompc_newton_steps_at_solution(dompc_handle* h, int32_t B, const 
                                               const double* zu, const double* lbx, const double* ubx, const double* lbg,
                                               const double* ubg, const double* p, double mu, double* dx, double* dlam) {
   if (!h || B < 1) return 1;
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipSetDevice(h->d.device));
-#endif
+  if (h->set_device()) return 1;
   const dompc_problem_desc& d = h->d;
   if (h->sharded) { h->error = "dompc_newton_steps_at_solution is not available on a sharded handle"; return 1; }
   int chunk = h->n_slots < B ? h->n_slots : B;
@@ -983,28 +855,28 @@ extern "C" int dompc_newton_steps_at_solution(dompc_handle* h, int32_t B, const 
   if (chunk < 1) chunk = 1;
   if (ensure_staging(h, chunk)) return 1;
   int rc = 0;
-  rc |= h2d(h, h->s_x0, x, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_lbx, lbx, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_ubx, ubx, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_lbg, lbg, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_ubg, ubg, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_dbg[0], lam_g, sizeof(double) * d.n_g);
-  rc |= h2d(h, h->s_dbg[1], zl, sizeof(double) * d.n_opt_x);
-  rc |= h2d(h, h->s_dbg[2], zu, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_x0, x, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_lbx, lbx, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_ubx, ubx, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_lbg, lbg, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_ubg, ubg, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_dbg[0], lam_g, sizeof(double) * d.n_g);
+  rc |= h->h2d(h->s_dbg[1], zl, sizeof(double) * d.n_opt_x);
+  rc |= h->h2d(h->s_dbg[2], zu, sizeof(double) * d.n_opt_x);
   if (rc) return 1;
   for (int b0 = 0; b0 < B; b0 += chunk) {
     const int nb = (B - b0 < chunk) ? B - b0 : chunk;
-    if (h2d(h, h->s_p, p + (size_t)b0 * d.n_opt_p, sizeof(double) * (size_t)nb * d.n_opt_p)) return 1;
+    if (h->h2d(h->s_p, p + (size_t)b0 * d.n_opt_p, sizeof(double) * (size_t)nb * d.n_opt_p)) return 1;
     dompc::KArgs A = h->base;
     A.x0 = h->s_x0; A.lbx = h->s_lbx; A.ubx = h->s_ubx; A.lbg = h->s_lbg; A.ubg = h->s_ubg; A.p = h->s_p;
     A.dbg_lam = h->s_dbg[0]; A.dbg_zl = h->s_dbg[1]; A.dbg_zu = h->s_dbg[2];
     A.dbg_dx = h->s_x; A.dbg_dlam = h->s_lamg; A.dbg_rd = h->s_lamx; A.dbg_c = h->s_g;        // (batch staging buffers: nb rows each)
     A.dbg_mu = mu; A.dbg_delta = 0.0;
     A.batch = nb; A.mode = 1; A.dbg_at_solution = 1;
-    if (launch(h, A, nb, fit_block(h, 256), main_stream(h))) return 1;
-    rc |= d2h(h, dx + (size_t)b0 * d.n_opt_x, h->s_x, sizeof(double) * (size_t)nb * d.n_opt_x);
-    rc |= d2h(h, dlam + (size_t)b0 * d.n_g, h->s_lamg, sizeof(double) * (size_t)nb * d.n_g);
-    if (rc || dev_sync(h)) return 1;
+    if (launch(h, A, nb, fit_block(h, 256), h->stream_ptr())) return 1;
+    rc |= h->d2h(dx + (size_t)b0 * d.n_opt_x, h->s_x, sizeof(double) * (size_t)nb * d.n_opt_x);
+    rc |= h->d2h(dlam + (size_t)b0 * d.n_g, h->s_lamg, sizeof(double) * (size_t)nb * d.n_g);
+    if (rc || h->sync()) return 1;
   }
   return 0;
 }
@@ -1014,6 +886,6 @@ extern "C" int dompc_newton_steps_at_solution(dompc_handle* h, int32_t B, const 
 extern "C" int dompc_debug_get_trace(dompc_handle* h, double* out, int32_t max_rows) {
   if (!h || !out) return 1;
   int rows = max_rows < h->trace_cap ? max_rows : h->trace_cap;
-  if (d2h(h, out, h->s_trace, sizeof(double) * 8 * (size_t)rows) || dev_sync(h)) return 1;
+  if (h->d2h(out, h->s_trace, sizeof(double) * 8 * (size_t)rows) || h->sync()) return 1;
   return 0;
 }

@@ -19,7 +19,7 @@ from typing import Callable, Optional
 
 import numpy as np
 
-from . import build, lowering
+from . import _native, build, lowering
 from .model import Model
 from .simulator import _flat_struct, _rows
 from .structs import NumStruct
@@ -159,14 +159,7 @@ class EKF:
         self.model_hash = self.generated_header.rsplit('EKF_MODEL_HASH "', 1)[1].split('"')[0]
         self._check_validity()
         if _lib_path is None:
-            import os
-            if not os.environ.get("DOMPC_NO_TORCH_FIRST"):
-                try:                      # torch ships its own HIP runtime: it has to be the first one in the process
-                    import torch          # noqa: F401
-                    torch.cuda.is_available()
-                except ImportError:
-                    pass
-            _lib_path = build.runtime_library()
+            _lib_path = _native.runtime_library()
             _code_object = build.ekf_code_object(self.generated_header, self.model_hash)
         self.code_object = _code_object
         self._lib = _bind(_lib_path)
@@ -175,11 +168,13 @@ class EKF:
                     device=self.settings.gpu_index, max_steps=self.settings.max_steps,
                     t_step=float(self.settings.t_step), reltol=float(self.settings.reltol), abstol=float(self.settings.abstol))
         h = C.c_void_p()
-        if self._lib.dompc_ekf_create(C.byref(d), C.byref(h)) != 0:
-            raise RuntimeError("dompc_ekf_create failed: " + (self._lib.dompc_ekf_last_error(None) or b"?").decode())
+        _native.check(self._lib.dompc_ekf_create(C.byref(d), C.byref(h)), "dompc_ekf_create failed: ", self._lib.dompc_ekf_last_error)
         self._h = h
         self.counter = 0
         self.flags["setup"] = True
+
+    def _check(self, rc):
+        _native.check(rc, "dompc_ekf: ", self._lib.dompc_ekf_last_error, self._h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -227,8 +222,7 @@ class EKF:
         ptr = lambda a: a.ctypes.data_as(C.c_void_p)      # noqa: E731
         rc = self._lib.dompc_ekf_step_batch(self._h, B, ptr(X), ptr(Pc), ptr(Yv), ptr(u), ptr(tvp), ptr(p), ptr(Qm), ptr(Rm), mask,
                                             ptr(xo), ptr(Po), ptr(status))
-        if rc != 0:
-            raise RuntimeError("dompc_ekf: " + (self._lib.dompc_ekf_last_error(self._h) or b"?").decode())
+        self._check(rc)
         return {"x": xo, "P": Po, "status": status & 0xFF, "n_steps": status >> 8}
 
     def step_batch_device(self, B, x, Pcov, y, u, tvp, p, Q, R, status=0, shared_mask=0, stream=0):
@@ -237,8 +231,7 @@ class EKF:
         args = [C.c_void_p(int(a) if a else None) for a in (x, Pcov, y, u, tvp, p, Q, R)]
         rc = self._lib.dompc_ekf_step_batch_device(self._h, int(B), *args, int(shared_mask), C.c_void_p(int(status) if status else None),
                                                    C.c_void_p(int(stream) if stream else None))
-        if rc != 0:
-            raise RuntimeError("dompc_ekf: " + (self._lib.dompc_ekf_last_error(self._h) or b"?").decode())
+        self._check(rc)
 
     def make_step(self, y_next, u_next, Q_k, R_k) -> np.ndarray:
         """One step of the filter (_ekf.py:231-329): the new state estimate from the measurement `y_next` and the input `u_next` with

@@ -20,7 +20,7 @@ from typing import Callable, Dict, Optional
 
 import numpy as np
 
-from . import build, lowering, sym
+from . import _native, build, lowering, sym
 from .model import Model
 from .structs import Entry, Layout, NumStruct
 
@@ -177,14 +177,7 @@ class Simulator:
         self.generated_header = self._lower()
         self.model_hash = self.generated_header.rsplit('PLANT_MODEL_HASH "', 1)[1].split('"')[0]
         if _lib_path is None:
-            import os
-            if not os.environ.get("DOMPC_NO_TORCH_FIRST"):
-                try:                      # torch ships its own HIP runtime: it has to be the first one in the process
-                    import torch          # noqa: F401
-                    torch.cuda.is_available()
-                except ImportError:
-                    pass
-            _lib_path = build.runtime_library()
+            _lib_path = _native.runtime_library()
             _code_object = build.plant_code_object(self.generated_header, self.model_hash)
         self._lib = _bind(_lib_path)
         d = PlantDesc(nx=m.n_x, nu=m.n_u, np=m.n_p, ntvp=m.n_tvp, nw=m.n_w, nv=m.n_v, ny=m.n_y,
@@ -193,15 +186,13 @@ class Simulator:
                       device=self.settings.gpu_index, max_steps=self.settings.max_steps,
                       t_step=float(self.settings.t_step), reltol=float(self.settings.reltol), abstol=float(self.settings.abstol))
         h = C.c_void_p()
-        if self._lib.dompc_plant_create(C.byref(d), C.byref(h)) != 0:
-            raise RuntimeError("dompc_plant_create failed: " + (self._lib.dompc_plant_last_error(None) or b"?").decode())
+        _native.check(self._lib.dompc_plant_create(C.byref(d), C.byref(h)), "dompc_plant_create failed: ", self._lib.dompc_plant_last_error)
         self._h = h
         tool = str(self.settings.integration_tool).lower()
         methods = {"cvodes": 0, "idas": 0, "auto": 0, "dopri5": 1, "rk45": 1, "sdirk4": 2, "implicit": 2}
         if tool not in methods:
             raise ValueError(f"integration_tool {self.settings.integration_tool!r}: expected one of {sorted(methods)}")
-        if self._lib.dompc_plant_set_method(h, methods[tool], int(self.settings.integration_opts.get("explicit_limit", 0))) != 0:
-            raise RuntimeError("dompc_plant: " + (self._lib.dompc_plant_last_error(h) or b"?").decode())
+        self._check(self._lib.dompc_plant_set_method(h, methods[tool], int(self.settings.integration_opts.get("explicit_limit", 0))))
         self._seed_z()
         self.flags["setup"] = True
 
@@ -210,6 +201,9 @@ class Simulator:
         if self.model.n_z and self._h:
             z = np.ascontiguousarray(self._z0.master, dtype=np.float64)
             self._lib.dompc_plant_set_z0(self._h, z.ctypes.data_as(C.c_void_p))
+
+    def _check(self, rc):
+        _native.check(rc, "dompc_plant: ", self._lib.dompc_plant_last_error, self._h)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -274,8 +268,7 @@ class Simulator:
         self._lib.dompc_plant_set_z_carry(self._h, 1 if carry_z else 0)
         rc = self._lib.dompc_plant_step_batch(self._h, B, ptr(X), ptr(u), ptr(tvp), ptr(p), ptr(w), ptr(v), mask,
                                               ptr(xn), ptr(y), ptr(status))
-        if rc != 0:
-            raise RuntimeError("dompc_plant: " + (self._lib.dompc_plant_last_error(self._h) or b"?").decode())
+        self._check(rc)
         return {"x": xn, "y": y[:, :m.n_y], "status": status & 0xFF, "n_steps": status >> 8}
 
     def step_batch_device(self, B, x, u, tvp, p, x_next, y=0, status=0, w=0, v=0, shared_mask=0, stream=0):
@@ -284,8 +277,7 @@ class Simulator:
         outs = [C.c_void_p(int(a) if a else None) for a in (x_next, y, status)]
         rc = self._lib.dompc_plant_step_batch_device(self._h, int(B), *args, int(shared_mask), *outs,
                                                      C.c_void_p(int(stream) if stream else None))
-        if rc != 0:
-            raise RuntimeError("dompc_plant: " + (self._lib.dompc_plant_last_error(self._h) or b"?").decode())
+        self._check(rc)
 
     def make_step(self, u0=None, v0=None, w0=None) -> np.ndarray:
         """One closed-loop sample (simulator.py:757-850): integrates x0 over t_step with u0 and the current p / tvp,

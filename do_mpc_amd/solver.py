@@ -18,7 +18,7 @@ from typing import Dict, Optional
 
 import numpy as np
 
-from . import build
+from . import _native, build
 from .structure import ProblemStructure
 
 _i32p = C.POINTER(C.c_int32)
@@ -165,14 +165,7 @@ class HipIpmSolver:
                           device=device, max_batch=max_batch, n_slots=n_slots, block_threads=block_threads)
         self.shard_capable = bool(shard) or _code_object == ""
         if _lib_path is None:
-            import os
-            if not os.environ.get("DOMPC_NO_TORCH_FIRST"):
-                try:                      # torch ships its own HIP runtime: it has to be the first one in the process
-                    import torch          # noqa: F401
-                    torch.cuda.is_available()
-                except ImportError:
-                    pass
-            _lib_path = build.runtime_library()
+            _lib_path = _native.runtime_library()
             _code_object = build.model_code_object(header_text, model_hash, shard=bool(shard))
             sibling = _code_object[:-len(".hsaco")] + "_batch.hsaco"
             # (a sibling left behind by an earlier handle is refreshed with the general object: the runtime launches whatever lies there)
@@ -221,9 +214,7 @@ class HipIpmSolver:
                 self.ignored_options.append(k)     # print levels, linear solver, ... : no meaning here
         self.options = d.opts
         h = C.c_void_p()
-        rc = self._lib.dompc_create(C.byref(d), C.byref(h))
-        if rc != 0:
-            raise RuntimeError("dompc_create failed: " + (self._lib.dompc_last_error(None) or b"?").decode())
+        _native.check(self._lib.dompc_create(C.byref(d), C.byref(h)), "dompc_create failed: ", self._lib.dompc_last_error)
         self._h = h
         # 0: no launch-shape-specific sibling code object, 1: loaded, 2: found but stale (other sources / model) and therefore not used
         self.batch_object_state = int(self._lib.dompc_batch_object_state(h))
@@ -249,8 +240,7 @@ class HipIpmSolver:
             pass
 
     def _check(self, rc):
-        if rc != 0:
-            raise RuntimeError("dompc: " + (self._lib.dompc_last_error(self._h) or b"?").decode())
+        _native.check(rc, "dompc: ", self._lib.dompc_last_error, self._h)
 
     # ------------------------------------------------------------------ nlpsol-like call
     def __call__(self, x0, lbx, ubx, lbg, ubg, p, lam_x0=None, lam_g0=None) -> dict:

@@ -1,40 +1,14 @@
-"""TEST-ONLY helpers of the extended Kalman filter tests: the host-emulation builder (csrc/dompc_ekf.hip compiled by g++ with
--DDOMPC_HOST_EMU, the text that ships) and a numpy / scipy twin of the reference's recursion on the model's own sym.Functions."""
-import hashlib
+"""TEST-ONLY helpers of the extended Kalman filter tests: setup on the host emulation (hostemu_build.ekf_hostemu_library:
+csrc/dompc_ekf.hip compiled by g++ with -DDOMPC_HOST_EMU, the text that ships) and a numpy / scipy twin of the reference's recursion
+on the model's own sym.Functions."""
 import os
-import shutil
 
 import numpy as np
 
 from do_mpc_amd import sym
-from do_mpc_amd.build import CSRC, _compile_to, _fresh, _locked, _sources_digest, _write_atomic
+from hostemu_build import OUT, ekf_hostemu_library  # noqa: F401  (callers name both through this module)
 
-OUT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_hostemu")
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def ekf_hostemu_library(header_text: str, model_hash: str, out_dir: str = OUT, force: bool = False) -> str:
-    """TEST-ONLY: filter kernel + runtime compiled for the host (g++); lives in tests/_hostemu, never loaded by the product."""
-    os.makedirs(out_dir, exist_ok=True)
-    hdr = os.path.join(out_dir, f"ekf_gen_{model_hash}.h")
-    defs = os.environ.get("DOMPC_DEFS", "").split()      # extra switches (tools/asan_hostemu.sh: -fsanitize=address): an own library per set
-    tag = ("_" + hashlib.sha256(" ".join(defs).encode()).hexdigest()[:8]) if defs else ""
-    out = os.path.join(out_dir, f"libdompc_ekf_hostemu_{model_hash}{tag}.so")
-    stamp = out + ".stamp"
-    dig = _sources_digest() + hashlib.sha256(header_text.encode()).hexdigest()[:12] + " ".join(defs)
-    if not force and _fresh(out, stamp, dig):
-        return out
-    with _locked(out_dir):
-        if not force and _fresh(out, stamp, dig):
-            return out
-        if not (os.path.exists(hdr) and open(hdr).read() == header_text):
-            _write_atomic(hdr, header_text)
-        cxx = shutil.which("g++") or "g++"
-        cmd = [cxx, "-O2", "-std=c++17", "-fPIC", "-shared", "-DDOMPC_HOST_EMU", *[(d if d.startswith("-") else f"-D{d}") for d in defs],
-               f"-DDOMPC_EKF_HEADER=\"{hdr}\"", "-I", CSRC, os.path.join(CSRC, "dompc_ekf_runtime.cpp"), "-x", "c++", os.path.join(CSRC, "dompc_ekf.hip"), "-lm"]
-        _compile_to(cmd, out, "building filter host emulation")
-        _write_atomic(stamp, dig)
-    return out
 
 
 def setup_on_hostemu(ekf):
