@@ -105,7 +105,7 @@ def runtime_library(force: bool = False) -> str:
             return out
         cmd = [_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
                os.path.join(CSRC, "dompc_runtime.cpp"), os.path.join(CSRC, "dompc_plant_runtime.cpp"),
-               os.path.join(CSRC, "dompc_ekf_runtime.cpp"), "-ldl"]
+               os.path.join(CSRC, "dompc_ekf_runtime.cpp"), os.path.join(CSRC, "dompc_lqr_runtime.cpp"), "-ldl"]
         _compile_to(cmd, out, "building libdompc_ipm.so")
         _write_atomic(stamp, dig)
     return out
@@ -222,3 +222,9 @@ def ekf_code_object(header_text: str, model_hash: str, force: bool = False, rema
     remarks=True: compile again with -Rpass-analysis=kernel-resource-usage and return (path, compiler output) - registers, scratch and
     LDS of the kernels (profiles/ekf_resource_usage.txt)."""
     return _kernel_code_object("ekf", "dompc_ekf.hip", "DOMPC_EKF_HEADER", "ekf_gen.h", "filter", header_text, model_hash, force, remarks)
+
+
+def lqr_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
+    """gfx950 code object of the batched LQR design (csrc/dompc_lqr.hip) for one lowered design (sizes, mode and - for gains_at - the
+    model's Jacobians).  remarks=True: as ekf_code_object (profiles/lqr_resource_usage.txt)."""
+    return _kernel_code_object("lqr", "dompc_lqr.hip", "DOMPC_LQR_HEADER", "lqr_gen.h", "LQR design", header_text, model_hash, force, remarks)

@@ -71,9 +71,11 @@ def install(force: bool = False):
         dm.__doc__ = "do_mpc_amd stand-in exposing do_mpc.model.Model and do_mpc.controller.MPC"
         m_model = types.ModuleType("do_mpc.model")
         m_model.Model = model.Model
+        m_model.LinearModel, m_model.linearize = model.LinearModel, model.linearize
         m_ctrl = types.ModuleType("do_mpc.controller")
         m_ctrl.MPC = controller.MPC
         m_ctrl.MPCSettings = controller.MPCSettings
+        m_ctrl.LQR, m_ctrl.LQRSettings = controller.LQR, controller.LQRSettings
         m_sim = types.ModuleType("do_mpc.simulator")
         m_sim.Simulator = simulator.Simulator
         m_est = types.ModuleType("do_mpc.estimator")

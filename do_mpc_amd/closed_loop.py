@@ -390,3 +390,76 @@ class BatchClosedLoopEKF:
         return {"mpc_stats": cs, "plant_status": (self.pstat.cpu().numpy() & 1), "ekf_status": est & 0xFF, "u0": self.U.cpu().numpy(),
                 "x_true": self.X.cpu().numpy(), "y": self.Y[:, :self.ny].cpu().numpy(), "x_est": self.x_est.cpu().numpy(),
                 "P": self.Pcov.cpu().numpy()}
+
+
+class BatchClosedLoopLQR:
+    """B closed loops LQR -> plant advancing together with the states resident in device memory: per control step the gain
+    u = K (x - xss) + uss (+ u_prev in inputRatePenalization mode: LQR.make_step_batch, a torch expression) and ONE batched plant step.
+    The per-sample loop of the reference is `u0 = lqr.make_step(x0)`, `x0 = simulator.make_step(u0)`
+    (/root/reference/examples/lqr_examples/CSTR_lqr/main.py:75-78).  State feedback: the plant's measurement must be its state.
+    X0: [B][nx]; K: None (lqr.K for every loop) or [B][nu][n], e.g. the schedule of LQR.gains_at; XSS / USS: None (the set-point of
+    set_setpoint), one set-point or one per loop, of the model's size; U_prev0: [B][nu] (default 0, like lqr.u0 after reset).
+    device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests)."""
+
+    def __init__(self, lqr, simulator, X0, K=None, XSS=None, USS=None, device=0, U_prev0=None):
+        import torch
+        self.torch = torch
+        self.lqr, self.sim = lqr, simulator
+        assert lqr.flags["setup"] is True, "LQR is not setup. run setup() function."
+        m = simulator.model
+        ml = lqr.model
+        assert (m.n_x, m.n_u) == (ml.n_x, ml.n_u), "controller and plant must share states and inputs"
+        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
+        X0 = np.asarray(X0, dtype=float).reshape(-1, m.n_x)
+        self.B = B = X0.shape[0]
+        dev = self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
+        t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)      # noqa: E731  (a copy, also on the host)
+        rate = lqr.mode == "inputRatePenalization"
+        if XSS is None and USS is None and hasattr(lqr, "xss"):
+            xs = np.asarray(lqr.xss, float).ravel()
+            XSS, USS = xs[:m.n_x], (xs[m.n_x:] if rate else np.asarray(lqr.uss, float).ravel())
+        self.xss = t(np.zeros((1, m.n_x)) if XSS is None else np.asarray(XSS, float).reshape(-1, m.n_x))
+        self.uss = t(np.zeros((1, m.n_u)) if USS is None else np.asarray(USS, float).reshape(-1, m.n_u))
+        self.K = t(np.asarray(lqr.K if K is None else K, float).reshape(-1, m.n_u, lqr.n_design))
+        assert self.K.shape[0] in (1, B) and self.xss.shape[0] in (1, B) and self.uss.shape[0] in (1, B), "one gain / set-point or one per loop"
+        self.X = t(X0)
+        self.Xn = torch.empty_like(self.X)
+        self.U = t(np.zeros((B, m.n_u)) if U_prev0 is None else np.asarray(U_prev0, float).reshape(B, m.n_u))
+        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
+        ts = float(simulator._t0[0])
+        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
+        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
+        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
+        self.k = 0
+
+    def step(self) -> dict:
+        """one control step of all B loops; returns the inputs applied, the new states and the plant status"""
+        torch, m = self.torch, self.sim.model
+        cuda = self.dev.type == "cuda"
+        if self.k > 0 and (m.n_p or m.n_tvp):      # the plant's parameters at the current loop time (simulator.py:790-800)
+            ts = self.t_sim0 + self.k * self.dt_sim
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
+            if m.n_p:
+                self.p_plant.copy_(up(self.sim.p_fun(ts).master))
+            if m.n_tvp:
+                self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
+        self.U = self.lqr.make_step_batch(self.X, K=self.K, XSS=self.xss, USS=self.uss, U_prev=self.U).contiguous()
+        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
+                                   self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16,
+                                   stream=(torch.cuda.current_stream().cuda_stream if cuda else 0))
+        self.X, self.Xn = self.Xn, self.X
+        self.k += 1
+        if cuda:
+            torch.cuda.synchronize()
+        return {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1)}
+
+    def run(self, n: int) -> dict:
+        """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step"""
+        xs, us, st = [self.X.cpu().numpy().copy()], [], []
+        for _ in range(int(n)):
+            r = self.step()
+            xs.append(r["x"].copy())
+            us.append(r["u0"].copy())
+            st.append(r["plant_status"])
+        return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, self.B, self.sim.model.n_u)),
+                "plant_status": np.stack(st) if st else np.zeros((0, self.B), dtype=np.int32)}

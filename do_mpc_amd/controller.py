@@ -877,3 +877,6 @@ class MPC:
         r = self.S.solve_batch(Xi, self._lb_opt_x.master, self._ub_opt_x.master, self._nlp_cons_lb, self._nlp_cons_ub, P)
         r["u0"] = r["x"][:, ps.iu(0, 0):ps.iu(0, 0) + ps.nu] * self._u_scaling.master
         return r
+
+
+from .lqr import LQR, LQRSettings  # noqa: E402,F401  (do_mpc.controller.LQR: the batched linear quadratic regulator, do_mpc_amd/lqr.py)

@@ -1,0 +1,21 @@
+// dompc_lqr_args.h - kernel argument block of the batched LQR design, shared by the generic host runtime (dompc_lqr_runtime.cpp)
+// and the per-design device code (dompc_lqr.hip).  Plain data, no size that depends on the design.
+#pragma once
+#include <stdint.h>
+
+namespace dompc_lqrk {
+struct Args {
+  double *A, *B;                             // [B][nx][nx], [B][nx][nu] row-major, the DISCRETE pair: read by a code object without a
+                                             // model, written (when not null) by one with a model
+  const double *x, *u, *tvp, *p;             // with a model: operating points [B][nx], [B][nu]; tvp / p per design or shared (stride 0)
+  const double *Q, *R, *Pf;                  // design-size weights [n][n], [nu][nu] and terminal weight [n][n] (finite horizon only);
+                                             // per design or shared (stride 0)
+  double *K, *P;                             // out: gain [B][nu][n], Riccati solution / cost-to-go [B][n][n]
+  int32_t* status;                           // [B] (may be null): bit 0 = the doubling iteration did not converge, bit 1 = singular or
+                                             // non-finite block (K = 0, P = Q are returned); iterations in status >> 8
+  int32_t batch, stride_q, stride_r, stride_pf, stride_tvp, stride_p;
+  int32_t n_horizon;                         // 0: infinite horizon (doubling); > 0: passes of the backward recursion
+  int32_t max_iter;
+  double t_step, tol;
+};
+}  // namespace dompc_lqrk

@@ -1,0 +1,124 @@
+// dompc_lqr_runtime.cpp - host side of the batched LQR design behind the C ABI of include/dompc_ipm.h (dompc_lqr_*).
+// Generic: sizes come from the per-design code object (dompc_lqr_info_kernel).
+// Build flavours as dompc_ekf_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU together with
+// dompc_lqr.hip compiled as C++ (tests/_hostemu; never shipped).
+#include "../../include/dompc_ipm.h"
+#include "dompc_host.h"
+#include "dompc_lqr_args.h"
+
+#ifdef DOMPC_HOST_EMU
+extern "C" void dompc_lqr_hostemu_info(int64_t* out, char* hash);
+extern "C" void dompc_lqr_hostemu_run(const dompc_lqrk::Args* A);
+#endif
+
+static thread_local std::string g_lqr_create_error;
+
+struct dompc_lqr : dompc_host::Context {
+  dompc_lqr_desc d;
+  int32_t cap = 0;
+  double *s_A = nullptr, *s_B = nullptr, *s_x = nullptr, *s_u = nullptr, *s_tvp = nullptr, *s_p = nullptr, *s_Q = nullptr, *s_R = nullptr,
+         *s_Pf = nullptr, *s_K = nullptr, *s_P = nullptr;
+  int32_t* s_st = nullptr;
+#ifndef DOMPC_HOST_EMU
+  hipModule_t module = nullptr;
+  hipFunction_t fn = nullptr, fn_info = nullptr;
+#endif
+};
+
+extern "C" const char* dompc_lqr_last_error(const dompc_lqr* h) { return h ? h->error.c_str() : g_lqr_create_error.c_str(); }
+
+extern "C" void dompc_lqr_destroy(dompc_lqr* h) {
+  if (!h) return;
+  h->close();
+  delete h;
+}
+
+extern "C" int dompc_lqr_create(const dompc_lqr_desc* desc, dompc_lqr** out) {
+  if (!desc || !out) { g_lqr_create_error = "null argument"; return 1; }
+  dompc_lqr* h = new dompc_lqr();
+  h->d = *desc;
+  h->device = desc->device;
+  auto fail = [&]() { g_lqr_create_error = h->error; dompc_lqr_destroy(h); *out = nullptr; return 1; };
+  if (desc->nx <= 0 || desc->nu <= 0) { h->error = "design without states or without inputs"; return fail(); }
+  if (desc->has_model && !desc->discrete && !(desc->t_step > 0.0)) { h->error = "t_step must be positive"; return fail(); }
+  if (desc->n_horizon < 0) { h->error = "n_horizon must not be negative"; return fail(); }
+  int64_t info[16] = {0};
+  char hash[64] = {0};
+#ifndef DOMPC_HOST_EMU
+  if (h->open_device("LQR design") ||
+      h->load_module(desc->code_object_path, &h->module, {{"dompc_lqr_kernel", &h->fn}, {"dompc_lqr_info_kernel", &h->fn_info}},
+                     "code object lacks the design kernels") ||
+      h->query_info(h->fn_info, "dompc_lqr_info_kernel", info, hash))
+    return fail();
+#else
+  dompc_lqr_hostemu_info(info, hash);
+#endif
+  const int64_t want[8] = {desc->nx, desc->nu, desc->n, desc->rate ? 1 : 0, desc->has_model ? 1 : 0,
+                           (desc->discrete || !desc->has_model) ? 1 : 0, desc->np, desc->ntvp};
+  if (h->check_info("design ", info, want, 8, 8, sizeof(dompc_lqrk::Args), hash, desc->model_hash)) return fail();
+  h->d.code_object_path = nullptr; h->d.model_hash = nullptr;
+  *out = h;
+  return 0;
+}
+
+extern "C" int dompc_lqr_design_batch_device(dompc_lqr* h, int32_t B, double* A, double* Bm, const double* x, const double* u,
+                                             const double* tvp, const double* p, const double* Q, const double* R, const double* Pf,
+                                             int32_t shared_mask, double* K, double* P, int32_t* status, void* stream) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  const dompc_lqr_desc& d = h->d;
+  if (!Q || !R || !K || !P || (d.n_horizon > 0 && !Pf) || (!d.has_model && (!A || !Bm)) ||
+      (d.has_model && (!x || !u || (d.ntvp && !tvp) || (d.np && !p)))) { h->error = "null pointer"; return 1; }
+  dompc_lqrk::Args G;
+  memset(&G, 0, sizeof(G));
+  G.A = A; G.B = Bm; G.x = x; G.u = u; G.tvp = tvp; G.p = p; G.Q = Q; G.R = R; G.Pf = Pf; G.K = K; G.P = P; G.status = status;
+  G.batch = B;
+  G.stride_q = (shared_mask & 1) ? 0 : d.n * d.n; G.stride_r = (shared_mask & 2) ? 0 : d.nu * d.nu;
+  G.stride_pf = (shared_mask & 4) ? 0 : d.n * d.n;
+  G.stride_tvp = (shared_mask & 8) ? 0 : d.ntvp; G.stride_p = (shared_mask & 16) ? 0 : d.np;
+  G.n_horizon = d.n_horizon;
+  G.max_iter = d.max_iter > 0 ? d.max_iter : 50;
+  G.t_step = d.t_step; G.tol = d.tol > 0 ? d.tol : 1e-13;
+  if (h->set_device()) return 1;
+#ifndef DOMPC_HOST_EMU
+  // one wavefront per workgroup, four designs per wavefront
+  return h->launch(h->fn, (unsigned)((B + 3) / 4), 64, 0, (hipStream_t)stream, &G, sizeof(G));
+#else
+  (void)stream;
+  dompc_lqr_hostemu_run(&G);
+  return 0;
+#endif
+}
+
+extern "C" int dompc_lqr_design_batch(dompc_lqr* h, int32_t B, const double* A, const double* Bm, const double* x, const double* u,
+                                      const double* tvp, const double* p, const double* Q, const double* R, const double* Pf,
+                                      int32_t shared_mask, double* K_out, double* P_out, double* A_out, double* B_out, int32_t* status) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  const dompc_lqr_desc& d = h->d;
+  if (!K_out || !P_out) { h->error = "null pointer"; return 1; }
+  if (h->set_device()) return 1;
+  const size_t D = sizeof(double);
+  if (h->grow_staging(&h->cap, B, {{(void**)&h->s_A, D * d.nx * d.nx}, {(void**)&h->s_B, D * d.nx * d.nu}, {(void**)&h->s_x, D * d.nx},
+                                   {(void**)&h->s_u, D * d.nu}, {(void**)&h->s_tvp, D * d.ntvp}, {(void**)&h->s_p, D * d.np},
+                                   {(void**)&h->s_Q, D * d.n * d.n}, {(void**)&h->s_R, D * d.nu * d.nu}, {(void**)&h->s_Pf, D * d.n * d.n},
+                                   {(void**)&h->s_K, D * d.nu * d.n}, {(void**)&h->s_P, D * d.n * d.n}, {(void**)&h->s_st, sizeof(int32_t)}}))
+    return 1;
+  auto rows = [&](int bit) { return (shared_mask & bit) ? (size_t)1 : (size_t)B; };
+  // (a null host pointer: an array this kind of design does not read, or an output the caller left out)
+  auto up = [&](void* dst, const void* src, size_t bytes) { return src ? h->h2d(dst, src, bytes) : 0; };
+  auto down = [&](void* dst, const void* src, size_t bytes) { return dst ? h->d2h(dst, src, bytes) : 0; };
+  if (up(h->s_A, A, D * B * d.nx * d.nx) || up(h->s_B, Bm, D * B * d.nx * d.nu) || up(h->s_x, x, D * B * d.nx) || up(h->s_u, u, D * B * d.nu) ||
+      up(h->s_tvp, tvp, D * rows(8) * d.ntvp) || up(h->s_p, p, D * rows(16) * d.np) || up(h->s_Q, Q, D * rows(1) * d.n * d.n) ||
+      up(h->s_R, R, D * rows(2) * d.nu * d.nu) || up(h->s_Pf, Pf, D * rows(4) * d.n * d.n))
+    return 1;
+  if (dompc_lqr_design_batch_device(h, B, (A || d.has_model) ? h->s_A : nullptr, (Bm || d.has_model) ? h->s_B : nullptr, x ? h->s_x : nullptr,
+                                    u ? h->s_u : nullptr, tvp ? h->s_tvp : nullptr, p ? h->s_p : nullptr, Q ? h->s_Q : nullptr,
+                                    R ? h->s_R : nullptr, Pf ? h->s_Pf : nullptr, shared_mask, h->s_K, h->s_P, h->s_st, h->stream_ptr()))
+    return 1;
+  if (down(K_out, h->s_K, D * B * d.nu * d.n) || down(P_out, h->s_P, D * B * d.n * d.n) ||
+      (d.has_model && (down(A_out, h->s_A, D * B * d.nx * d.nx) || down(B_out, h->s_B, D * B * d.nx * d.nu))) ||
+      down(status, h->s_st, sizeof(int32_t) * (size_t)B))
+    return 1;
+  return h->sync();
+}

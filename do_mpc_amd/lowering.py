@@ -529,3 +529,59 @@ def lower_ekf(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discrete
     text = "\n".join(hdr) + "\n" + "\n".join(parts)
     digest = hashlib.sha256(text.encode()).hexdigest()[:16]
     return text + f"\n#define EKF_MODEL_HASH \"{digest}\"\n"
+
+
+def lower_lqr(*, nx, nu, rate, x_sym=None, u_sym=(), tvp_sym=(), p_sym=(), w_sym=(), v_sym=(), z_sym=(), rhs=None, discrete=True,
+              name="lqr") -> str:
+    """Header for the batched LQR design (csrc/dompc_lqr.hip): the sizes LQR_NX, LQR_NU and the design size LQR_N (nx, or nx + nu in
+    inputRatePenalization mode, /root/reference/do_mpc/controller/_lqr.py:219-226) and - with a model (`rhs` given) - `lqr_lin`:
+    the structural non-zeros of d rhs / d x and d rhs / d u (row-major; tables LQR_A_NZ / LQR_B_NZ) at (x, u, tvp, p), in PHYSICAL
+    units with the noise symbols zero, like lower_ekf.  A continuous model is discretised by zero-order hold inside the kernel."""
+    n = nx + nu if rate else nx
+    has_model = rhs is not None
+    if len(z_sym):
+        raise NotImplementedError("structured HIP backend: an LQR design for a model with algebraic states "
+                                  "(the reference asserts the same: 'Linearization around steady state is not supported for DAEs')")
+    if n > 16 or nu > 16:
+        raise NotImplementedError(f"structured HIP backend: an LQR design of size N > 16 or with more than 16 inputs (this design: "
+                                  f"n_x = {nx}, n_u = {nu}, N = {n}; the kernel maps one design to a row of 16 lanes)")
+    if has_model and not discrete and nx + nu > 16:
+        raise NotImplementedError(f"structured HIP backend: the zero-order hold of an LQR design with n_x + n_u > 16 (this model: "
+                                  f"n_x = {nx}, n_u = {nu}; the block [[A, B], [0, 0]] has to fit a row of 16 lanes)")
+    parts, tables = [], []
+    if has_model:
+        assert len(x_sym) == nx and len(u_sym) == nu and len(rhs) == nx
+        binds: Dict[int, str] = {}
+        for cname, syms in (("x", x_sym), ("u", u_sym), ("tvp", tvp_sym), ("p", p_sym)):
+            for i, s in enumerate(syms):
+                binds[s.idx] = f"{cname}[{i}]"
+        A = sym.forward_jacobian(list(rhs), list(x_sym))
+        Bm = sym.forward_jacobian(list(rhs), list(u_sym)) if nu else [[] for _ in range(nx)]
+        if sym.depends_on([e for Mx in (A, Bm) for row in Mx for e in row], list(w_sym)):
+            raise NotImplementedError("structured HIP backend: an LQR design whose linearisation depends on _w (process noise)")
+        zero = {s.idx: sym.ZERO for s in list(w_sym) + list(v_sym)}
+        flat = sym.substitute_nodes([e for Mx in (A, Bm) for row in Mx for e in row], zero)
+        free = [s for s in sym.free_symbols(flat) if s.idx not in binds]
+        if free:
+            raise Exception(f"the linearisation depends on symbols outside (_x,_u,_tvp,_p,_w,_v): {free}")
+        A = [flat[i * nx:(i + 1) * nx] for i in range(nx)]
+        Bm = [flat[nx * nx + i * nu:nx * nx + (i + 1) * nu] for i in range(nx)]
+        nz = lambda e: not (e.op == "const" and e.val == 0.0)      # noqa: E731
+        outs = [(f"A[{i * nx + j}]", A[i][j]) for i in range(nx) for j in range(nx) if nz(A[i][j])]
+        outs += [(f"B[{i * nu + j}]", Bm[i][j]) for i in range(nx) for j in range(nu) if nz(Bm[i][j])]
+        body = sym.emit_c(outs, binds, indent="  ")
+        parts.append(f"DOMPC_FN void lqr_lin(const double* x, const double* u, const double* tvp, const double* p, double* A, double* B) {{\n{body}\n}}\n")
+
+        def table(tname, Mx, cols):
+            vals = [1 if nz(Mx[i][j]) else 0 for i in range(nx) for j in range(cols)] or [0]
+            return f"static constexpr int {tname}[{len(vals)}] = {{{', '.join(str(v) for v in vals)}}};"
+        tables = ["// structure of d rhs / d x (NX x NX) and d rhs / d u (NX x NU), row-major: 1 = written by lqr_lin, 0 = zero for every argument",
+                  table("LQR_A_NZ", A, nx), table("LQR_B_NZ", Bm, nu)]
+    hdr = ["// GENERATED by do_mpc_amd/lowering.py:lower_lqr - do not edit.", "#pragma once", "#include <math.h>",
+           f"#define LQR_MODEL_NAME \"{name}\"",
+           f"#define LQR_NX {nx}", f"#define LQR_NU {nu}", f"#define LQR_N {n}", f"#define LQR_RATE {1 if rate else 0}",
+           f"#define LQR_HAS_MODEL {1 if has_model else 0}", f"#define LQR_DISCRETE {1 if (discrete or not has_model) else 0}",
+           f"#define LQR_NP {len(p_sym) if has_model else 0}", f"#define LQR_NTVP {len(tvp_sym) if has_model else 0}", *tables, ""]
+    text = "\n".join(hdr) + "\n" + "\n".join(parts)
+    digest = hashlib.sha256(text.encode()).hexdigest()[:16]
+    return text + f"\n#define LQR_MODEL_HASH \"{digest}\"\n"

@@ -331,6 +331,37 @@ int dompc_ekf_step_batch_device(dompc_ekf* h, int32_t B, double* x, double* P, c
                                 const double* tvp, const double* p, const double* Q, const double* R, int32_t shared_mask,
                                 int32_t* status, void* stream);
 
+/* ---- batched LQR design (csrc/dompc_lqr.hip): what do_mpc.controller.LQR.setup computes - the discrete Riccati solution and the gain
+ * K = -(B'PB + R)^-1 B'PA - for B designs per launch, on an infinite horizon (structure-preserving doubling iteration) or over
+ * n_horizon passes of the backward recursion (the K of the LAST pass, like the reference).  A code object WITHOUT a model reads the
+ * discrete pairs A [B][nx][nx], B [B][nx][nu]; one WITH a model linearises the model at (x, u, tvp, p), discretises a continuous one
+ * by zero-order hold over t_step and writes the discrete pairs.  rate != 0: inputRatePenalization mode, design size n = nx + nu with
+ * A~ = [[A, B], [0, I]], B~ = [[B], [I]]; otherwise n = nx.  n <= 16, nu <= 16.  Q [n][n], R [nu][nu], Pf [n][n] (terminal weight, finite
+ * horizon only) are in DESIGN size, per design or - with their bit of shared_mask set (bit 0/1/2/3/4 = Q/R/Pf/tvp/p) - ONE shared.
+ * status[b]: bit 0 = the doubling did not converge within max_iter; bit 1 = a singular or non-finite block, K = 0 and P = Q are
+ * returned, never NaN; iterations / passes = status[b] >> 8. */
+typedef struct dompc_lqr dompc_lqr;
+typedef struct dompc_lqr_desc {
+  int32_t nx, nu, n, rate, has_model, discrete, np, ntvp;
+  const char* code_object_path;      /* gfx950 code object built from the lowered design                        */
+  const char* model_hash;            /* LQR_MODEL_HASH of the header the code object was built from            */
+  int32_t device;
+  int32_t n_horizon;                 /* 0: infinite horizon                                                     */
+  int32_t max_iter;                  /* doubling steps; 0 = 50                                                  */
+  double t_step, tol;                /* tol: relative change of H that ends the doubling; 0 = 1e-13             */
+} dompc_lqr_desc;
+int  dompc_lqr_create(const dompc_lqr_desc* desc, dompc_lqr** out);
+void dompc_lqr_destroy(dompc_lqr* h);
+const char* dompc_lqr_last_error(const dompc_lqr* h);         /* h may be NULL: error of the last failed create */
+/* host buffers; arrays the design does not read and outputs that are not wanted (A_out, B_out, status) may be NULL */
+int dompc_lqr_design_batch(dompc_lqr* h, int32_t B, const double* A, const double* Bm, const double* x, const double* u,
+                           const double* tvp, const double* p, const double* Q, const double* R, const double* Pf,
+                           int32_t shared_mask, double* K_out, double* P_out, double* A_out, double* B_out, int32_t* status);
+/* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*); with a model A / Bm are outputs and may be NULL */
+int dompc_lqr_design_batch_device(dompc_lqr* h, int32_t B, double* A, double* Bm, const double* x, const double* u,
+                                  const double* tvp, const double* p, const double* Q, const double* R, const double* Pf,
+                                  int32_t shared_mask, double* K, double* P, int32_t* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,7 +14,7 @@ Output: tests/golden/<case>.npz  (small, committed), and tests/golden/sampling_t
 sampling tool chain produces for examples/tools/sampling/regular/test_fun/sampling_test.py
 (results/res_sampling_test_test_fun.pkl, compared for equality by testing/test_sampling_tools.py:55-67; plain
 dicts of floats / ints / strings, written with repr-exact floats).
-Run:    python tools/extract_golden.py
+Run:    python tools/extract_golden.py [case ...]      (cases named: only their .npz files are written)
 """
 import io
 import os
@@ -35,6 +35,8 @@ CASES = {
     "triple_tank": "results_triple_tank_ekf.pkl",
     "oscillating_masses_dae": "results_oscillatingMasses_dae.pkl",      # DAE models (`_z`): discrete, and
     "dip": "results_dip.pkl",                                           # double inverted pendulum (collocation, nl_cons, tvp)
+    "cstr_lqr": "results_CSTR_LQR.pkl",                                 # linear quadratic regulator: simulator records only
+    "oscillating_masses_lqr": "results_oscillatingMasses_LQR.pkl",
 }
 
 
@@ -66,7 +68,13 @@ def _state(obj):
 
 def main():
     os.makedirs(OUT, exist_ok=True)
+    only = sys.argv[1:]
+    unknown = [c for c in only if c not in CASES]
+    if unknown:
+        raise SystemExit(f"unknown cases {unknown}; known: {sorted(CASES)}")
     for case, fn in CASES.items():
+        if only and case not in only:
+            continue
         with open(os.path.join(REF, fn), "rb") as f:
             res = _Unpickler(io.BytesIO(f.read())).load()
         out = {}
@@ -87,6 +95,8 @@ def main():
         path = os.path.join(OUT, case + ".npz")
         np.savez_compressed(path, **out)
         print(case, "->", path, {k: v.shape for k, v in out.items() if v.ndim > 0})
+    if only:
+        return
     import json
     with open(os.path.join(REF, "res_sampling_test_test_fun.pkl"), "rb") as f:
         tab = pickle.load(f)
