@@ -36,10 +36,8 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-#ifndef DOMPC_HOST_EMU
-#include <utility>
-#endif
 #include "dompc_kargs.h"
+#include "dompc_lanes.h"        // (in front of namespace dompc: dompc_quad.h takes its cross-lane primitives from it)
 
 namespace dompc {
 

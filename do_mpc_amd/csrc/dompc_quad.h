@@ -23,32 +23,15 @@
 //     they are (industrial_poly: 25 of 91 packed entries per point).
 //   * condensing in the same layout: lane c owns column c of [W | w0 | -], T = (H_p + Sigma_p) Z_p is lane-local, Z_p' T takes the rows of
 //     Z_p from a staged copy in LDS (group-uniform reads, no vector-ALU slots).
-// Measured effect: DESIGN.md section 4 / profiles/r06_*.
+// Measured effect: DESIGN.md section 4 / profiles/r06_*.  The cross-lane primitives and their rules: dompc_lanes.h, DESIGN.md section 4k.
 #if !defined(DOMPC_HOST_EMU) && DOMPC_DEG >= 1 && DOMPC_M >= 1 && DOMPC_NI == 1 && DOMPC_NX + DOMPC_NU + 2 <= 16 && DOMPC_DEG * DOMPC_DEG * DOMPC_NX <= 64      // (array sizes and lane numbers below; the rest of the conditions: QUAD_EDGE, dompc_edge.h)
 
-extern "C" __device__ double dompc_dpp_f64(double old, double src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) __asm("llvm.amdgcn.update.dpp.f64");
-// value of `v` in lane L of this lane's row of 16 lanes (v_mov_b64_dpp row_newbcast:L)
-template <int L>
-__device__ inline double rbc(double v) {
-  static_assert(L >= 0 && L < 16, "lane inside a row of 16");
-  return dompc_dpp_f64(0.0, v, 0x150 + L, 0xf, 0xf, true);
-}
-// the value is computed HERE (an empty asm the optimiser cannot look through): without it the IR-level sinking pass moves whole chains of
-// arithmetic next to their first use, hundreds of instructions later, and keeps their operands alive (in scratch) in between
-__device__ inline void pin(double& v) { asm volatile("" : "+v"(v)); }
-__device__ inline void pin(int& v) { asm volatile("" : "+v"(v)); }
-// d += (value of `src` in lane L of the row of 16) * mul in ONE instruction: v_fmac_f64_dpp with the broadcast as the DPP operand.  The compiler
-// has the instruction but never folds a v_mov_b64_dpp into it, and an inline-asm DPP read is outside its hazard recogniser: the caller
-// guarantees that `src` was not written by one of the two preceding vector instructions (gfx9 DPP hazard: two wait states).
-template <int L>
-__device__ inline void fmac_rbc(double& d, const double& src, double mul) {
-  asm volatile("v_fmac_f64_dpp %0, %1, %2 row_newbcast:%3 row_mask:0xf bank_mask:0xf" : "+v"(d) : "v"(src), "v"(mul), "n"(L));
-}
-template <class F, int... I>
-__device__ inline void sfor_(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-// f(integral_constant<int, i>) for i = 0 .. N-1: loops whose index has to be a constant expression
-template <int N, class F>
-__device__ inline void sfor(F&& f) { sfor_(f, std::make_integer_sequence<int, (N > 0 ? N : 0)>{}); }
+// the lane-row layer (dompc_lanes.h; its rule 2 - no DPP source written by one of the two preceding vector instructions - is kept by
+// hand in the eliminations below: s_nop 1 in front of the updates of a pivot, the slot of the pivot column last)
+using dompc_lanes::rbc;
+using dompc_lanes::pin;
+using dompc_lanes::fmac_rbc;
+using dompc_lanes::sfor;
 
 // where a dense entry of the model-output record lives: kind 0 structural zero, 1 model constant (index into the constant table),
 // 2 variable (offset inside the compact record of the edge)

@@ -55,3 +55,9 @@ def ekf_hostemu_library(header_text: str, model_hash: str, out_dir: str = OUT, f
     """TEST-ONLY: filter kernel + runtime compiled for the host (g++); lives in tests/_hostemu, never loaded by the product."""
     return _hostemu("dompc_ekf_hostemu", "dompc_ekf_runtime.cpp", "dompc_ekf.hip", "DOMPC_EKF_HEADER", "ekf_gen", [], "filter ",
                     header_text, model_hash, out_dir, force)
+
+
+def lqr_hostemu_library(header_text: str, model_hash: str, out_dir: str = OUT, force: bool = False) -> str:
+    """TEST-ONLY: design kernel + runtime compiled for the host (g++); lives in tests/_hostemu, never loaded by the product."""
+    return _hostemu("dompc_lqr_hostemu", "dompc_lqr_runtime.cpp", "dompc_lqr.hip", "DOMPC_LQR_HEADER", "lqr_gen", [], "LQR design ",
+                    header_text, model_hash, out_dir, force)

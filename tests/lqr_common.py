@@ -13,15 +13,9 @@ from do_mpc_amd.examples import CASES
 from do_mpc_amd.lqr import LQR
 from do_mpc_amd.model import LinearModel
 from ekf_common import relerr  # noqa: F401  (the measure of the stored-run and gain comparisons)
-from hostemu_build import OUT, _hostemu
+from hostemu_build import OUT, lqr_hostemu_library
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def lqr_hostemu_library(header_text: str, model_hash: str, out_dir: str = OUT, force: bool = False) -> str:
-    """TEST-ONLY: design kernel + runtime compiled for the host (g++); lives in tests/_hostemu, never loaded by the product."""
-    return _hostemu("dompc_lqr_hostemu", "dompc_lqr_runtime.cpp", "dompc_lqr.hip", "DOMPC_LQR_HEADER", "lqr_gen", [], "LQR design ",
-                    header_text, model_hash, out_dir, force)
 
 
 def setup_lqr(lqr, hostemu):

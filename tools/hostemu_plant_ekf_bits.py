@@ -1,5 +1,5 @@
-"""Bit-for-bit comparison of two source trees on the TEST-ONLY host emulation of the plant integrator and of the extended Kalman
-filter - the counterpart of tools/hostemu_bits.py (solver) for the other two runtimes.
+"""Bit-for-bit comparison of two source trees on the TEST-ONLY host emulation of the plant integrator, of the extended Kalman
+filter and of the LQR design - the counterpart of tools/hostemu_bits.py (solver) for the other three runtimes.
 
     python tools/hostemu_plant_ekf_bits.py record out.npz      in each of the two checkouts, then
     python tools/hostemu_plant_ekf_bits.py compare a.npz b.npz
@@ -7,7 +7,9 @@ filter - the counterpart of tools/hostemu_bits.py (solver) for the other two run
 `record`: seeded batches through Simulator.make_step_batch (one ODE plant, one DAE plant; two consecutive calls with carry_z) and
 EKF.step_batch (one discrete, one continuous model; shared and per-filter Q / R), each with B = 9 and with a batch that grows after a
 smaller one (B = 3, 9, 3: the staging buffers are regrown and then reused); x, y / P, status and step counts of every call are stored.
-`compare` asks np.array_equal of every stored array.
+LQR: a standard design and a finite-horizon one (n_horizon passes) through gains_batch, a design in inputRatePenalization mode
+through gains_at on the CSTR (Jacobians, zero-order hold), with the same batches; K, P, the discrete pair, status and step counts are
+stored.  `compare` asks np.array_equal of every stored array.
 """
 import os
 import sys
@@ -58,8 +60,36 @@ def record(out):
                 r = ekf.step_batch(X[:B], Pc[:B], Y[:B], U[:B], Qs if shared else Qs[:B], Rs if shared else Rs[:B])
                 store(f"filter {name} {tag} growth call {i} B={B}", r, "P")
         print(f"filter {name}: recorded", flush=True)
+    record_lqr(flat)
     np.savez_compressed(out, **flat)
     print("stored", len(flat), "arrays in", out)
+
+
+def record_lqr(flat):
+    import lqr_common as lc
+    rng = np.random.default_rng(11)
+    n, nu = 6, 2
+    A = np.empty((9, n, n)); Bm = np.empty((9, n, nu))
+    for b in range(9):
+        A[b], Bm[b] = lc.twin_zoh(rng.standard_normal((n, n)) / np.sqrt(n), rng.standard_normal((n, nu)), float(rng.uniform(0.1, 0.5)))
+    Q = np.diag(10.0 ** rng.uniform(-1, 1, n))
+    R = np.diag(10.0 ** rng.uniform(-1, 1, nu))
+    ex, plant, _ = lc.example("cstr_lqr", True, n_horizon=None)
+    X, U = lc.family_b_points(ex, 9)
+    designs = {                                                 # label -> (fresh controller, call on the first B members)
+        "standard": (lambda: lc.model_free_lqr(n, nu, True), lambda q, B: q.gains_batch(A[:B], Bm[:B], Q, R)),
+        "n_horizon=7": (lambda: lc.model_free_lqr(n, nu, True, n_horizon=7), lambda q, B: q.gains_batch(A[:B], Bm[:B], Q, R, P=Q)),
+        "rate gains_at": (lambda: lc.example("cstr_lqr", True, n_horizon=None)[2], lambda q, B: q.gains_at(plant, X[:B], U[:B])),
+    }
+    for label, (fresh, call) in designs.items():
+        def store(tag, r, B):
+            for k, v in (("K", r["K"]), ("P", r["P"]), ("A", r.get("A", A[:B])), ("B", r.get("B", Bm[:B])), ("status", r["status"]), ("iters", r["iters"])):
+                flat[f"design {label} {tag}/{k}"] = np.asarray(v).copy()
+        store("B=9", call(fresh(), 9), 9)
+        q = fresh()                                             # a fresh handle: B = 3, then 9, then 3
+        for i, B in enumerate((3, 9, 3)):
+            store(f"growth call {i} B={B}", call(q, B), B)
+        print(f"design {label}: recorded", flush=True)
 
 
 def compare(a, b):
@@ -68,8 +98,9 @@ def compare(a, b):
     bad = [k for k in sorted(A.files) if not (A[k].shape == B[k].shape and np.array_equal(A[k], B[k], equal_nan=True))]
     for k in bad:
         print("DIFFERENT", k)
-    ok = sum(int((A[k] == 0).all()) for k in A.files if k.endswith("/status"))
-    print(f"{len(A.files)} arrays of {len(A.files) // 4} calls compared, {len(bad)} different; calls with status 0 in every row: {ok}")
+    ok = [sum(int((Z[k] == 0).all()) for k in Z.files if k.endswith("/status")) for Z in (A, B)]
+    print(f"{len(A.files)} arrays of {sum(k.endswith('/status') for k in A.files)} calls compared, {len(bad)} different; "
+          f"calls with status 0 in every row: {ok[0]} / {ok[1]}")
     return 1 if bad else 0
 
 
