@@ -105,7 +105,8 @@ def runtime_library(force: bool = False) -> str:
             return out
         cmd = [_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
                os.path.join(CSRC, "dompc_runtime.cpp"), os.path.join(CSRC, "dompc_plant_runtime.cpp"),
-               os.path.join(CSRC, "dompc_ekf_runtime.cpp"), os.path.join(CSRC, "dompc_lqr_runtime.cpp"), "-ldl"]
+               os.path.join(CSRC, "dompc_ekf_runtime.cpp"), os.path.join(CSRC, "dompc_lqr_runtime.cpp"),
+               os.path.join(CSRC, "dompc_ampc_runtime.cpp"), "-ldl"]
         _compile_to(cmd, out, "building libdompc_ipm.so")
         _write_atomic(stamp, dig)
     return out
@@ -228,3 +229,9 @@ def lqr_code_object(header_text: str, model_hash: str, force: bool = False, rema
     """gfx950 code object of the batched LQR design (csrc/dompc_lqr.hip) for one lowered design (sizes, mode and - for gains_at - the
     model's Jacobians).  remarks=True: as ekf_code_object (profiles/lqr_resource_usage.txt)."""
     return _kernel_code_object("lqr", "dompc_lqr.hip", "DOMPC_LQR_HEADER", "lqr_gen.h", "LQR design", header_text, model_hash, force, remarks)
+
+
+def ampc_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
+    """gfx950 code object of the batched approximate-MPC step (csrc/dompc_ampc.hip) for one lowered network shape (sizes, activations,
+    scaling; the weights are runtime data).  remarks=True: as ekf_code_object (profiles/ampc_resource_usage.txt)."""
+    return _kernel_code_object("ampc", "dompc_ampc.hip", "DOMPC_AMPC_HEADER", "ampc_gen.h", "network", header_text, model_hash, force, remarks)

@@ -93,8 +93,12 @@ def install(force: bool = False):
         m_data = types.ModuleType("do_mpc.data")
         m_data.save_results, m_data.load_results, m_data.MPCData = _data.save_results, _data.load_results, _data.MPCData
         dm.data = m_data
-        m_ampc = types.ModuleType("do_mpc.approximateMPC")      # (the data-generation half; the torch model is out of scope)
+        from . import ampc as _ampc      # (imports torch: only when the stand-ins are installed)
+        m_ampc = types.ModuleType("do_mpc.approximateMPC")      # sampler (batched solves) + network controller and its trainer
         m_ampc.AMPCSampler = sampling.AMPCSampler
+        m_ampc.ApproxMPC, m_ampc.Trainer, m_ampc.FeedforwardNN = _ampc.ApproxMPC, _ampc.Trainer, _ampc.FeedforwardNN
+        m_ampc.ApproximateMPCSettings, m_ampc.TrainerSettings = _ampc.ApproximateMPCSettings, _ampc.TrainerSettings
+        m_ampc.TrainerSchedulerSettings, m_ampc.SamplerSettings = _ampc.TrainerSchedulerSettings, sampling.SamplerSettings
         dm.approximateMPC = m_ampc
         dm.__version__ = "5.1.1+dompc_amd"
         sys.modules["do_mpc"] = dm

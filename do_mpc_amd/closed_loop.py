@@ -463,3 +463,73 @@ class BatchClosedLoopLQR:
             st.append(r["plant_status"])
         return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, self.B, self.sim.model.n_u)),
                 "plant_status": np.stack(st) if st else np.zeros((0, self.B), dtype=np.int32)}
+
+
+class BatchClosedLoopAMPC:
+    """B closed loops approximate MPC -> plant advancing together with X and U resident in device memory (float64): per control step
+    TWO launches, the network kernel (ApproxMPC.make_step_batch_device) and ONE batched plant step.  The per-sample loop of the
+    reference is `u0 = approx_mpc.make_step(x0)`, `x0 = simulator.make_step(u0)`
+    (/root/reference/examples/CSTR_approximate_mpc/main.py:164-170).  State feedback: the plant's measurement must be its state.
+    X0: [B][nx]; U_prev0: [B][nu], the inputs before the first step (default: ampc.u0 for every loop; read only when the controller
+    has an rterm).  device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests)."""
+
+    def __init__(self, ampc, simulator, X0, U_prev0=None, device=0, clip_to_bounds=True):
+        import torch
+        self.torch = torch
+        self.ampc, self.sim, self.clip = ampc, simulator, bool(clip_to_bounds)
+        assert ampc.flags["setup"] == True, "MPC was not setup yet. Please call ApproxMPC.setup()."      # noqa: E712
+        m = simulator.model
+        mc = ampc.mpc.model
+        assert (m.n_x, m.n_u) == (mc.n_x, mc.n_u), "controller and plant must share states and inputs"
+        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
+        X0 = np.asarray(X0, dtype=float).reshape(-1, m.n_x)
+        self.B = B = X0.shape[0]
+        dev = self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
+        t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)      # noqa: E731  (a copy, also on the host)
+        self.X = t(X0)
+        self.Xn = torch.empty_like(self.X)
+        if U_prev0 is None:
+            u0 = ampc.u0
+            U_prev0 = np.tile(np.asarray(u0.master if hasattr(u0, "master") else u0, dtype=float).reshape(1, m.n_u), (B, 1))
+        self.U = t(np.asarray(U_prev0, float).reshape(B, m.n_u))
+        self.Un = torch.empty_like(self.U)
+        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
+        ts = float(simulator._t0[0])
+        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
+        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
+        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
+        self.k = 0
+
+    def step(self) -> dict:
+        """one control step of all B loops; returns the inputs applied, the new states and the plant status"""
+        torch, m = self.torch, self.sim.model
+        cuda = self.dev.type == "cuda"
+        if self.k > 0 and (m.n_p or m.n_tvp):      # the plant's parameters at the current loop time
+            ts = self.t_sim0 + self.k * self.dt_sim
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
+            if m.n_p:
+                self.p_plant.copy_(up(self.sim.p_fun(ts).master))
+            if m.n_tvp:
+                self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
+        stream = torch.cuda.current_stream().cuda_stream if cuda else 0
+        self.ampc.make_step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr() if self.ampc.rterm else 0, self.Un.data_ptr(),
+                                         stream=stream, clip_to_bounds=self.clip)
+        self.U, self.Un = self.Un, self.U
+        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
+                                   self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16, stream=stream)
+        self.X, self.Xn = self.Xn, self.X
+        self.k += 1
+        if cuda:
+            torch.cuda.synchronize()
+        return {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1)}
+
+    def run(self, n: int) -> dict:
+        """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step"""
+        xs, us, st = [self.X.cpu().numpy().copy()], [], []
+        for _ in range(int(n)):
+            r = self.step()
+            xs.append(r["x"].copy())
+            us.append(r["u0"].copy())
+            st.append(r["plant_status"])
+        return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, self.B, self.sim.model.n_u)),
+                "plant_status": np.stack(st) if st else np.zeros((0, self.B), dtype=np.int32)}

@@ -1,0 +1,129 @@
+// dompc_ampc_runtime.cpp - host side of the batched approximate-MPC step behind the C ABI of include/dompc_ipm.h (dompc_ampc_*).
+// Generic: sizes come from the per-network code object (dompc_ampc_info_kernel); weights and bounds are data of the handle.
+// Build flavours as dompc_lqr_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU together with
+// dompc_ampc.hip compiled as C++ (tests/_hostemu; never shipped).
+#include "../../include/dompc_ipm.h"
+#include "dompc_host.h"
+#include "dompc_ampc_args.h"
+
+#ifdef DOMPC_HOST_EMU
+extern "C" void dompc_ampc_hostemu_info(int64_t* out, char* hash);
+extern "C" void dompc_ampc_hostemu_run(const dompc_ampck::Args* A);
+#endif
+
+static thread_local std::string g_ampc_create_error;
+
+struct dompc_ampc : dompc_host::Context {
+  dompc_ampc_desc d;
+  int64_t packed = 0;                    // floats of the packed weights the code object reads
+  bool have_weights = false;
+  float* w = nullptr;
+  double* par = nullptr;
+  int32_t cap = 0;
+  double *s_x = nullptr, *s_up = nullptr, *s_u = nullptr;
+#ifndef DOMPC_HOST_EMU
+  hipModule_t module = nullptr;
+  hipFunction_t fn = nullptr, fn_info = nullptr;
+#endif
+};
+
+extern "C" const char* dompc_ampc_last_error(const dompc_ampc* h) { return h ? h->error.c_str() : g_ampc_create_error.c_str(); }
+
+extern "C" void dompc_ampc_destroy(dompc_ampc* h) {
+  if (!h) return;
+  h->close();
+  delete h;
+}
+
+extern "C" int dompc_ampc_create(const dompc_ampc_desc* desc, dompc_ampc** out) {
+  if (!desc || !out) { g_ampc_create_error = "null argument"; return 1; }
+  dompc_ampc* h = new dompc_ampc();
+  h->d = *desc;
+  h->device = desc->device;
+  auto fail = [&]() { g_ampc_create_error = h->error; dompc_ampc_destroy(h); *out = nullptr; return 1; };
+  if (desc->n_in <= 0 || desc->n_out <= 0) { h->error = "network without inputs or without outputs"; return fail(); }
+  if (desc->nx <= 0 || desc->nx > desc->n_in) { h->error = "nx must be between 1 and n_in"; return fail(); }
+  int64_t info[16] = {0};
+  char hash[64] = {0};
+#ifndef DOMPC_HOST_EMU
+  if (h->open_device("approximate MPC") ||
+      h->load_module(desc->code_object_path, &h->module, {{"dompc_ampc_kernel", &h->fn}, {"dompc_ampc_info_kernel", &h->fn_info}},
+                     "code object lacks the network kernels") ||
+      h->query_info(h->fn_info, "dompc_ampc_info_kernel", info, hash))
+    return fail();
+#else
+  dompc_ampc_hostemu_info(info, hash);
+#endif
+  const int64_t want[7] = {desc->n_in, desc->n_out, desc->n_hidden_layers, desc->n_neurons, desc->act, desc->out_act, desc->scaling ? 1 : 0};
+  if (h->check_info("network ", info, want, 7, 7, sizeof(dompc_ampck::Args), hash, desc->model_hash)) return fail();
+  h->packed = info[8];
+  if (h->packed <= 0) { h->error = "network code object reports no weights"; return fail(); }
+  if (h->alloc((void**)&h->w, sizeof(float) * (size_t)h->packed) ||
+      h->alloc((void**)&h->par, sizeof(double) * (size_t)(2 * desc->n_in + 3 * desc->n_out)))
+    return fail();
+  h->d.code_object_path = nullptr; h->d.model_hash = nullptr;
+  *out = h;
+  return 0;
+}
+
+extern "C" int64_t dompc_ampc_packed_size(const dompc_ampc* h) { return h ? h->packed : 0; }
+
+extern "C" int dompc_ampc_set_weights(dompc_ampc* h, const float* packed, int64_t n, const double* lb_in, const double* ub_in,
+                                      const double* lbu, const double* ubu) {
+  if (!h) return 1;
+  if (!packed || !lb_in || !ub_in || !lbu || !ubu) { h->error = "null pointer"; return 1; }
+  if (n != h->packed) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "packed weights have %lld floats, the code object reads %lld", (long long)n, (long long)h->packed);
+    h->error = buf;
+    return 1;
+  }
+  const int ni = h->d.n_in, no = h->d.n_out;
+  std::vector<double> par((size_t)(2 * ni + 3 * no));
+  for (int i = 0; i < ni; ++i) { par[i] = lb_in[i]; par[ni + i] = ub_in[i] - lb_in[i]; }
+  for (int i = 0; i < no; ++i) { par[2 * ni + i] = lbu[i]; par[2 * ni + no + i] = ubu[i]; par[2 * ni + 2 * no + i] = ubu[i] - lbu[i]; }
+  if (h->set_device()) return 1;
+#ifndef DOMPC_HOST_EMU
+  HIPCHK(h, hipDeviceSynchronize());     // no step that still reads the old weights is in flight on any stream
+#endif
+  if (h->h2d(h->w, packed, sizeof(float) * (size_t)n) || h->h2d(h->par, par.data(), sizeof(double) * par.size()) || h->sync()) return 1;
+  h->have_weights = true;
+  return 0;
+}
+
+extern "C" int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, int32_t clip,
+                                            void* stream) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  const dompc_ampc_desc& d = h->d;
+  if (!h->have_weights) { h->error = "no weights: call dompc_ampc_set_weights first"; return 1; }
+  if (!x || !u || (d.n_in > d.nx && !u_prev)) { h->error = "null pointer"; return 1; }
+  dompc_ampck::Args G;
+  memset(&G, 0, sizeof(G));
+  G.x = x; G.u_prev = u_prev; G.u = u; G.w = h->w; G.par = h->par;
+  G.batch = B; G.nx = d.nx; G.clip = clip ? 1 : 0;
+  if (h->set_device()) return 1;
+#ifndef DOMPC_HOST_EMU
+  // one wavefront per workgroup, 32 samples per wavefront
+  return h->launch(h->fn, (unsigned)(((int64_t)B + 31) / 32), 64, 0, (hipStream_t)stream, &G, sizeof(G));
+#else
+  (void)stream;
+  dompc_ampc_hostemu_run(&G);
+  return 0;
+#endif
+}
+
+extern "C" int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, int32_t clip) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  const dompc_ampc_desc& d = h->d;
+  const int nup = d.n_in - d.nx;
+  if (!x || !u_out || (nup > 0 && !u_prev)) { h->error = "null pointer"; return 1; }
+  if (h->set_device()) return 1;
+  const size_t D = sizeof(double);
+  if (h->grow_staging(&h->cap, B, {{(void**)&h->s_x, D * d.nx}, {(void**)&h->s_up, D * nup}, {(void**)&h->s_u, D * d.n_out}})) return 1;
+  if (h->h2d(h->s_x, x, D * B * d.nx) || (nup > 0 && h->h2d(h->s_up, u_prev, D * B * nup))) return 1;
+  if (dompc_ampc_step_batch_device(h, B, h->s_x, nup > 0 ? h->s_up : nullptr, h->s_u, clip, h->stream_ptr())) return 1;
+  if (h->d2h(u_out, h->s_u, D * B * d.n_out)) return 1;
+  return h->sync();
+}

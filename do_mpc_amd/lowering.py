@@ -585,3 +585,38 @@ def lower_lqr(*, nx, nu, rate, x_sym=None, u_sym=(), tvp_sym=(), p_sym=(), w_sym
     text = "\n".join(hdr) + "\n" + "\n".join(parts)
     digest = hashlib.sha256(text.encode()).hexdigest()[:16]
     return text + f"\n#define LQR_MODEL_HASH \"{digest}\"\n"
+
+
+AMPC_ACTIVATIONS = {"relu": 0, "tanh": 1, "leaky_relu": 2, "sigmoid": 3, "linear": 4}
+AMPC_LIMITS = {"n_in": 64, "n_out": 32, "n_neurons": 128, "n_hidden_layers": 8}
+
+
+def lower_ampc(n_in, n_out, n_hidden_layers, n_neurons, act_fn, output_act_fn, scaling) -> str:
+    """Header for the batched approximate-MPC step (csrc/dompc_ampc.hip): the SHAPE of the feed-forward network - sizes, activation
+    selectors, scaling on or off.  Weights, biases, shift, range and bounds are runtime data of the handle, not code: retraining
+    never rebuilds a code object.  With n_hidden_layers = 0 the network is ONE layer that ends in act_fn (the reference's layer rule):
+    output_act_fn is not used then, and the header says so.  Networks beyond AMPC_LIMITS (one wavefront holds 32 samples' activations of a layer in registers)
+    are refused by name."""
+    sizes = {"n_in": int(n_in), "n_out": int(n_out), "n_neurons": int(n_neurons), "n_hidden_layers": int(n_hidden_layers)}
+    for key, v in sizes.items():
+        lo = 0 if key == "n_hidden_layers" else 1
+        if not lo <= v <= AMPC_LIMITS[key]:
+            raise NotImplementedError(f"structured HIP backend: an approximate MPC network with {key} = {v} (the network kernel takes "
+                                      f"{lo} <= {key} <= {AMPC_LIMITS[key]})")
+    if act_fn not in AMPC_ACTIVATIONS or act_fn == "linear" or output_act_fn not in AMPC_ACTIVATIONS:
+        raise ValueError("Activation function not implemented.")
+    if sizes["n_hidden_layers"] == 0 and sizes["n_neurons"] != sizes["n_out"]:
+        # (the reference's layer rule: without a hidden layer the network is Linear(n_in, n_neurons) + act_fn alone)
+        raise ValueError(f"an approximate MPC network with n_hidden_layers = 0 is one layer of n_neurons outputs: n_neurons "
+                         f"({n_neurons}) must equal the number of inputs of the plant ({n_out})")
+    hdr = ["// GENERATED by do_mpc_amd/lowering.py:lower_ampc - do not edit.", "#pragma once",
+           f"#define AMPC_N_IN {sizes['n_in']}", f"#define AMPC_N_OUT {sizes['n_out']}", f"#define AMPC_N_HIDDEN {sizes['n_hidden_layers']}",
+           f"#define AMPC_N_NEURONS {sizes['n_neurons']}",
+           f"#define AMPC_ACT {AMPC_ACTIVATIONS[act_fn]}      // {act_fn}",
+           (f"#define AMPC_OUT_ACT {AMPC_ACTIVATIONS[act_fn]}      // {act_fn}: without a hidden layer the one layer ends in act_fn, "
+            f"output_act_fn ({output_act_fn}) is not used" if sizes["n_hidden_layers"] == 0 else
+            f"#define AMPC_OUT_ACT {AMPC_ACTIVATIONS[output_act_fn]}      // {output_act_fn}"),
+           f"#define AMPC_SCALING {1 if scaling else 0}", ""]
+    text = "\n".join(hdr)
+    digest = hashlib.sha256(text.encode()).hexdigest()[:16]
+    return text + f"\n#define AMPC_MODEL_HASH \"{digest}\"\n"

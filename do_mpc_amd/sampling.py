@@ -384,7 +384,7 @@ class DataHandler(_Settable):
 
 # ----------------------------------------------------------------------------------------------------------------------
 # The data-generation half of the reference's approximate-MPC module (`do_mpc.approximateMPC.AMPCSampler`,
-# /root/reference/do_mpc/approximateMPC/_ampc_sampler.py:41-526; its neural-network half is out of scope): same settings,
+# /root/reference/do_mpc/approximateMPC/_ampc_sampler.py:41-526; its neural-network half - ApproxMPC, Trainer - is ampc.py): same settings,
 # same files (`<data_dir>/<name>/sampling_plan_<name>.pkl`, `samples_<name>/sample_<id>.pkl`, `data_<name>_all.pkl`,
 # `data_<name>_opt.pkl`), but the plan is solved as batched launches instead of one `make_step` per row.
 from dataclasses import dataclass as _dataclass, field as _field

@@ -362,6 +362,34 @@ int dompc_lqr_design_batch_device(dompc_lqr* h, int32_t B, double* A, double* Bm
                                   const double* tvp, const double* p, const double* Q, const double* R, const double* Pf,
                                   int32_t shared_mask, double* K, double* P, int32_t* status, void* stream);
 
+/* ---- batched approximate MPC (csrc/dompc_ampc.hip): what do_mpc.approximateMPC.ApproxMPC.make_step computes - scale the input
+ * [x; u_prev] by its bounds box, evaluate a feed-forward network in float32, rescale the output to [lbu, ubu] and clip - for B
+ * samples per launch.  The code object is built for the network's SHAPE (n_in <= 64, n_out <= 32, n_hidden_layers <= 8 of
+ * n_neurons <= 128, activations: 0 relu, 1 tanh, 2 leaky_relu, 3 sigmoid, 4 linear (output only), scaling on or off); weights,
+ * biases and bounds are data of the handle and may be replaced at any time (dompc_ampc_set_weights), e.g. after every optimiser
+ * step.  x: [B][nx]; u_prev: [B][n_in - nx], NULL when n_in == nx; u: [B][n_out]; all float64. */
+typedef struct dompc_ampc dompc_ampc;
+typedef struct dompc_ampc_desc {
+  int32_t n_in, n_out, n_hidden_layers, n_neurons, act, out_act, scaling;
+  int32_t nx;                        /* leading entries of the network input that come from x; the others from u_prev */
+  const char* code_object_path;      /* gfx950 code object built from the lowered network shape                  */
+  const char* model_hash;            /* AMPC_MODEL_HASH of the header the code object was built from             */
+  int32_t device;
+} dompc_ampc_desc;
+int  dompc_ampc_create(const dompc_ampc_desc* desc, dompc_ampc** out);
+void dompc_ampc_destroy(dompc_ampc* h);
+const char* dompc_ampc_last_error(const dompc_ampc* h);       /* h may be NULL: error of the last failed create */
+int64_t dompc_ampc_packed_size(const dompc_ampc* h);          /* floats of the packed weights the code object reads */
+/* packed_f32: n floats in the operand order of the kernel (do_mpc_amd/ampc.py:pack_weights); lb_in / ub_in [n_in]:
+ * the box of the network input (shift = lb_in, range = ub_in - lb_in); lbu / ubu [n_out].  Host pointers; returns when the copy is done. */
+int dompc_ampc_set_weights(dompc_ampc* h, const float* packed_f32, int64_t n, const double* lb_in, const double* ub_in,
+                           const double* lbu, const double* ubu);
+/* host buffers */
+int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, int32_t clip_to_bounds);
+/* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*) */
+int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, int32_t clip_to_bounds,
+                                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif
