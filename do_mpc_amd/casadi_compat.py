@@ -16,7 +16,7 @@ from . import controller, differentiator, estimator, model, sampling, simulator,
 _CASADI_NAMES = [
     "SX", "DM", "vertcat", "horzcat", "vertsplit", "mtimes", "sum1", "sum2", "sumsqr", "dot", "exp", "log", "sqrt", "sin",
     "cos", "tan", "tanh", "sinh", "cosh", "asin", "acos", "atan", "atan2", "sign", "fabs", "fmin", "fmax", "jacobian",
-    "gradient", "hessian", "substitute", "Function",
+    "gradient", "hessian", "substitute", "Function", "inv",
 ]
 
 
@@ -61,7 +61,9 @@ def install(force: bool = False):
         tools = types.ModuleType("casadi.tools")
         tools.entry = structs.entry
         tools.indexf = differentiator.indexf
-        tools.__all__ = ["entry", "indexf"]
+        for n in ("vertcat", "substitute", "jacobian", "inv"):      # (what do_mpc/model/_dae2odeconversion.py reads from casadi.tools)
+            setattr(tools, n, getattr(sym, n))
+        tools.__all__ = ["entry", "indexf", "vertcat", "substitute", "jacobian", "inv"]
         cas.tools = tools
         sys.modules["casadi"] = cas
         sys.modules["casadi.tools"] = tools
@@ -72,6 +74,7 @@ def install(force: bool = False):
         m_model = types.ModuleType("do_mpc.model")
         m_model.Model = model.Model
         m_model.LinearModel, m_model.linearize = model.LinearModel, model.linearize
+        m_model.dae2odeconversion, m_model.linearize_dae = model.dae2odeconversion, model.linearize_dae
         m_ctrl = types.ModuleType("do_mpc.controller")
         m_ctrl.MPC = controller.MPC
         m_ctrl.MPCSettings = controller.MPCSettings

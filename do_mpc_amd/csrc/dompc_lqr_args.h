@@ -12,10 +12,17 @@ struct Args {
                                              // per design or shared (stride 0)
   double *K, *P;                             // out: gain [B][nu][n], Riccati solution / cost-to-go [B][n][n]
   int32_t* status;                           // [B] (may be null): bit 0 = the doubling iteration did not converge, bit 1 = singular or
-                                             // non-finite block (K = 0, P = Q are returned); iterations in status >> 8
+                                             // non-finite block (K = 0, P = Q are returned), bit 2 (models with algebraic states) =
+                                             // Newton on g = 0 did not converge, or g_z singular or not finite at the last iterate
+                                             // (K = 0, P = Q, A = B = 0); iterations in bits 8 .. 23, Newton passes in bits 24 .. 30
   int32_t batch, stride_q, stride_r, stride_pf, stride_tvp, stride_p;
   int32_t n_horizon;                         // 0: infinite horizon (doubling); > 0: passes of the backward recursion
   int32_t max_iter;
   double t_step, tol;
+  // models with algebraic states (LQR_NZ > 0): the index-1 reduction inside the design
+  const double* z;                           // [B][nz] guess of the algebraic states at the operating points
+  double* z_out;                             // [B][nz] (may be null): the consistent algebraic states (the last Newton iterate)
+  double z_tol;                              // Newton stops at max |g| <= z_tol ...
+  int32_t z_max_iter;                        // ... or after z_max_iter updates z <- z - g_z^-1 g (at most 127)
 };
 }  // namespace dompc_lqrk

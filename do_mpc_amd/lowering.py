@@ -531,15 +531,23 @@ def lower_ekf(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discrete
     return text + f"\n#define EKF_MODEL_HASH \"{digest}\"\n"
 
 
+LQR_MAX_NZ = 16          # algebraic states of a design: g_z is eliminated on one row of 16 lanes
+
+
 def lower_lqr(*, nx, nu, rate, x_sym=None, u_sym=(), tvp_sym=(), p_sym=(), w_sym=(), v_sym=(), z_sym=(), rhs=None, discrete=True,
-              name="lqr") -> str:
+              name="lqr", alg=None) -> str:
     """Header for the batched LQR design (csrc/dompc_lqr.hip): the sizes LQR_NX, LQR_NU and the design size LQR_N (nx, or nx + nu in
     inputRatePenalization mode, /root/reference/do_mpc/controller/_lqr.py:219-226) and - with a model (`rhs` given) - `lqr_lin`:
     the structural non-zeros of d rhs / d x and d rhs / d u (row-major; tables LQR_A_NZ / LQR_B_NZ) at (x, u, tvp, p), in PHYSICAL
-    units with the noise symbols zero, like lower_ekf.  A continuous model is discretised by zero-order hold inside the kernel."""
+    units with the noise symbols zero, like lower_ekf.  A continuous model is discretised by zero-order hold inside the kernel.
+    With `alg` (the algebraic equations g of an index-1 DAE model, next to `z_sym`) the header carries LQR_NZ, `lqr_lin_dae` (the
+    structural non-zeros of f_x f_u f_z g_x g_u g_z at (x, u, tvp, p, z); tables LQR_*_NZ) and `lqr_alg` (g and g_z alone: the Newton
+    passes); the kernel designs on the reduced system, so the size rules apply to n_x and n_u as they stand, and n_z <= 16.  Headers
+    of designs without algebraic states carry none of this (their text, and with it their hash, is what it was)."""
     n = nx + nu if rate else nx
     has_model = rhs is not None
-    if len(z_sym):
+    nzs = len(z_sym)
+    if nzs and alg is None:
         raise NotImplementedError("structured HIP backend: an LQR design for a model with algebraic states "
                                   "(the reference asserts the same: 'Linearization around steady state is not supported for DAEs')")
     if n > 16 or nu > 16:
@@ -548,8 +556,65 @@ def lower_lqr(*, nx, nu, rate, x_sym=None, u_sym=(), tvp_sym=(), p_sym=(), w_sym
     if has_model and not discrete and nx + nu > 16:
         raise NotImplementedError(f"structured HIP backend: the zero-order hold of an LQR design with n_x + n_u > 16 (this model: "
                                   f"n_x = {nx}, n_u = {nu}; the block [[A, B], [0, 0]] has to fit a row of 16 lanes)")
+    if nzs > LQR_MAX_NZ:
+        raise NotImplementedError(f"structured HIP backend: an LQR design for a model with more than {LQR_MAX_NZ} algebraic states (this "
+                                  f"model: n_z = {nzs}; the kernel eliminates g_z on a row of 16 lanes)")
     parts, tables = [], []
-    if has_model:
+    if has_model and nzs:
+        assert len(x_sym) == nx and len(u_sym) == nu and len(rhs) == nx and len(alg) == nzs
+        binds: Dict[int, str] = {}
+        for cname, syms in (("x", x_sym), ("u", u_sym), ("tvp", tvp_sym), ("p", p_sym), ("z", z_sym)):
+            for i, s in enumerate(syms):
+                binds[s.idx] = f"{cname}[{i}]"
+        wrt = (("x", list(x_sym)), ("u", list(u_sym)), ("z", list(z_sym)))
+        jac = {(fn, wn): sym.forward_jacobian(list(f), w) for fn, f in (("F", rhs), ("G", alg)) for wn, w in wrt}
+        flat = [e for Mx in jac.values() for row in Mx for e in row] + list(alg)
+        if sym.depends_on(flat[:-nzs], list(w_sym)):
+            raise NotImplementedError("structured HIP backend: an LQR design whose linearisation depends on _w (process noise)")
+        flat = sym.substitute_nodes(flat, {s.idx: sym.ZERO for s in list(w_sym) + list(v_sym)})
+        free = [s for s in sym.free_symbols(flat) if s.idx not in binds]
+        if free:
+            raise Exception(f"the linearisation depends on symbols outside (_x,_u,_z,_tvp,_p,_w,_v): {free}")
+        pos = 0
+        for key, Mx in jac.items():
+            rows, cols = len(Mx), len(Mx[0]) if Mx else 0
+            jac[key] = [flat[pos + i * cols:pos + (i + 1) * cols] for i in range(rows)]
+            pos += rows * cols
+        g0 = flat[pos:]
+        nz = lambda e: not (e.op == "const" and e.val == 0.0)      # noqa: E731
+        sig = "const double* x, const double* u, const double* tvp, const double* p, const double* z"
+        arrays = (("F", "x", "Fx"), ("F", "u", "Fu"), ("F", "z", "Fz"), ("G", "x", "Gx"), ("G", "u", "Gu"), ("G", "z", "Gz"))
+        # entries that are constants go through one table and one rolled loop per matrix (256 stores of literals, unrolled, take every
+        # register of the kernel: n_z = 16 with a linear g spilled), the others are emitted as expressions
+        parts.append("#ifndef DOMPC_HOST_EMU\n#define LQR_GEN_CONST __device__ static const\n#else\n#define LQR_GEN_CONST static const\n#endif\n"
+                     "#ifdef __clang__\n#define LQR_GEN_ROLLED _Pragma(\"nounroll\")\n#else\n#define LQR_GEN_ROLLED\n#endif\n")
+        loops, exprs = {}, {}
+        for fn, wn, arr in arrays:
+            cols = len(jac[fn, wn][0]) if jac[fn, wn] else 0
+            flat_e = [(i * cols + j, e) for i, row in enumerate(jac[fn, wn]) for j, e in enumerate(row) if nz(e)]
+            cst = [(k, e.val) for k, e in flat_e if e.op == "const"]
+            exprs[arr] = [(f"{arr}[{k}]", e) for k, e in flat_e if e.op != "const"]
+            loops[arr] = ""
+            if cst:
+                parts.append(_fmt_array(f"LQR_{arr.upper()}_CI", [k for k, _ in cst], "int").replace("DOMPC_CONST", "LQR_GEN_CONST"))
+                parts.append(_fmt_array(f"LQR_{arr.upper()}_CV", [v for _, v in cst]).replace("DOMPC_CONST", "LQR_GEN_CONST"))
+                loops[arr] = f"  LQR_GEN_ROLLED\n  for (int k = 0; k < {len(cst)}; ++k) {arr}[LQR_{arr.upper()}_CI[k]] = LQR_{arr.upper()}_CV[k];\n"
+        body = sym.emit_c([o for _, _, arr in arrays for o in exprs[arr]], binds, indent="  ")
+        parts.append(f"DOMPC_FN void lqr_lin_dae({sig}, double* Fx, double* Fu, double* Fz, double* Gx, double* Gu, double* Gz) {{\n"
+                     f"{''.join(loops[arr] for _, _, arr in arrays)}{body}\n}}\n")
+        body = sym.emit_c([(f"g[{i}]", e) for i, e in enumerate(g0)] + exprs["Gz"], binds, indent="  ")
+        parts.append(f"DOMPC_FN void lqr_alg({sig}, double* g, double* Gz) {{\n{loops['Gz']}{body}\n}}\n")
+        parts.append("DOMPC_FN void lqr_lin(const double*, const double*, const double*, const double*, double*, double*) {}\n")
+
+        def table(tname, key):
+            vals = [1 if nz(e) else 0 for row in jac[key] for e in row] or [0]
+            return f"static constexpr int {tname}[{len(vals)}] = {{{', '.join(str(v) for v in vals)}}};"
+        tables = [f"#define LQR_NZ {nzs}",
+                  "// structure of f_x (NX x NX), f_u (NX x NU), f_z (NX x NZ), g_x (NZ x NX), g_u (NZ x NU), g_z (NZ x NZ), row-major: 1 = written by",
+                  "// lqr_lin_dae (g_z by lqr_alg too), 0 = zero for every argument",
+                  table("LQR_A_NZ", ("F", "x")), table("LQR_B_NZ", ("F", "u")), table("LQR_FZ_NZ", ("F", "z")),
+                  table("LQR_GX_NZ", ("G", "x")), table("LQR_GU_NZ", ("G", "u")), table("LQR_GZ_NZ", ("G", "z"))]
+    elif has_model:
         assert len(x_sym) == nx and len(u_sym) == nu and len(rhs) == nx
         binds: Dict[int, str] = {}
         for cname, syms in (("x", x_sym), ("u", u_sym), ("tvp", tvp_sym), ("p", p_sym)):

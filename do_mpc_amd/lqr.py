@@ -9,7 +9,10 @@ finite horizon, and the finite-horizon gain is the K of the LAST pass of the bac
 Underneath, scipy's solve_discrete_are / the recursion of discrete_gain - and, for `gains_at`, the Jacobians of
 do_mpc.model.linearize and the zero-order hold of LinearModel.discretize - are one launch of csrc/dompc_lqr.hip behind the C ABI
 `dompc_lqr_*` (include/dompc_ipm.h): `gains_batch` designs B controllers for B discrete pairs, `gains_at` for B operating points of
-a nonlinear model, `*_device` do the same on device pointers.  `setup()` is the batch of one.
+a nonlinear model, `*_device` do the same on device pointers.  `setup()` is the batch of one.  A model with algebraic states
+(index-1 DAE) is designed by `gains_at` on its original states and inputs: Newton on the algebraic equations and the reduction
+A = f_x - f_z g_z^-1 g_x, B = f_u - f_z g_z^-1 g_u run inside the same launch (the reference's own route for such a model,
+do_mpc.model.dae2odeconversion -> linearize -> LQR, is in model.py and needs nothing of the kernel).
 
 There is no CPU fallback: without a HIP device `setup()` raises.
 """
@@ -35,6 +38,8 @@ class LQRSettings:
     n_horizon: Optional[int] = None
     tol: float = 1e-13                    # relative change of the Riccati iterate
     max_iter: int = 50
+    z_tol: float = 1e-10                  # models with algebraic states: Newton on g = 0 stops at max |g| <= z_tol ...
+    z_max_iter: int = 20                  # ... or after z_max_iter updates (at most 127)
     gpu_index: int = 0
 
     def check_for_mandatory_settings(self):
@@ -45,7 +50,8 @@ class LQRSettings:
 class LQRDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("nx", "nu", "n", "rate", "has_model", "discrete", "np", "ntvp")] + \
                [("code_object_path", C.c_char_p), ("model_hash", C.c_char_p), ("device", C.c_int32), ("n_horizon", C.c_int32),
-                ("max_iter", C.c_int32), ("t_step", C.c_double), ("tol", C.c_double)]
+                ("max_iter", C.c_int32), ("t_step", C.c_double), ("tol", C.c_double), ("nz", C.c_int32), ("z_max_iter", C.c_int32),
+                ("z_tol", C.c_double)]
 
 
 def _bind(lib_path: str) -> C.CDLL:
@@ -60,6 +66,10 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_lqr_design_batch.restype = C.c_int
     lib.dompc_lqr_design_batch_device.argtypes = [vp, C.c_int32] + [vp] * 9 + [C.c_int32] + [vp] * 4
     lib.dompc_lqr_design_batch_device.restype = C.c_int
+    lib.dompc_lqr_design_dae_batch.argtypes = [vp, C.c_int32] + [vp] * 8 + [C.c_int32] + [vp] * 6
+    lib.dompc_lqr_design_dae_batch.restype = C.c_int
+    lib.dompc_lqr_design_dae_batch_device.argtypes = [vp, C.c_int32] + [vp] * 10 + [C.c_int32] + [vp] * 5
+    lib.dompc_lqr_design_dae_batch_device.restype = C.c_int
     return lib
 
 
@@ -99,12 +109,12 @@ class _Design:
             hdr = lowering.lower_lqr(nx=nx, nu=nu, rate=rate)
         else:
             assert model.flags["setup"] is True, "Run this function after original model is setup"
-            assert model._z.size == 0, "Linearization around steady state is not supported for DAEs"
             assert (model.n_x, model.n_u) == (nx, nu), "the model must have the states and inputs of the controller's model"
             hdr = lowering.lower_lqr(nx=nx, nu=nu, rate=rate, x_sym=model._x.cat.nodes(), u_sym=model._u.cat.nodes(),
                                      tvp_sym=model._tvp.cat.nodes(), p_sym=model._p.cat.nodes(), w_sym=model._w.cat.nodes(),
                                      v_sym=model._v.cat.nodes(), z_sym=model._z.cat.nodes(), rhs=model._rhs.nodes(),
-                                     discrete=model.model_type == "discrete", name=type(model).__name__)
+                                     discrete=model.model_type == "discrete", name=type(model).__name__,
+                                     **({"alg": model._alg.nodes()} if model.n_z else {}))
         self.header = hdr
         self.hash = hdr.rsplit('LQR_MODEL_HASH "', 1)[1].split('"')[0]
         self.model = model
@@ -219,7 +229,9 @@ class LQR:
         if nh < 1 and s.n_horizon is not None:
             raise ValueError(f"n_horizon must be None (infinite horizon) or at least 1, you have {s.n_horizon}")
         cont = model is not None and model.model_type == "continuous"
-        skey = (nh, int(s.max_iter), float(s.tol), float(s.t_step) if cont else 0.0, int(s.gpu_index))
+        nz = 0 if model is None else model.n_z
+        skey = (nh, int(s.max_iter), float(s.tol), float(s.t_step) if cont else 0.0, int(s.gpu_index)) + \
+            ((float(s.z_tol), int(s.z_max_iter)) if nz else ())
         if d.h is not None and d.key == skey:
             return d
         if d.h is not None:
@@ -232,7 +244,8 @@ class LQR:
                        has_model=0 if model is None else 1, discrete=0 if cont else 1,
                        np=0 if model is None else model.n_p, ntvp=0 if model is None else model.n_tvp,
                        code_object_path=code_object.encode(), model_hash=d.hash.encode(), device=s.gpu_index, n_horizon=nh,
-                       max_iter=int(s.max_iter), t_step=float(s.t_step) if cont else 0.0, tol=float(s.tol))
+                       max_iter=int(s.max_iter), t_step=float(s.t_step) if cont else 0.0, tol=float(s.tol), nz=nz,
+                       z_max_iter=int(s.z_max_iter) if nz else 0, z_tol=float(s.z_tol) if nz else 0.0)
         h = C.c_void_p()
         _native.check(d.lib.dompc_lqr_create(C.byref(desc), C.byref(h)), "dompc_lqr_create failed: ", d.lib.dompc_lqr_last_error)
         d.h, d.key = h, skey
@@ -306,20 +319,31 @@ class LQR:
             raise ValueError(f"B: expected shape ({Bn}, {m.n_x}, {m.n_u}), got {Bm.shape}")
         return self._run(None, Bn, A, Bm, None, None, None, None, Q, R, P)
 
-    def gains_at(self, model: Model, XSS, USS, TVP=None, P=None, Q=None, R=None, PAR=None) -> dict:
-        """Designs at Bn operating points XSS [Bn][nx], USS [Bn][nu] of the nonlinear ODE `model` in ONE launch: Jacobians at the
+    def gains_at(self, model: Model, XSS, USS, TVP=None, P=None, Q=None, R=None, PAR=None, Z0=None, z_out: bool = True) -> dict:
+        """Designs at Bn operating points XSS [Bn][nx], USS [Bn][nu] of the nonlinear `model` in ONE launch: Jacobians at the
         points, zero-order hold over settings.t_step for a continuous model, Riccati solution and gain.  Q, R, P: the weights, as in
         gains_batch (P is the terminal weight of a finite horizon).  TVP / PAR: the model's time-varying and constant parameters, one
-        row or one per point.  Returns what gains_batch returns plus 'A', 'B': the discrete pairs."""
+        row or one per point.  Returns what gains_batch returns plus 'A', 'B': the discrete pairs.
+
+        A model with algebraic states (x' = f(x, u, z), 0 = g(x, u, z)) is designed on its ORIGINAL states and inputs: Z0 [Bn][nz] or
+        [nz] (default 0) is the guess of the algebraic states, every design solves g = 0 for z by Newton's method (settings.z_tol,
+        settings.z_max_iter) and linearises the reduced system x' = f(x, u, zeta(x, u)): A = f_x - f_z g_z^-1 g_x, B = f_u - f_z
+        g_z^-1 g_u, exact at any operating point.  The dict then holds 'Z' [Bn][nz], the consistent algebraic states (unless
+        z_out=False), and 'newton', the Newton updates of every design; status bit 2 = Newton did not converge, or g_z singular or
+        not finite at the last iterate (K = 0, P = Q, A = B = 0)."""
         m = self.model
         X = np.ascontiguousarray(np.asarray(XSS, dtype=np.float64)).reshape(-1, m.n_x)
         Bn = X.shape[0]
         U = np.ascontiguousarray(np.asarray(USS, dtype=np.float64)).reshape(Bn, m.n_u)
         if model.model_type == "continuous":
             self.settings.check_for_mandatory_settings()
-        return self._run(model, Bn, None, None, X, U, TVP, PAR, Q, R, P)
+        Z = None
+        if model.n_z:
+            Z = np.zeros((Bn, model.n_z)) if Z0 is None else np.asarray(Z0, dtype=np.float64)
+            Z = np.ascontiguousarray(np.broadcast_to(Z.reshape(-1, model.n_z), (Bn, model.n_z)))
+        return self._run(model, Bn, None, None, X, U, TVP, PAR, Q, R, P, Z, z_out)
 
-    def _run(self, model, Bn, A, Bm, X, U, TVP, Pm, Q, R, Pt) -> dict:
+    def _run(self, model, Bn, A, Bm, X, U, TVP, Pm, Q, R, Pt, Z=None, z_out=True) -> dict:
         d = self._design(model)
         lib = d.lib
         m = self.model
@@ -337,12 +361,21 @@ class LQR:
         Bo = np.empty((Bn, m.n_x, m.n_u)) if model is not None else None
         status = np.zeros(Bn, dtype=np.int32)
         ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None      # noqa: E731
-        rc = lib.dompc_lqr_design_batch(d.h, Bn, ptr(A), ptr(Bm), ptr(X), ptr(U), ptr(tvp), ptr(p), ptr(Qd), ptr(Rd), ptr(Pd), mask,
-                                        ptr(K), ptr(Pout), ptr(Ao), ptr(Bo), ptr(status))
+        Zo = np.empty_like(Z) if Z is not None and z_out else None
+        if Z is not None:
+            rc = lib.dompc_lqr_design_dae_batch(d.h, Bn, ptr(X), ptr(U), ptr(Z), ptr(tvp), ptr(p), ptr(Qd), ptr(Rd), ptr(Pd), mask,
+                                                ptr(K), ptr(Pout), ptr(Ao), ptr(Bo), ptr(Zo), ptr(status))
+        else:
+            rc = lib.dompc_lqr_design_batch(d.h, Bn, ptr(A), ptr(Bm), ptr(X), ptr(U), ptr(tvp), ptr(p), ptr(Qd), ptr(Rd), ptr(Pd), mask,
+                                            ptr(K), ptr(Pout), ptr(Ao), ptr(Bo), ptr(status))
         self._check(lib, rc, d.h)
-        out = {"K": K, "P": Pout, "iters": status >> 8, "status": status & 0xFF}
+        out = {"K": K, "P": Pout, "iters": (status >> 8) & 0xFFFF, "status": status & 0xFF}
         if model is not None:
             out["A"], out["B"] = Ao, Bo
+        if Z is not None:
+            out["newton"] = status >> 24
+            if Zo is not None:
+                out["Z"] = Zo
         return out
 
     def gains_batch_device(self, Bn, A, B, Q, R, K, P, P_term=0, status=0, shared_mask=0, stream=0):
@@ -355,14 +388,20 @@ class LQR:
             C.c_void_p(int(stream) if stream else None))
         self._check(d.lib, rc, d.h)
 
-    def gains_at_device(self, model, Bn, x, u, Q, R, K, P, tvp=0, p=0, P_term=0, A=0, B=0, status=0, shared_mask=0, stream=0):
+    def gains_at_device(self, model, Bn, x, u, Q, R, K, P, tvp=0, p=0, P_term=0, A=0, B=0, status=0, shared_mask=0, stream=0, z=0,
+                        z_out=0):
         """gains_at on raw device addresses; A / B (optional) receive the discrete pairs.  shared_mask: bit 0/1/2/3/4 =
-        Q/R/P_term/tvp/p is one row shared by all designs."""
+        Q/R/P_term/tvp/p is one row shared by all designs.  A model with algebraic states needs z [Bn][nz], the guess of the algebraic
+        states; z_out [Bn][nz] (optional, may be z itself) receives the consistent ones."""
         d = self._design(model)
-        args = [C.c_void_p(int(a) if a else None) for a in (A, B, x, u, tvp, p, Q, R, P_term)]
-        rc = d.lib.dompc_lqr_design_batch_device(
-            d.h, int(Bn), *args, int(shared_mask), C.c_void_p(int(K)), C.c_void_p(int(P)), C.c_void_p(int(status) if status else None),
-            C.c_void_p(int(stream) if stream else None))
+        vp = lambda a: C.c_void_p(int(a) if a else None)      # noqa: E731
+        if model.n_z:
+            rc = d.lib.dompc_lqr_design_dae_batch_device(
+                d.h, int(Bn), *[vp(a) for a in (A, B, x, u, z, tvp, p, Q, R, P_term)], int(shared_mask), vp(K), vp(P), vp(z_out), vp(status),
+                vp(stream))
+        else:
+            rc = d.lib.dompc_lqr_design_batch_device(
+                d.h, int(Bn), *[vp(a) for a in (A, B, x, u, tvp, p, Q, R, P_term)], int(shared_mask), vp(K), vp(P), vp(status), vp(stream))
         self._check(d.lib, rc, d.h)
 
     # ------------------------------------------------------------------ setup and runtime

@@ -463,3 +463,121 @@ def linearize(model: Model, xss: np.ndarray = None, uss: np.ndarray = None, tvp0
         D = None
     linear.setup(A, B, C, D)
     return linear
+
+
+# ------------------------------------------------------------------------------------------------ models with algebraic states
+def dae2odeconversion(model: Model) -> Model:
+    """Index-1 DAE model x' = f(x, u, z), 0 = g(x, u, z) (or x+ = f for a discrete one) as an ODE model by differentiation of the
+    algebraic equations, with the surface of the reference (/root/reference/do_mpc/model/_dae2odeconversion.py): the new model has the
+    STATES [x, u, z] under their old names and ONE input `q` of shape (n_u, 1), the rate of the old inputs:
+
+        x' = f(x, u, z),   u' = q,   z' = -g_z^-1 g_x f - g_z^-1 g_u q.
+
+    `_p` and `_tvp` are carried over, and so is the process noise of every state that had it.  g_z^-1 is symbolic (sym.inv)."""
+    assert model.flags["setup"] is True, "Run this function after original model is setup"
+    new = Model(model.model_type, model.symvar_type)
+    groups = {}
+    for var_type, target in (("_x", "_x"), ("_u", "_x"), ("_z", "_x"), ("_p", "_p"), ("_tvp", "_tvp")):
+        old_nodes, new_nodes = [], []
+        for name in getattr(model, var_type).names:
+            if name == "default":
+                continue
+            v_old = getattr(model, var_type).vars[name]
+            v_new = new.set_variable(target, name, v_old.shape)
+            old_nodes += v_old.nodes()
+            new_nodes += v_new.nodes()
+        groups[var_type] = (old_nodes, new_nodes)
+    q = new.set_variable("_u", "q", (model.n_u, 1))
+    mapping = {o.idx: n for old_nodes, new_nodes in groups.values() for o, n in zip(old_nodes, new_nodes)}
+    col = lambda nodes: sym.SX(list(nodes), (len(nodes), 1))      # noqa: E731
+    rhs = col(sym.substitute_nodes(model._rhs.nodes(), mapping))          # (on the new symbols, with the old model's noise symbols)
+    alg = col(sym.substitute_nodes(model._alg.nodes(), mapping))
+    w_old = model._w.cat.nodes()
+    rhs_new = col(sym.substitute_nodes(rhs.nodes(), {s.idx: sym.ZERO for s in w_old}))
+    off = 0
+    for name in model._x.names:
+        k = model._x.vars[name].numel()
+        new.set_rhs(name, rhs_new[off:off + k], process_noise=(name + "_noise") in model._w.names)
+        off += k
+    w_new = new._w.cat.nodes()
+    assert len(w_new) == len(w_old)
+    rhs_mod = col(sym.substitute_nodes(rhs.nodes(), {o.idx: n for o, n in zip(w_old, w_new)}))
+    alg = col(sym.substitute_nodes(alg.nodes(), {o.idx: n for o, n in zip(w_old, w_new)}))
+    x_new, u_new, z_new = (col(groups[k][1]) for k in ("_x", "_u", "_z"))
+    gz_inv = sym.inv(sym.jacobian(alg, z_new))
+    z_next = -gz_inv @ sym.jacobian(alg, x_new) @ rhs_mod - gz_inv @ sym.jacobian(alg, u_new) @ q
+    off = 0
+    for name in model._u.names:
+        if name == "default":
+            continue
+        k = model._u.vars[name].numel()
+        new.set_rhs(name, q[off:off + k])
+        off += k
+    off = 0
+    for name in model._z.names:
+        if name == "default":
+            continue
+        k = model._z.vars[name].numel()
+        new.set_rhs(name, z_next[off:off + k])
+        off += k
+    new.setup()
+    print("The states of the new model are {}".format(new.x.keys()))
+    return new
+
+
+def _dae_functions(model: Model):
+    """(g and g_z; f_x f_u f_z g_x g_u g_z) of a model with algebraic states as functions of (x, u, z, tvp, p), noise zero"""
+    if getattr(model, "_dae_lin", None) is None:
+        zero = {s.idx: sym.ZERO for s in model._w.cat.nodes() + model._v.cat.nodes()}
+        col = lambda nodes: sym.SX(list(nodes), (len(nodes), 1))      # noqa: E731
+        f, g = col(sym.substitute_nodes(model._rhs.nodes(), zero)), col(sym.substitute_nodes(model._alg.nodes(), zero))
+        ins = [model._x.cat, model._u.cat, model._z.cat, model._tvp.cat, model._p.cat]
+        x, u, z = ins[:3]
+        model._dae_lin = (sym.Function("alg", ins, [g, sym.jacobian(g, z)]),
+                          sym.Function("lin", ins, [sym.jacobian(a, b) for a in (f, g) for b in (x, u, z)]))
+    return model._dae_lin
+
+
+def linearize_dae(model: Model, xss: np.ndarray, uss: np.ndarray, z0: np.ndarray = None, tvp0: np.ndarray = None, p0: np.ndarray = None,
+                  tol: float = 1e-10, max_iter: int = 20) -> LinearModel:
+    """LinearModel (states and inputs of `model`, state feedback) of the REDUCED system of an index-1 DAE model x' = f(x, u, z),
+    0 = g(x, u, z) (x+ = f for a discrete one) at the operating point (xss, uss) - the host statement, in numpy, of what the design
+    kernel of LQR.gains_at does for such a model:
+      1. Newton on g(xss, uss, z) = 0 from the guess z0 (default 0): z <- z - g_z^-1 g until max |g| <= tol, at most max_iter updates;
+      2. g_z [Z_x Z_u] = [g_x g_u];
+      3. A = f_x - f_z Z_x, B = f_u - f_z Z_u.
+    Unlike the route dae2odeconversion -> linearize this is exact at any operating point and keeps the model's size.  The consistent
+    algebraic states are returned as the attribute `zss` [nz][1] of the linear model, the Newton updates as `newton_passes`.  Raises
+    when Newton does not converge or g_z is singular."""
+    assert model.flags["setup"] is True, "Run this function after original model is setup"
+    assert model.n_z > 0, "linearize_dae is for models with algebraic states: use linearize"
+    f_alg, f_lin = _dae_functions(model)
+    flat = lambda a, n, what: np.zeros(n) if (a is None and what == "z0") else np.asarray(      # noqa: E731
+        a.master if hasattr(a, "master") else a, dtype=float).reshape(-1)
+    for what, a, n in (("tvp0", tvp0, model.n_tvp), ("p0", p0, model.n_p)):
+        if a is None and n:
+            raise NotImplementedError(f"LTV models are not yet implemented. ({what} is needed: the model has parameters)")
+    args = [flat(xss, model.n_x, "xss"), flat(uss, model.n_u, "uss"), flat(z0, model.n_z, "z0"),
+            flat(tvp0 if model.n_tvp else np.zeros(0), 0, "tvp0"), flat(p0 if model.n_p else np.zeros(0), 0, "p0")]
+    nz = model.n_z
+    passes = 0
+    while True:
+        g, gz = f_alg.eval(*args)
+        gz = gz.reshape((nz, nz), order="F")
+        if np.max(np.abs(g)) <= tol:
+            break
+        if passes >= max_iter or not np.all(np.isfinite(g)):
+            raise RuntimeError(f"linearize_dae: Newton on the algebraic equations did not converge (max |g| = {np.max(np.abs(g)):.3e} "
+                               f"after {passes} updates)")
+        args[2] = args[2] - np.linalg.solve(gz, g)
+        passes += 1
+    n_x, n_u = model.n_x, model.n_u
+    fx, fu, fz, gx, gu, gz = (M.reshape(shape, order="F") for M, shape in zip(
+        f_lin.eval(*args), ((n_x, n_x), (n_x, n_u), (n_x, nz), (nz, n_x), (nz, n_u), (nz, nz))))
+    Z = np.linalg.solve(gz, np.hstack([gx, gu]))
+    A, B = fx - fz @ Z[:, :n_x], fu - fz @ Z[:, n_x:]
+    linear = LinearModel(model.model_type, model.symvar_type)
+    model._transfer_variables(model, linear, transfer=("_x", "_u", "_tvp", "_p", "_aux"))
+    linear.setup(A, B)
+    linear.zss, linear.newton_passes = args[2].reshape(-1, 1).copy(), passes
+    return linear

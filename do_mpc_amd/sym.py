@@ -763,6 +763,33 @@ def mtimes(a, b) -> SX:
     return SX(out, (n, m))
 
 
+def inv(a) -> SX:
+    """Inverse of a square matrix by Gauss-Jordan elimination on the expression DAG, with constant folding (a matrix of constants
+    gives a matrix of constants).  The pivot is chosen STRUCTURALLY - the first entry of the column, among the rows that are left,
+    that is not the constant 0 - so the result is valid wherever those entries do not vanish; a column without one raises."""
+    a = _sx(a)
+    n, m = a.shape
+    if n != m:
+        raise ValueError(f"inv: the matrix must be square, you have {a.shape}")
+    M = [[a.data[i + j * n] for j in range(n)] for i in range(n)]
+    R = [[ONE if i == j else ZERO for j in range(n)] for i in range(n)]
+    for k in range(n):
+        piv = next((r for r in range(k, n) if not _is(M[r][k], 0.0)), None)
+        if piv is None:
+            raise RuntimeError(f"inv: the matrix is structurally singular (column {k} has no entry left that is not the constant 0)")
+        M[k], M[piv], R[k], R[piv] = M[piv], M[k], R[piv], R[k]
+        d = M[k][k]
+        M[k] = [div(e, d) for e in M[k]]
+        R[k] = [div(e, d) for e in R[k]]
+        for r in range(n):
+            f = M[r][k]
+            if r == k or _is(f, 0.0):
+                continue
+            M[r] = [sub(e, mul(f, pe)) for e, pe in zip(M[r], M[k])]
+            R[r] = [sub(e, mul(f, pe)) for e, pe in zip(R[r], R[k])]
+    return SX([R[i][j] for j in range(n) for i in range(n)], (n, n))
+
+
 def sum1(a) -> SX:
     a = _sx(a)
     n, m = a.shape

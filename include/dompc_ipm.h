@@ -349,6 +349,9 @@ typedef struct dompc_lqr_desc {
   int32_t n_horizon;                 /* 0: infinite horizon                                                     */
   int32_t max_iter;                  /* doubling steps; 0 = 50                                                  */
   double t_step, tol;                /* tol: relative change of H that ends the doubling; 0 = 1e-13             */
+  int32_t nz;                        /* algebraic states of the model (0: none; at most 16)                    */
+  int32_t z_max_iter;                /* Newton updates on g = 0; 0 = 20, at most 127                            */
+  double z_tol;                      /* Newton stops at max |g| <= z_tol; 0 = 1e-10                             */
 } dompc_lqr_desc;
 int  dompc_lqr_create(const dompc_lqr_desc* desc, dompc_lqr** out);
 void dompc_lqr_destroy(dompc_lqr* h);
@@ -361,6 +364,18 @@ int dompc_lqr_design_batch(dompc_lqr* h, int32_t B, const double* A, const doubl
 int dompc_lqr_design_batch_device(dompc_lqr* h, int32_t B, double* A, double* Bm, const double* x, const double* u,
                                   const double* tvp, const double* p, const double* Q, const double* R, const double* Pf,
                                   int32_t shared_mask, double* K, double* P, int32_t* status, void* stream);
+/* ... for a model with algebraic states (desc.nz > 0; x' = f(x, u, z), 0 = g(x, u, z)): the design of the reduced system
+ * x' = f(x, u, zeta(x, u)) in the same launch - Newton on g = 0 from the guess z [B][nz], g_z [Z_x Z_u] = [g_x g_u],
+ * A = f_x - f_z Z_x, B = f_u - f_z Z_u, then as above.  z_out / Z_out [B][nz] (may be NULL) receive the consistent algebraic states.
+ * status bit 2 = Newton did not converge, or g_z singular or not finite at the last iterate (K = 0, P = Q, A = B = 0); iterations
+ * = (status >> 8) & 0xFFFF, Newton updates = status >> 24. */
+int dompc_lqr_design_dae_batch(dompc_lqr* h, int32_t B, const double* x, const double* u, const double* z, const double* tvp,
+                               const double* p, const double* Q, const double* R, const double* Pf, int32_t shared_mask,
+                               double* K_out, double* P_out, double* A_out, double* B_out, double* Z_out, int32_t* status);
+int dompc_lqr_design_dae_batch_device(dompc_lqr* h, int32_t B, double* A, double* Bm, const double* x, const double* u,
+                                      const double* z, const double* tvp, const double* p, const double* Q, const double* R,
+                                      const double* Pf, int32_t shared_mask, double* K, double* P, double* z_out, int32_t* status,
+                                      void* stream);
 
 /* ---- batched approximate MPC (csrc/dompc_ampc.hip): what do_mpc.approximateMPC.ApproxMPC.make_step computes - scale the input
  * [x; u_prev] by its bounds box, evaluate a feed-forward network in float32, rescale the output to [lbu, ubu] and clip - for B

@@ -37,6 +37,7 @@ CASES = {
     "dip": "results_dip.pkl",                                           # double inverted pendulum (collocation, nl_cons, tvp)
     "cstr_lqr": "results_CSTR_LQR.pkl",                                 # linear quadratic regulator: simulator records only
     "oscillating_masses_lqr": "results_oscillatingMasses_LQR.pkl",
+    "batch_reactor_lqr_dae": "results_batch_reactor_LQR_DAE.pkl",       # LQR on the converted DAE model: simulator records only
 }
 
 
