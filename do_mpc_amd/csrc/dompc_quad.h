@@ -71,7 +71,8 @@ __device__ inline QdPack qd_pack(const KArgs& A, int e, double sf) {
   return k;
 }
 // request the compact records of edges e0 .. e0 + 3 (contiguous in memory) into bank `bank` of the wavefront's LDS region (LDS-DMA,
-// 64 lanes x 16 B per instruction).  Runs past the last record of the problem into the arrays behind it (ws_layout) - never used.
+// 64 lanes x 16 B per instruction).  Runs past the last record of the problem into the arrays behind it (ws_layout) - never read:
+// the rows of a partial quad beyond the last edge take the last edge's record.
 __device__ inline void stage_quad(const Prob& Q, int e0, int lane, ldsd* Ld, int bank) {
   const double* src = Q.mo + (int64_t)e0 * MO_REC;
   ldsd* dst = Ld + bank * QL_MOSZ;
@@ -151,7 +152,9 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
   __builtin_amdgcn_wave_barrier();
   QD_PH(4)
   QD_SB();
-  const ldsd* rec = Ld + bank * QL_MOSZ + g * MO_REC;         // compact record of this lane's edge
+  // compact record of this lane's edge.  A row beyond the last edge repeats that edge with ITS record, row e - e0 of the bank: row g holds
+  // what stage_quad() copied from behind the last record, and the lanes of the row vote in the pivot test below
+  const ldsd* rec = Ld + bank * QL_MOSZ + (e - e0) * MO_REC;
   // ---- 2. residual rows of state b: collocation rows (one per point), continuity row, end-point row (optimizer.py:951-983, _mpc.py:1224)
   double res[DEG], rc, ce;
   {
@@ -854,7 +857,7 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the staged records (and everything above) have landed
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    const ldsd* rec = Ld + bank * QL_MOSZ + g * MO_REC;
+    const ldsd* rec = Ld + bank * QL_MOSZ + (e - e0) * MO_REC;      // (a row beyond the last edge: the last edge's record, as in eval_edge_quad - the same verdict as the sweep's)
     ldsd* Lv = Ld + QL_WB + g * QF_VG;                        // dw | dy | rhs | rr of this lane's edge
     constexpr int V_DW = 0, V_DY = NW, V_RHS = NW + NA, V_RR = 2 * NW + NA;
     // dy -> LDS (the u part by the lanes NX ..: they hold du[j - NX] like everybody)

@@ -379,29 +379,44 @@ def check_newton_step(make_mpc, name, oracle_iters=6, delta=0.0):
     hl, hu = np.isfinite(lb), np.isfinite(ub)
     lb[hl] -= 1e-8 * np.maximum(1, np.abs(lb[hl]))
     ub[hu] += 1e-8 * np.maximum(1, np.abs(ub[hu]))
+    check_newton_step_at(mpc, nlp, x, lam, lb, ub, mu, delta, p)
+
+
+def newton_reference(mpc, nlp, x, lam, lb, ub, mu, delta, p):
+    """The KKT system of one Newton direction at (x, lam) in the box [lb, ub] with z_L, z_U = mu / distance, as the oracle states it:
+    dict(zl, zu, cv, rd, H, A, K, rhs, dx, dlam), the solution by a general sparse LU with three steps of refinement."""
+    hl, hu = np.isfinite(lb), np.isfinite(ub)
     dl, du = np.where(hl, x - lb, 1.0), np.where(hu, ub - x, 1.0)
     assert dl.min() > 0 and du.min() > 0
     zl, zu = np.where(hl, mu / dl, 0.0), np.where(hu, mu / du, 0.0)
-    dx, dlam, rd, c = mpc.S.debug_newton_step(x, lam, zl, zu, lb, ub, nlp.lbg, nlp.ubg, p, mu, delta)
     W, A, gf, cv = nlp.hess(x, p, 1.0, lam), nlp.jac(x, p), nlp.grad(x, p), nlp.g(x, p) - nlp.lbg
-    assert np.max(np.abs(c - cv)) < 1e-10 * max(1.0, np.max(np.abs(cv)))
-    assert np.max(np.abs(rd - (gf + A.T @ lam - zl + zu))) < 1e-9 * max(1.0, np.max(np.abs(rd)))
     sig = zl / dl * hl + zu / du * hu
     rx = gf + A.T @ lam - np.where(hl, mu / dl, 0.0) + np.where(hu, mu / du, 0.0)
     rx = rx + ipm.DEFAULTS["kappa_d"] * mu * ((hl & ~hu).astype(float) - (hu & ~hl).astype(float))   # damping of one-sided bounds
     dummy = np.asarray(mpc.structure.tables["dummy_idx"])
     pin = np.zeros(x.size)
     pin[dummy] = (sig[dummy] == 0)
-    K = sps.bmat([[W + sps.diags(sig + pin + delta), A.T], [A, None]], format="csc")
+    H = (W + sps.diags(sig + pin + delta)).tocsc()
+    K = sps.bmat([[H, A.T], [A, None]], format="csc")
     rhs = -np.concatenate([rx, cv])
     lu = spla.splu(K)
     sol = lu.solve(rhs)
     for _ in range(3):
         sol += lu.solve(rhs - K @ sol)
-    dxo, dlo = sol[:x.size], sol[x.size:]
+    return dict(zl=zl, zu=zu, cv=cv, rd=gf + A.T @ lam - zl + zu, H=H, A=A, K=K, rhs=rhs, dx=sol[:x.size], dlam=sol[x.size:])
+
+
+def check_newton_step_at(mpc, nlp, x, lam, lb, ub, mu, delta, p, ref=None):
+    """the kernel's Newton direction (debug_newton_step) against newton_reference() of the same arguments; returns the kernel's dx"""
+    ref = newton_reference(mpc, nlp, x, lam, lb, ub, mu, delta, p) if ref is None else ref
+    dx, dlam, rd, c = mpc.S.debug_newton_step(x, lam, ref["zl"], ref["zu"], lb, ub, nlp.lbg, nlp.ubg, p, mu, delta)
+    cv, dxo, K, rhs = ref["cv"], ref["dx"], ref["K"], ref["rhs"]
+    assert np.max(np.abs(c - cv)) < 1e-10 * max(1.0, np.max(np.abs(cv)))
+    assert np.max(np.abs(rd - ref["rd"])) < 1e-9 * max(1.0, np.max(np.abs(rd)))
     assert np.max(np.abs(dx - dxo)) < STEP_TOL * max(1e-12, np.max(np.abs(dxo))), np.max(np.abs(dx - dxo)) / np.max(np.abs(dxo))
     res = K @ np.concatenate([dx, dlam]) - rhs
     assert np.max(np.abs(res)) < 1e-7 * max(1.0, np.max(np.abs(rhs)))
+    return dx
 
 
 def check_newton_step_at_late_iterate(make_mpc):
@@ -453,8 +468,8 @@ def check_newton_step_at_late_iterate(make_mpc):
 
 
 def check_sweep_blocks(mpc, name, to_dev, from_dev, B=3, seed=1):
-    """Sweep kernel: g(x) and the per-edge linearised dynamics [A|B], c against the oracle's g and
-    sparse Jacobian (A = -S G_w^-1 G_x computed densely per edge from the oracle's rows)."""
+    """Sweep kernel: g(x) and the linearised dynamics [A|B], c of every edge against the oracle's g and
+    sparse Jacobian (assert_sweep_records_match_oracle)."""
     ps = mpc.structure
     nlp = oracle_nlp(name)
     g = golden(name)
@@ -468,31 +483,37 @@ def check_sweep_blocks(mpc, name, to_dev, from_dev, B=3, seed=1):
     dG, dB = to_dev(np.zeros((B, ps.n_g))), to_dev(np.zeros((B, ps.n_edges, blk)))
     mpc.S.sweep_batch_device(B, dX.ptr, dL.ptr, dP.ptr, dG.ptr, dB.ptr)
     G, BL = from_dev(dG), from_dev(dB)
+    for b in range(B):
+        assert_sweep_records_match_oracle(ps, nlp, X[b], P[b], G[b], BL[b])
+
+
+def assert_sweep_records_match_oracle(ps, nlp, x, p, g_out, blocks):
+    """g and, for EVERY edge, [A B] and c of one iterate's sweep records against the oracle's g and its sparse Jacobian
+    (A = -S G_w^-1 G_x computed densely per edge from the oracle's rows)"""
     nx, nu, M = ps.nx, ps.nu, ps.M
     na = nx + nu
-    for b in range(B):
-        gv = nlp.g(X[b], P[b])
-        assert np.max(np.abs(G[b] - gv)) < 1e-10 * max(1.0, np.max(np.abs(gv)))
-        J = nlp.jac(X[b], P[b]).tocsr()
-        for e in (0, ps.n_edges // 2, ps.n_edges - 1):
-            row0 = ps.tables["edge_row0"][e]
-            n = ps.tables["edge_parent"][e]
-            xo, uo, wo = ps.tables["node_x_off"][n], ps.tables["node_u_off"][n], ps.tables["edge_w_off"][e]
-            AB = BL[b, e, :nx * na].reshape(nx, na)
-            cvec = BL[b, e, nx * na:nx * na + nx]
-            ycols = list(range(xo, xo + nx)) + list(range(uo, uo + nu))
-            if M == 0:
-                Jy = J[row0:row0 + nx][:, ycols].toarray()
-                assert np.allclose(AB, Jy, atol=1e-12)
-                assert np.allclose(cvec, gv[row0:row0 + nx], atol=1e-12)
-            else:
-                nw = M * nx
-                Gw = J[row0:row0 + nw][:, wo:wo + nw].toarray()
-                Gy = J[row0:row0 + nw][:, ycols].toarray()
-                W = -np.linalg.solve(Gw, Gy)
-                w0 = -np.linalg.solve(Gw, gv[row0:row0 + nw])
-                assert np.allclose(AB, W[-nx:], rtol=1e-8, atol=1e-10)
-                assert np.allclose(cvec, w0[-nx:] + gv[row0 + nw:row0 + nw + nx], rtol=1e-8, atol=1e-10)
+    gv = nlp.g(x, p)
+    assert np.max(np.abs(g_out - gv)) < 1e-10 * max(1.0, np.max(np.abs(gv)))
+    J = nlp.jac(x, p).tocsr()
+    for e in range(ps.n_edges):
+        row0 = ps.tables["edge_row0"][e]
+        n = ps.tables["edge_parent"][e]
+        xo, uo, wo = ps.tables["node_x_off"][n], ps.tables["node_u_off"][n], ps.tables["edge_w_off"][e]
+        AB = blocks[e, :nx * na].reshape(nx, na)
+        cvec = blocks[e, nx * na:nx * na + nx]
+        ycols = list(range(xo, xo + nx)) + list(range(uo, uo + nu))
+        if M == 0:
+            Jy = J[row0:row0 + nx][:, ycols].toarray()
+            assert np.allclose(AB, Jy, atol=1e-12), e
+            assert np.allclose(cvec, gv[row0:row0 + nx], atol=1e-12), e
+        else:
+            nw = M * nx
+            Gw = J[row0:row0 + nw][:, wo:wo + nw].toarray()
+            Gy = J[row0:row0 + nw][:, ycols].toarray()
+            W = -np.linalg.solve(Gw, Gy)
+            w0 = -np.linalg.solve(Gw, gv[row0:row0 + nw])
+            assert np.allclose(AB, W[-nx:], rtol=1e-8, atol=1e-10), e
+            assert np.allclose(cvec, w0[-nx:] + gv[row0 + nw:row0 + nw + nx], rtol=1e-8, atol=1e-10), e
 
 
 class HostArr:
