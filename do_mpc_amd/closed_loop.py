@@ -267,7 +267,9 @@ class BatchClosedLoopEKF:
     the reference is `u0 = mpc.make_step(x0)`, `y = simulator.make_step(u0)`, `x0 = ekf.make_step(y, u0, Q, R)`
     (/root/reference/examples/triple_tank_ekf/main.py:191-200 for the plant and the filter).
     X0_true: [B][nx] plant states; x0_est: [nx] or [B][nx]; P0: [nx][nx] or [B][nx][nx]; Q, R: one matrix or one per loop;
-    V: measurement noise of the plant, None, [B][nv] (the same in every step) or a callable k -> [B][nv]."""
+    V: measurement noise of the plant, None, [B][nv] (the same in every step) or a callable k -> [B][nv].
+    A filter of a model with algebraic states (ekf.settings.dae_reduction) keeps a resident [B][nz] buffer: `ekf.z0` for every loop at
+    the start, then the algebraic states of each step's last Newton solve as the guess of the next; step() returns it as `z_est`."""
 
     def __init__(self, mpc, simulator, ekf, X0_true, x0_est, P0, Q, R, V=None, device: int = 0):
         import torch
@@ -328,6 +330,10 @@ class BatchClosedLoopEKF:
         self.p_ekf = t(ekf.p_fun(te).master if me.n_p else np.zeros(1))
         self.tvp_ekf = t(ekf.tvp_fun(te).master if me.n_tvp else np.zeros(1))
         self.estat = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.nz = me.n_z
+        if self.nz:
+            self.z_est = t(np.tile(ekf.z0.master, (B, 1)))
+            self.enewton = torch.zeros(B, dtype=torch.int32, device=dev)
         self.t_mpc0, self.dt = t0, float(mpc.settings.t_step)
         self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
         self.t_ekf0, self.dt_ekf = te, float(ekf.settings.t_step)
@@ -378,7 +384,8 @@ class BatchClosedLoopEKF:
         # 3. filter: estimate and covariance in place
         self.ekf.step_batch_device(B, self.x_est.data_ptr(), self.Pcov.data_ptr(), self.Y.data_ptr(), self.U.data_ptr(),
                                    self.tvp_ekf.data_ptr(), self.p_ekf.data_ptr(), self.Q.data_ptr(), self.R.data_ptr(),
-                                   status=self.estat.data_ptr(), shared_mask=self.mask, stream=stream.cuda_stream)
+                                   status=self.estat.data_ptr(), shared_mask=self.mask, stream=stream.cuda_stream,
+                                   **({"z": self.z_est.data_ptr(), "newton": self.enewton.data_ptr()} if self.nz else {}))
         # 4. next controller problem: x0 <- estimate, u_prev <- applied input, initial guess <- previous solution
         self.Pc[:, :nx] = self.x_est
         self.Pc[:, ps.p_off_uprev:] = self.U
@@ -387,9 +394,12 @@ class BatchClosedLoopEKF:
         torch.cuda.synchronize()
         cs = np.frombuffer(self.c_stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
         est = self.estat.cpu().numpy()
-        return {"mpc_stats": cs, "plant_status": (self.pstat.cpu().numpy() & 1), "ekf_status": est & 0xFF, "u0": self.U.cpu().numpy(),
-                "x_true": self.X.cpu().numpy(), "y": self.Y[:, :self.ny].cpu().numpy(), "x_est": self.x_est.cpu().numpy(),
-                "P": self.Pcov.cpu().numpy()}
+        out = {"mpc_stats": cs, "plant_status": (self.pstat.cpu().numpy() & 1), "ekf_status": est & 0xFF, "u0": self.U.cpu().numpy(),
+               "x_true": self.X.cpu().numpy(), "y": self.Y[:, :self.ny].cpu().numpy(), "x_est": self.x_est.cpu().numpy(),
+               "P": self.Pcov.cpu().numpy()}
+        if self.nz:
+            out["z_est"], out["ekf_newton"] = self.z_est.cpu().numpy(), self.enewton.cpu().numpy()
+        return out
 
 
 class BatchClosedLoopLQR:

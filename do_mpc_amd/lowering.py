@@ -472,19 +472,125 @@ def lower_plant(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discre
     return text + f"\n#define PLANT_MODEL_HASH \"{digest}\"\n"
 
 
-def lower_ekf(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discrete, name="ekf", z_sym=(), alg=()) -> str:
+def _gen_const_prelude(prefix: str) -> str:
+    return (f"#ifndef DOMPC_HOST_EMU\n#define {prefix}_GEN_CONST __device__ static const\n#else\n#define {prefix}_GEN_CONST static const\n#endif\n"
+            f"#ifdef __clang__\n#define {prefix}_GEN_ROLLED _Pragma(\"nounroll\")\n#else\n#define {prefix}_GEN_ROLLED\n#endif\n")
+
+
+def _split_constants(prefix: str, arr: str, Mx):
+    """The structural non-zeros of the matrix `Mx` for a generated function that writes them into `arr` (row-major) ->
+    (tables, loop, exprs): entries that are constants go through one index table and one value table (`tables`, text for the header)
+    and one rolled loop (`loop`, text for the function body); the others are `exprs` for sym.emit_c.  256 stores of literals,
+    unrolled, take every register of a kernel (n_z = 16 with a linear g spilled)."""
+    cols = len(Mx[0]) if Mx else 0
+    flat_e = [(i * cols + j, e) for i, row in enumerate(Mx) for j, e in enumerate(row) if not (e.op == "const" and e.val == 0.0)]
+    cst = [(k, e.val) for k, e in flat_e if e.op == "const"]
+    exprs = [(f"{arr}[{k}]", e) for k, e in flat_e if e.op != "const"]
+    if not cst:
+        return [], "", exprs
+    ci, cv = f"{prefix}_{arr.upper()}_CI", f"{prefix}_{arr.upper()}_CV"
+    tables = [_fmt_array(ci, [k for k, _ in cst], "int").replace("DOMPC_CONST", f"{prefix}_GEN_CONST"),
+              _fmt_array(cv, [v for _, v in cst]).replace("DOMPC_CONST", f"{prefix}_GEN_CONST")]
+    return tables, f"  {prefix}_GEN_ROLLED\n  for (int k = 0; k < {len(cst)}; ++k) {arr}[{ci}[k]] = {cv}[k];\n", exprs
+
+
+EKF_MAX_NZ = 16          # algebraic states of a filter: g_z is eliminated on one row of 16 lanes
+
+
+def _lower_ekf_dae(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, z_sym, rhs, meas, alg, discrete, name) -> str:
+    """lower_ekf for a model with algebraic states: see there"""
+    nx, ny, nzs = len(x_sym), len(meas), len(z_sym)
+    assert len(rhs) == nx and len(alg) == nzs
+    binds: Dict[int, str] = {}
+    for cname, syms in (("x", x_sym), ("u", u_sym), ("tvp", tvp_sym), ("p", p_sym), ("z", z_sym)):
+        for i, s in enumerate(syms):
+            binds[s.idx] = f"{cname}[{i}]"
+    noise = list(w_sym) + list(v_sym)
+    wrt = (("x", list(x_sym)), ("z", list(z_sym)))
+    arrays = (("F", "x", "Fx"), ("F", "z", "Fz"), ("G", "x", "Gx"), ("G", "z", "Gz"), ("H", "x", "Hx"), ("H", "z", "Hz"))
+    what = {"Fx": "f_x = d rhs / d x", "Fz": "f_z = d rhs / d z", "Gx": "g_x = d alg / d x", "Gz": "g_z = d alg / d z",
+            "Hx": "h_x = d y / d x", "Hz": "h_z = d y / d z"}
+    jac = {(fn, wn): sym.forward_jacobian(list(f), w) for fn, f in (("F", rhs), ("G", alg), ("H", meas)) for wn, w in wrt}
+    for fn, wn, arr in arrays:
+        if sym.depends_on([e for row in jac[fn, wn] for e in row], noise):
+            raise NotImplementedError(f"structured HIP backend: an extended Kalman filter whose linearisation {what[arr]} depends on _w or _v")
+    zero = {s.idx: sym.ZERO for s in noise}
+    rhs0, meas0, alg0 = (sym.substitute_nodes(list(e), zero) for e in (rhs, meas, alg))
+    flat = [e for key in jac for row in jac[key] for e in row]
+    for label, nodes in (("rhs", rhs0), ("meas", meas0), ("alg", alg0), ("the linearisation", flat)):
+        free = [s for s in sym.free_symbols(list(nodes)) if s.idx not in binds]
+        if free:
+            raise Exception(f"{label} depends on symbols outside (_x,_u,_z,_tvp,_p,_w,_v): {free}")
+    nz = lambda e: not (e.op == "const" and e.val == 0.0)      # noqa: E731
+    sig = "const double* x, const double* u, const double* tvp, const double* p, const double* z"
+    parts = [_gen_const_prelude("EKF")]
+    loops, exprs = {}, {}
+    for fn, wn, arr in arrays:
+        tabs, loops[arr], exprs[arr] = _split_constants("EKF", arr, jac[fn, wn])
+        parts += tabs
+    body = sym.emit_c([(f"f[{i}]", e) for i, e in enumerate(rhs0)], binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_rhs({sig}, double* f) {{\n{body}\n}}\n")
+    body = sym.emit_c([(f"y[{i}]", e) for i, e in enumerate(meas0)], binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_meas({sig}, double* y) {{\n{body}\n}}\n")
+    body = sym.emit_c([(f"g[{i}]", e) for i, e in enumerate(alg0)] + exprs["Gz"], binds, indent="  ")
+    parts.append(f"DOMPC_FN void ekf_alg({sig}, double* g, double* Gz) {{\n{loops['Gz']}{body}\n}}\n")
+    for fname, arrs in (("ekf_jac_dae", ("Fx", "Fz", "Gx", "Gz")), ("ekf_lin_dae", ("Fx", "Fz", "Gx", "Gz", "Hx", "Hz"))):
+        body = sym.emit_c([o for a in arrs for o in exprs[a]], binds, indent="  ")
+        parts.append(f"DOMPC_FN void {fname}({sig}, {', '.join('double* ' + a for a in arrs)}) {{\n{''.join(loops[a] for a in arrs)}{body}\n}}\n")
+
+    pat = {arr: [[nz(e) for e in row] for row in jac[fn, wn]] for fn, wn, arr in arrays}
+    gx_col = [any(pat["Gx"][l][j] for l in range(nzs)) for j in range(nx)]
+
+    def reduced(Mx, Mz, rows):
+        """pattern of M_x - M_z g_z^-1 g_x with g_z^-1 taken as dense"""
+        return [[Mx[i][j] or (any(Mz[i]) and gx_col[j]) for j in range(nx)] for i in range(rows)]
+
+    def table(tname, P):
+        vals = [1 if v else 0 for row in P for v in row] or [0]
+        return f"static constexpr int {tname}[{len(vals)}] = {{{', '.join(str(v) for v in vals)}}};"
+    hdr = ["// GENERATED by do_mpc_amd/lowering.py:lower_ekf - do not edit.", "#pragma once", "#include <math.h>",
+           f"#define EKF_MODEL_NAME \"{name}\"",
+           f"#define EKF_NX {nx}", f"#define EKF_NU {len(u_sym)}", f"#define EKF_NP {len(p_sym)}",
+           f"#define EKF_NTVP {len(tvp_sym)}", f"#define EKF_NY {ny}", f"#define EKF_DISCRETE {1 if discrete else 0}",
+           f"#define EKF_NZ {nzs}",
+           "// structure of the REDUCED A = f_x - f_z g_z^-1 g_x (NX x NX) and C = h_x - h_z g_z^-1 g_x (NY x NX), row-major, g_z^-1 taken as",
+           "// dense: 1 = may be non-zero, 0 = zero for every argument (the kernel writes them; everything downstream indexes these tables)",
+           table("EKF_A_NZ", reduced(pat["Fx"], pat["Fz"], nx)), table("EKF_C_NZ", reduced(pat["Hx"], pat["Hz"], ny)),
+           "// structure of f_x (NX x NX), f_z (NX x NZ), g_x (NZ x NX), g_z (NZ x NZ), h_x (NY x NX), h_z (NY x NZ), row-major: 1 = written by",
+           "// ekf_lin_dae (all but the h blocks by ekf_jac_dae, g_z by ekf_alg too), 0 = zero for every argument",
+           *[table(f"EKF_{arr.upper()}_NZ", pat[arr]) for _, _, arr in arrays], ""]
+    text = "\n".join(hdr) + "\n" + "\n".join(parts)
+    digest = hashlib.sha256(text.encode()).hexdigest()[:16]
+    return text + f"\n#define EKF_MODEL_HASH \"{digest}\"\n"
+
+
+def lower_ekf(*, x_sym, u_sym, tvp_sym, p_sym, w_sym, v_sym, rhs, meas, discrete, name="ekf", z_sym=(), alg=(),
+              dae_reduction=False) -> str:
     """Header for the batched extended Kalman filter (csrc/dompc_ekf.hip), in PHYSICAL units like lower_plant:
     `ekf_rhs`, `ekf_meas` (measurement function with v = 0), `ekf_lin` (A = d rhs / d x and C = d y / d x, row-major; only their
     structural non-zeros are written, the tables EKF_A_NZ / EKF_C_NZ say which) and `ekf_jac` (A alone: the stages of the covariance
     integration).  Noise symbols are zero, as in the reference's get_linear_system_matrices (/root/reference/do_mpc/model/_model.py:1126-1128)
-    and in EKF.make_step (/root/reference/do_mpc/estimator/_ekf.py:273-274)."""
+    and in EKF.make_step (/root/reference/do_mpc/estimator/_ekf.py:273-274).
+    A model with algebraic states (`z_sym`, `alg`: x' = f(x, u, z), 0 = g(x, u, z), y = h(x, u, z)) is refused unless `dae_reduction`
+    is set (EKFSettings.dae_reduction).  Its header then carries EKF_NZ, `ekf_rhs` / `ekf_meas` taking z, `ekf_alg` (g and g_z: the
+    Newton passes), `ekf_lin_dae` (the structural non-zeros of f_x f_z g_x g_z h_x h_z at (x, u, tvp, p, z); tables EKF_*_NZ) and
+    `ekf_jac_dae` (the same without the h blocks: the stages of the integration); EKF_A_NZ / EKF_C_NZ describe the REDUCED matrices
+    A = f_x - f_z g_z^-1 g_x, C = h_x - h_z g_z^-1 g_x the kernel forms from them.  Headers of models without algebraic states carry
+    none of this (their text, and with it their hash, is what it was), whatever `dae_reduction` says."""
     nx, ny = len(x_sym), len(meas)
-    if len(z_sym) or len(alg):
+    if (len(z_sym) or len(alg)) and not dae_reduction:
         raise NotImplementedError("structured HIP backend: an extended Kalman filter for a model with algebraic states "
-                                  "(the reference asserts the same: 'EKF with algebraic equations not ready for use!')")
+                                  "(the reference asserts the same: 'EKF with algebraic equations not ready for use!'; "
+                                  "settings.dae_reduction = True runs the filter on the reduced system z = zeta(x, u))")
     if nx > 16 or ny > 16:
         raise NotImplementedError(f"structured HIP backend: an extended Kalman filter with more than 16 states or more than 16 measurements "
                                   f"(this model: n_x = {nx}, n_y = {ny}; the kernel maps one filter to a row of 16 lanes)")
+    if len(z_sym) > EKF_MAX_NZ:
+        raise NotImplementedError(f"structured HIP backend: an extended Kalman filter for a model with more than {EKF_MAX_NZ} algebraic states "
+                                  f"(this model: n_z = {len(z_sym)}; the kernel eliminates g_z on a row of 16 lanes)")
+    if len(z_sym) or len(alg):
+        return _lower_ekf_dae(x_sym=x_sym, u_sym=u_sym, tvp_sym=tvp_sym, p_sym=p_sym, w_sym=w_sym, v_sym=v_sym, z_sym=z_sym, rhs=rhs,
+                              meas=meas, alg=alg, discrete=discrete, name=name)
     groups = [("x", x_sym), ("u", u_sym), ("tvp", tvp_sym), ("p", p_sym)]
     binds: Dict[int, str] = {}
     for cname, syms in groups:
@@ -586,19 +692,11 @@ def lower_lqr(*, nx, nu, rate, x_sym=None, u_sym=(), tvp_sym=(), p_sym=(), w_sym
         arrays = (("F", "x", "Fx"), ("F", "u", "Fu"), ("F", "z", "Fz"), ("G", "x", "Gx"), ("G", "u", "Gu"), ("G", "z", "Gz"))
         # entries that are constants go through one table and one rolled loop per matrix (256 stores of literals, unrolled, take every
         # register of the kernel: n_z = 16 with a linear g spilled), the others are emitted as expressions
-        parts.append("#ifndef DOMPC_HOST_EMU\n#define LQR_GEN_CONST __device__ static const\n#else\n#define LQR_GEN_CONST static const\n#endif\n"
-                     "#ifdef __clang__\n#define LQR_GEN_ROLLED _Pragma(\"nounroll\")\n#else\n#define LQR_GEN_ROLLED\n#endif\n")
+        parts.append(_gen_const_prelude("LQR"))
         loops, exprs = {}, {}
         for fn, wn, arr in arrays:
-            cols = len(jac[fn, wn][0]) if jac[fn, wn] else 0
-            flat_e = [(i * cols + j, e) for i, row in enumerate(jac[fn, wn]) for j, e in enumerate(row) if nz(e)]
-            cst = [(k, e.val) for k, e in flat_e if e.op == "const"]
-            exprs[arr] = [(f"{arr}[{k}]", e) for k, e in flat_e if e.op != "const"]
-            loops[arr] = ""
-            if cst:
-                parts.append(_fmt_array(f"LQR_{arr.upper()}_CI", [k for k, _ in cst], "int").replace("DOMPC_CONST", "LQR_GEN_CONST"))
-                parts.append(_fmt_array(f"LQR_{arr.upper()}_CV", [v for _, v in cst]).replace("DOMPC_CONST", "LQR_GEN_CONST"))
-                loops[arr] = f"  LQR_GEN_ROLLED\n  for (int k = 0; k < {len(cst)}; ++k) {arr}[LQR_{arr.upper()}_CI[k]] = LQR_{arr.upper()}_CV[k];\n"
+            tabs, loops[arr], exprs[arr] = _split_constants("LQR", arr, jac[fn, wn])
+            parts += tabs
         body = sym.emit_c([o for _, _, arr in arrays for o in exprs[arr]], binds, indent="  ")
         parts.append(f"DOMPC_FN void lqr_lin_dae({sig}, double* Fx, double* Fu, double* Fz, double* Gx, double* Gu, double* Gz) {{\n"
                      f"{''.join(loops[arr] for _, _, arr in arrays)}{body}\n}}\n")

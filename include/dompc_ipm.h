@@ -305,10 +305,18 @@ int dompc_plant_step_batch_device(dompc_plant* h, int32_t B, const double* x, co
  *   t_step with dP/dt = A(x) P + P A(x)' + Q (explicit Dormand-Prince 5(4), step-size control per filter, no implicit method);
  *   S = C P- C' + R, L = P- C' S^-1, x = x- + L (y - meas(x-, u)), P = (I - L C) P-.
  * The model functions come from a per-model gfx950 code object (do_mpc_amd/lowering.py:lower_ekf); at most 16 states and 16
- * measurements, no algebraic states.  Layout: x [B][nx], P [B][nx][nx] row-major, y [B][ny]; u / tvp / p / Q (nx*nx) / R (ny*ny)
+ * measurements.  Layout: x [B][nx], P [B][nx][nx] row-major, y [B][ny]; u / tvp / p / Q (nx*nx) / R (ny*ny)
  * are [B][n] or, with their bit of shared_mask set (bit 0/1/2/3/4 = u/tvp/p/Q/R), ONE row shared by all filters.
  * status[b]: bit 0 = the integration did not reach t_step (step limit, NaN right-hand side); bit 1 = S singular or not finite - the
- * a-priori x-, P- are returned, never NaN; integration steps taken = status[b] >> 8. */
+ * a-priori x-, P- are returned, never NaN; integration steps taken = status[b] >> 8.
+ * Models with algebraic states (nz > 0, at most 16; x' = f(x, u, z), 0 = g(x, u, z), y = h(x, u, z)): the same filter on the reduced
+ * system z = zeta(x, u), through the entries dompc_ekf_step_dae_batch[_device].  Before every evaluation of the model Newton solves
+ * g = 0 for z (until max |g| <= z_tol, at most z_max_iter updates per solve, warm-started from the previous solve and first from the
+ * guess z [B][nz]); A = f_x - f_z g_z^-1 g_x and C = h_x - h_z g_z^-1 g_x take the place of A and C.  z_out: the algebraic states
+ * consistent with the a-priori state x- (the last solve of the step: the warm start of the next call); newton[b]: Newton updates
+ * of filter b.  status bit 2 = a Newton iteration did not converge, or g_z was singular or not finite (with bit 0 when this happens
+ * during the integration): that filter hands back its prior x, P and its guess z unchanged.  The two entries without z run such a
+ * handle from the guess 0 and hand no z back. */
 typedef struct dompc_ekf dompc_ekf;
 typedef struct dompc_ekf_desc {
   int32_t nx, nu, np, ntvp, ny;
@@ -318,6 +326,9 @@ typedef struct dompc_ekf_desc {
   int32_t device;
   int32_t max_steps;                 /* integration steps per filter and call; 0 = 200000                      */
   double t_step, reltol, abstol;
+  int32_t nz;                        /* algebraic states of the model (0: an ODE model)                       */
+  int32_t z_max_iter;                /* Newton updates per solve of g = 0; 0 = 20                              */
+  double z_tol;                      /* Newton stops at max |g| <= z_tol; 0 = 1e-10                            */
 } dompc_ekf_desc;
 int  dompc_ekf_create(const dompc_ekf_desc* desc, dompc_ekf** out);
 void dompc_ekf_destroy(dompc_ekf* h);
@@ -330,6 +341,15 @@ int dompc_ekf_step_batch(dompc_ekf* h, int32_t B, const double* x, const double*
 int dompc_ekf_step_batch_device(dompc_ekf* h, int32_t B, double* x, double* P, const double* y, const double* u,
                                 const double* tvp, const double* p, const double* Q, const double* R, int32_t shared_mask,
                                 int32_t* status, void* stream);
+/* ... for a model with algebraic states: z [B][nz] the guess (NULL = 0); z_out (may alias z) and newton may be NULL.  z_out is written
+ * only when z is given: without a guess nothing is handed back (as on the device, where z is both) */
+int dompc_ekf_step_dae_batch(dompc_ekf* h, int32_t B, const double* x, const double* P, const double* y, const double* u,
+                             const double* z, const double* tvp, const double* p, const double* Q, const double* R,
+                             int32_t shared_mask, double* x_out, double* P_out, double* z_out, int32_t* newton, int32_t* status);
+/* DEVICE buffers; z is updated IN PLACE like x and P (NULL: guess 0, nothing handed back) */
+int dompc_ekf_step_dae_batch_device(dompc_ekf* h, int32_t B, double* x, double* P, const double* y, const double* u, double* z,
+                                    const double* tvp, const double* p, const double* Q, const double* R, int32_t shared_mask,
+                                    int32_t* newton, int32_t* status, void* stream);
 
 /* ---- batched LQR design (csrc/dompc_lqr.hip): what do_mpc.controller.LQR.setup computes - the discrete Riccati solution and the gain
  * K = -(B'PB + R)^-1 B'PA - for B designs per launch, on an infinite horizon (structure-preserving doubling iteration) or over
