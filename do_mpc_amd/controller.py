@@ -850,11 +850,18 @@ class MPC:
 
     # ------------------------------------------------------------------ batched hot path (extension)
     def make_step_batch(self, X0: np.ndarray, U_prev: Optional[np.ndarray] = None,
-                        opt_x_init: Optional[np.ndarray] = None) -> dict:
+                        opt_x_init: Optional[np.ndarray] = None, sensitivities: bool = False) -> dict:
         """B independent MPC problems (same model/settings, different x0) in one device call.
         This is what do_mpc.sampling fans out over processes in the reference
-        (/root/reference/do_mpc/sampling/_sampler.py:198-228)."""
+        (/root/reference/do_mpc/sampling/_sampler.py:198-228).
+        The result carries "p", the parameter rows the problems were solved with.  sensitivities=True: the solve is followed by
+        `DoMPCDifferentiator.differentiate_batch` and its keys (du0dx0, du0du_prev, dxdp, residual_step, ok) join the result."""
         assert self.flags["setup"] is True, "MPC was not setup yet. Please call MPC.setup()."
+        if sensitivities:                                          # (what the differentiator refuses is refused before the solve)
+            nd = getattr(self, "_batch_differentiator", None)
+            if nd is None or nd[0] is not self.S:                  # (a new setup() brings a new solver and new layouts)
+                from .differentiator import DoMPCDifferentiator
+                nd = self._batch_differentiator = (self.S, DoMPCDifferentiator(self))
         ps = self.structure
         X0 = np.asarray(X0, dtype=float).reshape(-1, ps.nx)
         B = X0.shape[0]
@@ -876,6 +883,9 @@ class MPC:
             Xi = np.asarray(opt_x_init, float).reshape(B, ps.n_opt_x)
         r = self.S.solve_batch(Xi, self._lb_opt_x.master, self._ub_opt_x.master, self._nlp_cons_lb, self._nlp_cons_ub, P)
         r["u0"] = r["x"][:, ps.iu(0, 0):ps.iu(0, 0) + ps.nu] * self._u_scaling.master
+        r["p"] = P
+        if sensitivities:
+            r.update(nd[1].differentiate_batch(r))
         return r
 
 

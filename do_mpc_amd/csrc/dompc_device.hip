@@ -101,6 +101,39 @@ extern "C" __global__ void __launch_bounds__(DOMPC_BLOCK_CONST ? DOMPC_BLOCK_CON
     else dompc::solve_problem(T, A, b, slot);
   }
 }
+
+// Mode 3 (sensitivities at B points, sens_newton) has its own entry: dompc_solve_kernel stays the kernel it was.  Work items b < A.batch
+// (= points x rows of the plan) are pulled from the device-wide counter like the sweeps of mode 2; one workgroup per workspace slot.
+extern "C" __global__ void __launch_bounds__(DOMPC_BLOCK_CONST ? DOMPC_BLOCK_CONST : DOMPC_MAXBLOCK, DOMPC_LB) dompc_sens_kernel(dompc::KArgs A) {
+  using namespace dompc;
+  const int POOL = A.pool_doubles;
+  if (threadIdx.x < 32) lds_prof[threadIdx.x] = 0;
+  if (threadIdx.x < 8) lds_flags[threadIdx.x] = 0;
+  for (int i = threadIdx.x; i < POOL; i += DOMPC_BDIM) lds_pool[i] = 0.0;
+  for (int i = threadIdx.x; i < 2 * MAX_FILTER; i += DOMPC_BDIM) lds_filt[i] = 0.0;
+  __syncthreads();
+  const int slot = (int)blockIdx.x;
+  if (slot >= A.n_slots) return;
+  Thr T = make_thr(A);
+  T.kp = (const void*)__builtin_amdgcn_kernarg_segment_ptr();
+  while (true) {
+    if (threadIdx.x == 0) lds_b = atomicAdd(A.work_counter, 1);
+    __syncthreads();
+    const int b = lds_b;
+    __syncthreads();
+    if (b >= A.batch) break;
+    dompc::sens_newton(T, A, b, slot);
+  }
+}
+// parameter rows before, difference quotients after the Newton kernel: one thread per element
+extern "C" __global__ void __launch_bounds__(256) dompc_sens_prep_kernel(dompc::KArgs A) {
+  const int64_t n = (int64_t)A.batch * A.n_opt_p;
+  for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) dompc::sens_prep_item(A, it);
+}
+extern "C" __global__ void __launch_bounds__(256) dompc_sens_finish_kernel(dompc::KArgs A) {
+  const int64_t n = (int64_t)(A.batch / A.sn_R) * A.sn_nsel * A.sn_ncols;
+  for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) dompc::sens_finish_item(A, it);
+}
 #else
 extern "C" void dompc_hostemu_model_info(const int32_t* in, int64_t* out, char* hash) {
   dompc::model_info(in, out);
@@ -121,6 +154,12 @@ extern "C" void dompc_hostemu_run(const dompc::KArgs* A) {
   dompc::Thr T{0, 1, red, filt, flags, edge_lds, nullptr, 1, 0, 1, 0, 1, nullptr, nullptr, 0u, 0u, dompc::make_xctx(*A), 0u, nullptr};
   if (A->mode == 1) {
     for (int b = 0; b < A->batch; ++b) dompc::debug_newton(T, *A, b, 0);
+    return;
+  }
+  if (A->mode == 3) {                    // sensitivities: parameter rows, Newton directions, difference quotients
+    for (int64_t it = 0; it < (int64_t)A->batch * A->n_opt_p; ++it) dompc::sens_prep_item(*A, it);
+    for (int b = 0; b < A->batch; ++b) dompc::sens_newton(T, *A, b, 0);
+    for (int64_t it = 0; it < (int64_t)(A->batch / A->sn_R) * A->sn_nsel * A->sn_ncols; ++it) dompc::sens_finish_item(*A, it);
     return;
   }
   for (int b = 0; b < A->batch; ++b) {

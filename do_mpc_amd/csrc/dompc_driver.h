@@ -732,29 +732,30 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
 // mode 1: one Newton direction at a given primal-dual point (parity tests against the oracle's
 // sparse KKT solve).  Slacks: s = d(x) pushed inside, z_s = 1.
 // (b: parameter vector / output row of a batched call - same point x, lam, z for every b; slot: workspace of the workgroup)
-DOMPC_DEV inline void debug_newton(const Thr& T, const KArgs& A, int b = 0, int slot = 0) {
+// Slack variables of the nl_cons rows at a given point x (Q.x) for the Newton directions of modes 1 and 3: s = d(x) pushed inside its
+// bounds with multipliers 1 (a starting point), or - at_solution - s = d(x) strictly inside the bounds the solver relaxed, multipliers
+// mu / distance.  reduce (mode 3, active-set reduction): a row with lbg != ubg that is inactive (farther than `tol` from both of its
+// ORIGINAL bounds) loses its bounds, an active one becomes an equality at its value d(x).
+DOMPC_DEV inline void newton_slack_setup(const Thr& T, const KArgs& A, Prob& Q, int at_solution, double mu, bool reduce, double tol) {
   const dompc_options& O = A.opt;
-  Prob Q = make_prob(A, slot, A.p + (int64_t)b * A.n_opt_p);
-  const int nX = A.n_opt_x;
-  for (int g = T.tid; g < nX; g += T.nt) {
-    Q.x[g] = A.x0[g]; Q.lb[g] = A.lbx[g]; Q.ub[g] = A.ubx[g];
-    Q.zl[g] = A.dbg_zl[g]; Q.zu[g] = A.dbg_zu[g];
-  }
-  for (int r = T.tid; r < A.n_g; r += T.nt) Q.lam[r] = A.dbg_lam[r];
-  T.sync();
   if (NE > 0) {
     for (int e = T.tid; e < A.n_edges; e += T.nt) {
       for (int i = 0; i < NE; ++i) { Q.s[e * NE1 + i] = 0.0; Q.sgn[e * NE1 + i] = 1.0; }
       if (DENSE_EDGE) dae_edge_f(Q, e, Q.x, Q.s, Q.ct); else eval_edge_f(Q, e, Q.x, Q.s, Q.ct);
       for (int i = 0; i < NE; ++i) {
         const int row = A.edge_row0[e] + NW + NX + i, si = e * NE1 + i;
-        const double l = A.lbg[row], u = A.ubg[row];
+        double l = A.lbg[row], u = A.ubg[row];
+        double sv = Q.ct[row];
+        if (reduce && l != u) {
+          const bool act = fabs(sv - l) <= tol || fabs(sv - u) <= tol;
+          l = act ? sv : -INFINITY;
+          u = act ? sv : INFINITY;
+        }
         const bool hl = l > -INFINITY, hu = u < INFINITY;
         double pl = hl ? O.bound_push * fmax(1.0, fabs(l)) : 0.0;
         double pu = hu ? O.bound_push * fmax(1.0, fabs(u)) : 0.0;
         if (hl && hu) { pl = fmin(pl, O.bound_frac * (u - l)); pu = fmin(pu, O.bound_frac * (u - l)); }
-        double sv = Q.ct[row];
-        if (A.dbg_at_solution) {
+        if (at_solution) {
           // a converged point: the row residual d(x) - s vanishes, the slack is strictly inside the bounds the solver
           // relaxed (bound_relax_factor), complementarity holds at the given barrier parameter
           const double lr = hl ? l - fmin(O.constr_viol_tol, O.bound_relax_factor * fmax(1.0, fabs(l))) : l;
@@ -763,7 +764,7 @@ DOMPC_DEV inline void debug_newton(const Thr& T, const KArgs& A, int b = 0, int 
           if (hl) sv = fmax(sv, lr + tiny);
           if (hu) sv = fmin(sv, ur - tiny);
           Q.s[si] = sv; Q.sl[si] = lr; Q.su[si] = ur;
-          Q.zsl[si] = hl ? A.dbg_mu / (sv - lr) : 0.0; Q.zsu[si] = hu ? A.dbg_mu / (ur - sv) : 0.0;
+          Q.zsl[si] = hl ? mu / (sv - lr) : 0.0; Q.zsu[si] = hu ? mu / (ur - sv) : 0.0;
           continue;
         }
         if (hl) sv = fmax(sv, l + pl);
@@ -774,6 +775,18 @@ DOMPC_DEV inline void debug_newton(const Thr& T, const KArgs& A, int b = 0, int 
     }
     T.sync();
   }
+}
+
+DOMPC_DEV inline void debug_newton(const Thr& T, const KArgs& A, int b = 0, int slot = 0) {
+  Prob Q = make_prob(A, slot, A.p + (int64_t)b * A.n_opt_p);
+  const int nX = A.n_opt_x;
+  for (int g = T.tid; g < nX; g += T.nt) {
+    Q.x[g] = A.x0[g]; Q.lb[g] = A.lbx[g]; Q.ub[g] = A.ubx[g];
+    Q.zl[g] = A.dbg_zl[g]; Q.zu[g] = A.dbg_zu[g];
+  }
+  for (int r = T.tid; r < A.n_g; r += T.nt) Q.lam[r] = A.dbg_lam[r];
+  T.sync();
+  newton_slack_setup(T, A, Q, A.dbg_at_solution, A.dbg_mu, false, 0.0);
   Q.sf = 1.0;
   // (b, slot: the outlined phases rebuild their view of the problem from exactly these two - ADVICE r3: with the literal
   //  (0, 0) every workgroup of a batched call swept and factorised slot 0 with parameter row 0)
@@ -789,6 +802,109 @@ DOMPC_DEV inline void debug_newton(const Thr& T, const KArgs& A, int b = 0, int 
     A.dbg_c[(int64_t)b * A.n_g + r] = Q.c[r];
   }
   T.sync();
+}
+
+// ------------------------------------------------------------------------------------------------
+// mode 3: Newton directions at B points for the parametric sensitivities (dompc_sens_batch_device).  Work item b = q * R + r: point q
+// (a row of the solve's results x, lam_g and its final barrier parameter), parameter row r of the plan (KArgs::sn_*).  The primal-dual
+// point is built here from what a solve returns: bound multipliers mu / distance to the relaxed bounds, and - SENS_REDUCE - the active-set
+// reduction (inactive bounds leave, active ones are held with z >= 1e3; the nl_cons rows in newton_slack_setup).  Only the entries
+// sn_sel of the direction leave the kernel.  A member that is no interior point (or whose mu is not a positive number: the host's mark
+// for "not solved") and a KKT matrix with the wrong inertia give NaN rows and clear sn_ok[q].
+// The launch runs with per-slot bounds (KArgs::lb_sh null): with the reduction every point has its own.
+enum { SENS_REDUCE = 1 };
+DOMPC_DEV inline void sens_newton(const Thr& T, const KArgs& A, int b, int slot) {
+  const dompc_options& O = A.opt;
+  const int q = b / A.sn_R, r = b % A.sn_R;
+  Prob Q = make_prob(A, slot, A.p + (int64_t)b * A.n_opt_p);
+  const int nX = A.n_opt_x;
+  const double* xin = A.sn_x + (int64_t)q * nX;
+  const double* lin = A.sn_lam + (int64_t)q * A.n_g;
+  const double mu = A.sn_mu[q];
+  const bool reduce = (A.sn_flags & SENS_REDUCE) != 0;
+  const double tol = A.sn_tol;
+  double bad[1] = {(mu > 0.0 && mu < INFINITY) ? 0.0 : 1.0};
+  for (int g = T.tid; g < nX; g += T.nt) {
+    const double xv = xin[g], l0 = A.lbx[g], u0 = A.ubx[g];
+    const bool hl = l0 > -INFINITY, hu = u0 < INFINITY;
+    double lr = hl ? l0 - fmin(O.constr_viol_tol, O.bound_relax_factor * fmax(1.0, fabs(l0))) : l0;
+    double ur = hu ? u0 + fmin(O.constr_viol_tol, O.bound_relax_factor * fmax(1.0, fabs(u0))) : u0;
+    const double dl = hl ? xv - lr : 1.0, du = hu ? ur - xv : 1.0;
+    if (!(dl > 0.0) || !(du > 0.0)) bad[0] = 1.0;
+    double zl = hl ? mu / dl : 0.0, zu = hu ? mu / du : 0.0;
+    if (reduce) {
+      const bool lo = fabs(xv - l0) <= tol, up = fabs(xv - u0) <= tol;
+      if (!lo && !up) { zl = 0.0; zu = 0.0; lr = -INFINITY; ur = INFINITY; }
+      if (lo) zl = fmax(zl, 1e3);
+      if (up) zu = fmax(zu, 1e3);
+    }
+    Q.x[g] = xv; Q.lb[g] = lr; Q.ub[g] = ur; Q.zl[g] = zl; Q.zu[g] = zu;
+  }
+  for (int i = T.tid; i < A.n_g; i += T.nt) Q.lam[i] = lin[i];
+  {
+    const int ops[1] = {R_MAX};
+    wg_reduce(T, bad, ops);
+  }
+  T.sync();
+  double* D = A.sn_D + (int64_t)b * A.sn_nsel;
+  int fail = bad[0] != 0.0;
+  if (!fail) {
+    newton_slack_setup(T, A, Q, 1, mu, reduce, tol);
+    Q.sf = 1.0;
+    run_sweep(T, Q, b, slot, mu, 0, 0.0);                  // (the three calls of debug_newton, delta_w = 0)
+    fail = run_backward(T, Q, b, slot, mu, 0.0);
+    run_forward(T, Q, b, slot, mu, 0.0);
+  }
+  for (int i = T.tid; i < A.sn_nsel; i += T.nt) {
+    const double v = fail ? NAN : Q.dx[A.sn_sel[i]];
+    D[i] = v;
+    if (!(fabs(v) < INFINITY)) A.sn_ok[q] = 0;              // (every writer stores the same value)
+  }
+  if (fail && T.tid == 0) A.sn_ok[q] = 0;
+  if (r == 0) {
+    // size of the direction at the point itself, over the variables that appear in the problem (dummy_idx: the others)
+    double m[1] = {0.0};
+    if (!fail) {
+      for (int g = T.tid; g < nX; g += T.nt) Q.dx_sv[g] = 1.0;
+      T.sync();
+      for (int i = T.tid; i < A.n_dummy; i += T.nt) Q.dx_sv[A.dummy_idx[i]] = 0.0;
+      T.sync();
+      for (int g = T.tid; g < nX; g += T.nt) if (Q.dx_sv[g] != 0.0) m[0] = fmax(m[0], fabs(Q.dx[g]));
+    }
+    const int ops[1] = {R_MAX};
+    wg_reduce(T, m, ops);
+    if (T.tid == 0) A.sn_res[q] = fail ? NAN : m[0];
+  }
+  T.sync();
+}
+
+// Parameter rows of mode 3, element k of row b = q * R + r: the parameters of point q, entry j of the row plan moved by +-h.
+// row plan: (j, kind) per row - kind 0: the base row, 1: a parameter that enters linearly (+h, h = max(1, |p_j|)), 2 / -2: the plus /
+// minus row of a central pair (h = fd_step max(1, |p_j|)).  The rows exist in memory before the Newton kernel starts: its phases read
+// them through scalar loads.
+DOMPC_HD inline double sens_step(int lin, double fd_step, double pj) { return (lin ? 1.0 : fd_step) * fmax(1.0, fabs(pj)); }
+DOMPC_DEV inline void sens_prep_item(const KArgs& A, int64_t it) {
+  const int np = A.n_opt_p;
+  const int64_t b = it / np;
+  const int k = (int)(it % np), q = (int)(b / A.sn_R), r = (int)(b % A.sn_R);
+  double v = A.sn_p[(int64_t)q * np + k];
+  const int j = A.sn_rows[2 * r], kind = A.sn_rows[2 * r + 1];
+  if (kind != 0 && j == k) {
+    const double h = sens_step(kind == 1, A.sn_fd_step, v);
+    v = kind < 0 ? v - h : v + h;
+  }
+  A.sn_prow[it] = v;
+  if (k == 0 && r == 0) A.sn_ok[q] = 1;
+}
+// S[q][i][c] from the directions: column plan (j, ip, im) per column - (D[ip] - D[0]) / h for im < 0, else (D[ip] - D[im]) / 2h
+DOMPC_DEV inline void sens_finish_item(const KArgs& A, int64_t it) {
+  const int nc = A.sn_ncols, ns = A.sn_nsel;
+  const int c = (int)(it % nc), i = (int)((it / nc) % ns), q = (int)(it / ((int64_t)nc * ns));
+  const int j = A.sn_cols[3 * c], ip = A.sn_cols[3 * c + 1], im = A.sn_cols[3 * c + 2];
+  const double* D = A.sn_D + (int64_t)q * A.sn_R * ns;
+  const double h = sens_step(im < 0, A.sn_fd_step, A.sn_p[(int64_t)q * A.n_opt_p + j]);
+  const double v = im < 0 ? (D[(int64_t)ip * ns + i] - D[i]) / h : (D[(int64_t)ip * ns + i] - D[(int64_t)im * ns + i]) / (2.0 * h);
+  A.sn_S[it] = A.sn_ok[q] ? v : NAN;
 }
 
 // number of doubles written per edge by the sweep kernel: [A|B] (NX*NA), c (NX), Qt (NA*NA), qv (NA)

@@ -90,6 +90,17 @@ struct KArgs {
   // error measures) then hit the L2 instead of streaming 2 x n_opt_x doubles per slot from HBM.  Every problem writes the same
   // values at its start; null = per-slot copies (DOMPC_SHARED_BOUNDS=0)
   double *lb_sh, *ub_sh;
+  // sensitivities (mode 3, dompc_sens_kernel and its two helpers; sens_newton in dompc_driver.h).  Work item b = q * sn_R + r.
+  const double *sn_x, *sn_lam, *sn_mu, *sn_p;   // the B points: [B][n_opt_x], [B][n_g], [B] (mu / obj_scaling; not > 0: member skipped), [B][n_opt_p]
+  const int32_t* sn_sel;                        // [sn_nsel] indices into opt_x of the entries of a direction that are kept
+  const int32_t* sn_rows;                       // [sn_R][2] row plan (j, kind): 0 base row, 1 linear +h, 2 / -2 plus / minus row of a central pair
+  const int32_t* sn_cols;                       // [sn_ncols][3] column plan (j, ip, im): rows of the plan that form column c, im < 0: linear
+  int32_t sn_nsel, sn_R, sn_ncols, sn_flags;    // sn_flags bit 0: active-set reduction with tolerance sn_tol
+  double sn_tol, sn_fd_step;
+  double* sn_prow;                              // [B sn_R][n_opt_p] parameter rows, written by the prepare kernel; KArgs::p points here
+  double* sn_D;                                 // [B sn_R][sn_nsel] selected entries of the directions
+  double *sn_S, *sn_res;                        // results: [B][sn_nsel][sn_ncols] sensitivities, [B] max |dx| of the base row
+  int32_t* sn_ok;                               // [B] 1: every direction of the point was computed
 };
 
 

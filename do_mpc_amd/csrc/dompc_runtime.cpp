@@ -50,6 +50,13 @@ struct dompc_handle : dompc_host::Context {
   int32_t* abort_word = nullptr;         // pinned host memory (device build) / plain word: stop request read by the kernel
   double watchdog_s = 600.0;
   int64_t n_exchanges = 0;                      // cross-rank exchanges served during the last sharded solve
+  // sensitivities (dompc_sens_batch_device): parameter rows and selected direction entries of a chunk of points; staging of the host twin
+  double* sn_work = nullptr;
+  int64_t sn_work_doubles = 0;
+  double *s_sn_mu = nullptr, *s_sn_S = nullptr, *s_sn_res = nullptr;
+  int32_t *s_sn_ok = nullptr, *s_sn_tab = nullptr;
+  int32_t sn_cap_batch = 0;
+  int64_t sn_cap_S = 0, sn_cap_tab = 0;
 #ifndef DOMPC_HOST_EMU
   // native RCCL collective (dlopen'ed): communicator of the sharded problem and its stream
   struct RcclUid { char internal[128]; };
@@ -63,6 +70,7 @@ struct dompc_handle : dompc_host::Context {
   hipStream_t rccl_stream = nullptr;
   hipModule_t module = nullptr, module_batch = nullptr;
   hipFunction_t fn_solve = nullptr, fn_info = nullptr, fn_solve_batch = nullptr;
+  hipFunction_t fn_sens = nullptr, fn_sens_batch = nullptr, fn_sens_prep = nullptr, fn_sens_finish = nullptr;     // looked up by the first sensitivity call
   hipStream_t shard_stream = nullptr;    // lowest priority: never shares a hardware queue with the collective's kernels
 #endif
 };
@@ -200,7 +208,7 @@ static int fit_block(const dompc_handle* h, int block) {
 }
 
 // `block` threads per workgroup (a multiple of 64): the LDS pool is sized for block/64 wavefronts
-static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* stream_v) {
+static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* stream_v, void* fn_other = nullptr) {
 #ifndef DOMPC_HOST_EMU
   hipStream_t st = (hipStream_t)stream_v;          // nullptr = HIP default stream
   if (dev_zero(h, A.work_counter, sizeof(int32_t), st)) return 1;
@@ -209,9 +217,10 @@ static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* s
   // (batch launches of the solver with one 64-thread workgroup per problem, not sharded, run the build of the kernels that is compiled for
   //  exactly that shape when it was loaded: build.py batch_only)
   hipFunction_t fn = (h->fn_solve_batch && (A.mode == 0 || A.mode == 2) && A.wide <= 1 && block == 64 && !h->sharded) ? h->fn_solve_batch : h->fn_solve;
+  if (fn_other) fn = (hipFunction_t)fn_other;      // (another entry of the code object with the same argument block and LDS pool: dompc_sens_kernel)
   return h->launch(fn, grid, block, (unsigned)(A.pool_doubles * sizeof(double)), st, &A, sizeof(A));
 #else
-  (void)h; (void)grid; (void)block; (void)stream_v;
+  (void)h; (void)grid; (void)block; (void)stream_v; (void)fn_other;
   dompc_hostemu_run(&A);
   return 0;
 #endif
@@ -878,6 +887,131 @@ extern "C" int dompc_newton_steps_at_solution(dompc_handle* h, int32_t B, const 
     rc |= h->d2h(dlam + (size_t)b0 * d.n_g, h->s_lamg, sizeof(double) * (size_t)nb * d.n_g);
     if (rc || h->sync()) return 1;
   }
+  return 0;
+}
+
+// Sensitivities at B points (dompc_ipm.h).  Three launches per chunk of points on `stream`: the parameter rows of the plan, the Newton
+// directions (work items points x rows, pulled from the device-wide counter by one workgroup per workspace slot), the difference quotients.
+// A chunk is as many points as the work buffer holds (rows of parameters and of selected direction entries).
+extern "C" int dompc_sens_batch_device(dompc_handle* h, int32_t B, const double* x, const double* lam_g, const double* mu, const double* p,
+                                       const double* lbx, const double* ubx, const double* lbg, const double* ubg, const int32_t* sel,
+                                       int32_t n_sel, const int32_t* row_plan, int32_t n_rows, const int32_t* col_plan, int32_t n_cols,
+                                       double fd_step, int32_t flags, double active_set_tol, double* S, double* residual_step,
+                                       int32_t* ok, void* stream) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  if (!x || !lam_g || !mu || !p || !lbx || !ubx || !lbg || !ubg || !sel || !row_plan || !col_plan || !S || !residual_step || !ok) { h->error = "null pointer"; return 1; }
+  if (n_sel < 1 || n_rows < 1 || n_cols < 1) { h->error = "dompc_sens_batch_device: empty selection or plan"; return 1; }
+  if (h->set_device()) return 1;
+  if (h->sharded) { h->error = "dompc_sens_batch_device is not available on a sharded handle"; return 1; }
+  const dompc_problem_desc& d = h->d;
+#ifndef DOMPC_HOST_EMU
+  if (!h->fn_sens) {
+    hipFunction_t f0 = nullptr, f1 = nullptr, f2 = nullptr;
+    if (hipModuleGetFunction(&f0, h->module, "dompc_sens_kernel") != hipSuccess || hipModuleGetFunction(&f1, h->module, "dompc_sens_prep_kernel") != hipSuccess ||
+        hipModuleGetFunction(&f2, h->module, "dompc_sens_finish_kernel") != hipSuccess) {
+      h->error = "code object lacks the sensitivity kernels: " + h->code_path;
+      return 1;
+    }
+    h->fn_sens_prep = f1; h->fn_sens_finish = f2;
+    if (h->fn_solve_batch && hipModuleGetFunction(&h->fn_sens_batch, h->module_batch, "dompc_sens_kernel") != hipSuccess) h->fn_sens_batch = nullptr;
+    h->fn_sens = f0;
+  }
+#endif
+  // work buffer: per point n_rows x (n_opt_p + n_sel) doubles; at most 32 Mi doubles (256 MiB) unless one point needs more
+  const int64_t per_point = (int64_t)n_rows * (d.n_opt_p + n_sel);
+  const int64_t cap_doubles = (int64_t)32 << 20;
+  int64_t chunk = cap_doubles / per_point;
+  if (chunk < 1) chunk = 1;
+  if (chunk > B) chunk = B;
+  if ((int64_t)chunk * n_rows > (int64_t)1 << 30) chunk = ((int64_t)1 << 30) / n_rows;      // (work items are 32-bit)
+  if (chunk * per_point > h->sn_work_doubles) {
+    double* old = h->sn_work;
+    h->sn_work = nullptr; h->sn_work_doubles = 0;
+    h->release(old);
+    if (h->alloc((void**)&h->sn_work, sizeof(double) * (size_t)(chunk * per_point))) return 1;
+    h->sn_work_doubles = chunk * per_point;
+  }
+  for (int64_t q0 = 0; q0 < B; q0 += chunk) {
+    const int nq = (int)(B - q0 < chunk ? B - q0 : chunk);
+    dompc::KArgs A = h->base;
+    A.lb_sh = A.ub_sh = nullptr;           // per-slot bounds: with the active-set reduction every point has its own
+    A.lbx = lbx; A.ubx = ubx; A.lbg = lbg; A.ubg = ubg;
+    A.sn_x = x + q0 * d.n_opt_x; A.sn_lam = lam_g + q0 * d.n_g; A.sn_mu = mu + q0; A.sn_p = p + q0 * d.n_opt_p;
+    A.sn_sel = sel; A.sn_nsel = n_sel; A.sn_rows = row_plan; A.sn_R = n_rows; A.sn_cols = col_plan; A.sn_ncols = n_cols;
+    A.sn_flags = flags; A.sn_tol = active_set_tol; A.sn_fd_step = fd_step;
+    A.sn_prow = h->sn_work; A.sn_D = h->sn_work + (int64_t)nq * n_rows * d.n_opt_p;
+    A.p = A.sn_prow;
+    A.sn_S = S + q0 * n_sel * n_cols; A.sn_res = residual_step + q0; A.sn_ok = ok + q0;
+    A.batch = nq * n_rows; A.mode = 3; A.wide = 1; A.wide_spread = 0;
+    const int block = fit_block(h, h->block_auto ? (A.batch >= BATCH_ONE_WAVE ? 64 : 256) : h->block);
+    const int cap = (h->block_auto && block != 64 && h->slots256 < h->n_slots) ? h->slots256 : h->n_slots;
+    const int grid = A.batch < cap ? A.batch : cap;
+#ifndef DOMPC_HOST_EMU
+    hipStream_t st = (hipStream_t)stream;
+    auto blocks_for = [](int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g)); };
+    if (h->launch(h->fn_sens_prep, blocks_for((int64_t)A.batch * d.n_opt_p), 256, 0, st, &A, sizeof(A))) return 1;
+    if (launch(h, A, grid, block, stream, (void*)((block == 64 && h->fn_sens_batch) ? h->fn_sens_batch : h->fn_sens))) return 1;
+    if (h->launch(h->fn_sens_finish, blocks_for((int64_t)nq * n_sel * n_cols), 256, 0, st, &A, sizeof(A))) return 1;
+#else
+    if (launch(h, A, grid, block, stream)) return 1;
+#endif
+  }
+  return 0;
+}
+
+// host-pointer twin: stages the points through the staging buffers of the solver and waits for the result
+extern "C" int dompc_sens_batch(dompc_handle* h, int32_t B, const double* x, const double* lam_g, const double* mu, const double* p,
+                                const double* lbx, const double* ubx, const double* lbg, const double* ubg, const int32_t* sel,
+                                int32_t n_sel, const int32_t* row_plan, int32_t n_rows, const int32_t* col_plan, int32_t n_cols,
+                                double fd_step, int32_t flags, double active_set_tol, double* S, double* residual_step, int32_t* ok) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  if (!x || !lam_g || !mu || !p || !lbx || !ubx || !lbg || !ubg || !sel || !row_plan || !col_plan || !S || !residual_step || !ok) { h->error = "null pointer"; return 1; }
+  if (n_sel < 1 || n_rows < 1 || n_cols < 1) { h->error = "dompc_sens_batch: empty selection or plan"; return 1; }
+  if (h->set_device()) return 1;
+  if (h->sharded) { h->error = "dompc_sens_batch is not available on a sharded handle"; return 1; }
+  const dompc_problem_desc& d = h->d;
+  const size_t D = sizeof(double);
+  if (ensure_staging(h, B)) return 1;
+  if (B > h->sn_cap_batch) {
+    if (h->sync()) return 1;
+    if (h->grow_staging(&h->sn_cap_batch, B, {{(void**)&h->s_sn_mu, D}, {(void**)&h->s_sn_res, D}, {(void**)&h->s_sn_ok, sizeof(int32_t)}})) return 1;
+  }
+  const int64_t nS = (int64_t)B * n_sel * n_cols, nT = (int64_t)n_sel + 2 * (int64_t)n_rows + 3 * (int64_t)n_cols;
+  if (nS > h->sn_cap_S) {
+    if (h->sync()) return 1;
+    double* old = h->s_sn_S; h->s_sn_S = nullptr; h->sn_cap_S = 0; h->release(old);
+    if (h->alloc((void**)&h->s_sn_S, D * (size_t)nS)) return 1;
+    h->sn_cap_S = nS;
+  }
+  if (nT > h->sn_cap_tab) {
+    if (h->sync()) return 1;
+    int32_t* old = h->s_sn_tab; h->s_sn_tab = nullptr; h->sn_cap_tab = 0; h->release(old);
+    if (h->alloc((void**)&h->s_sn_tab, sizeof(int32_t) * (size_t)nT)) return 1;
+    h->sn_cap_tab = nT;
+  }
+  int32_t* t_sel = h->s_sn_tab, *t_rows = t_sel + n_sel, *t_cols = t_rows + 2 * n_rows;
+  int rc = 0;
+  rc |= h->h2d(h->s_x, x, D * (size_t)B * d.n_opt_x);
+  rc |= h->h2d(h->s_lamg, lam_g, D * (size_t)B * d.n_g);
+  rc |= h->h2d(h->s_sn_mu, mu, D * (size_t)B);
+  rc |= h->h2d(h->s_p, p, D * (size_t)B * d.n_opt_p);
+  rc |= h->h2d(h->s_lbx, lbx, D * d.n_opt_x);
+  rc |= h->h2d(h->s_ubx, ubx, D * d.n_opt_x);
+  rc |= h->h2d(h->s_lbg, lbg, D * d.n_g);
+  rc |= h->h2d(h->s_ubg, ubg, D * d.n_g);
+  rc |= h->h2d(t_sel, sel, sizeof(int32_t) * (size_t)n_sel);
+  rc |= h->h2d(t_rows, row_plan, sizeof(int32_t) * 2 * (size_t)n_rows);
+  rc |= h->h2d(t_cols, col_plan, sizeof(int32_t) * 3 * (size_t)n_cols);
+  if (rc) return 1;
+  if (dompc_sens_batch_device(h, B, h->s_x, h->s_lamg, h->s_sn_mu, h->s_p, h->s_lbx, h->s_ubx, h->s_lbg, h->s_ubg, t_sel, n_sel, t_rows, n_rows,
+                              t_cols, n_cols, fd_step, flags, active_set_tol, h->s_sn_S, h->s_sn_res, h->s_sn_ok, h->stream_ptr()))
+    return 1;
+  rc |= h->d2h(S, h->s_sn_S, D * (size_t)nS);
+  rc |= h->d2h(residual_step, h->s_sn_res, D * (size_t)B);
+  rc |= h->d2h(ok, h->s_sn_ok, sizeof(int32_t) * (size_t)B);
+  if (rc || h->sync()) return 1;
   return 0;
 }
 

@@ -167,6 +167,7 @@ class DoMPCDifferentiator:
                                       "own KKT system has the internal row layout, solver.RowMappedSolver)")
         self.optimizer = optimizer
         self.settings = NLPDifferentiatorSettings(**kwargs)
+        self._asked = set(kwargs)
         ps = optimizer.structure
         if getattr(ps, "eps_global", False):
             raise NotImplementedError("structured HIP backend: DoMPCDifferentiator with nl_cons_single_slack (the Newton steps at the "
@@ -353,6 +354,114 @@ class DoMPCDifferentiator:
         dxdp *= self.x_scaling_factors[:, None]                    # _nlpdifferentiator.py:851-853
         self.sens_num["dxdp"] = dxdp
         return dxdp.view(_Sens), dldp.view(_Sens)
+
+
+    # ------------------------------------------------------------------------------------------------ batch
+    def _keys(self, keys, default):
+        """one key (a tuple that starts with a name, or indexf[...]) or a list of them -> list of power-index tuples"""
+        if keys is None:
+            return list(default)
+        if isinstance(keys, _IndexF):
+            return [keys.key]
+        if isinstance(keys, tuple) and keys and isinstance(keys[0], str):
+            return [keys]
+        return [k.key if isinstance(k, _IndexF) else (tuple(k) if isinstance(k, (tuple, list)) else (k,)) for k in keys]
+
+    def _batch_plan(self, rows, cols):
+        """(sel, columns, row plan, column plan) of a batched call - the plan of `differentiate()` restricted to the wanted columns:
+        the base row, one row per column that enters linearly, a central pair for the others (include/dompc_ipm.h)"""
+        mpc = self.optimizer
+        default = rows is None and cols is None
+        rk = self._keys(rows, [("_u", 0, 0)])
+        ck = self._keys(cols, [("_x0",), ("_u_prev",)])
+        cache = self.__dict__.setdefault("_plans", {})
+        key = (tuple(rk), tuple(ck))
+        if key not in cache:
+            sel = np.concatenate([mpc._opt_x_layout.resolve(k).ravel() for k in rk]).astype(np.int32)
+            col = np.concatenate([mpc._opt_p_layout.resolve(k).ravel() for k in ck]).astype(np.int32)
+            if sel.size == 0 or col.size == 0:
+                raise ValueError("differentiate_batch: empty selection of rows or columns")
+            row_plan, col_plan = [(0, 0)], []
+            for j in col:
+                if self._linear[j]:
+                    col_plan.append((j, len(row_plan), -1)); row_plan.append((j, 1))
+                else:
+                    col_plan.append((j, len(row_plan), len(row_plan) + 1)); row_plan.extend([(j, 2), (j, -2)])
+            cache[key] = (sel, col, np.array(row_plan, np.int32), np.array(col_plan, np.int32))
+        return cache[key] + (default,)
+
+    def _refuse_batch_checks(self):
+        for name in ("check_LICQ", "check_SC", "check_rank"):
+            if name == "check_SC" and "check_SC" not in self._asked:
+                continue        # (on by default for differentiate(): a batched call refuses it only when the constructor was asked for it)
+            if getattr(self.settings, name):
+                raise NotImplementedError("DoMPCDifferentiator.differentiate_batch: settings.%s is a per-point host check of "
+                                          "differentiate() and is not available for a batch" % name)
+
+    def differentiate_batch(self, result, rows=None, cols=None) -> dict:
+        """Sensitivities of B solutions in one device call (`dompc_sens_batch`).  `result`: what `MPC.make_step_batch` returned (x,
+        lam_g, stats, p).  rows: key(s) into opt_x (default ("_u", 0, 0)), cols: key(s) into opt_p (default _x0 and _u_prev); a key
+        is a tuple like ("_x", 1, 0, -1) or indexf[...], several keys go in a list.  Returns dxdp [B, n_rows, n_cols] (rows in
+        unscaled variables like `sens_num`), with the defaults also du0dx0 [B, n_u, n_x] and du0du_prev [B, n_u, n_u], residual_step [B]
+        (max |Newton direction| at the point the directions were taken at: with active_set_reduction the reduced one) and ok [B]: False -
+        and NaN rows - for a member whose solve did not succeed, whose point is not strictly inside its relaxed bounds or whose KKT
+        matrix has the wrong inertia.  No exception for single members."""
+        self._refuse_batch_checks()
+        mpc = self.optimizer
+        sel, col, row_plan, col_plan, default = self._batch_plan(rows, cols)
+        st = result["stats"]
+        success = np.asarray(st["success"]) != 0
+        with np.errstate(divide="ignore", invalid="ignore"):
+            mu = np.where(success, np.asarray(st["mu"], float) / np.asarray(st["obj_scaling"], float), np.nan)
+        cfg = self.settings
+        S, res, ok = mpc.S.sens_batch(result["x"], result["lam_g"], mu, result["p"], mpc._lb_opt_x.master, mpc._ub_opt_x.master,
+                                      mpc._nlp_cons_lb, mpc._nlp_cons_ub, sel, row_plan, col_plan, cfg.fd_step,
+                                      reduce=cfg.active_set_reduction, active_set_tol=cfg.active_set_tol)
+        S *= self.x_scaling_factors[sel][None, :, None]                    # _nlpdifferentiator.py:851-853
+        out = {"dxdp": S, "residual_step": res, "ok": (ok != 0) & success}
+        if default:
+            nx = mpc.structure.nx
+            out["du0dx0"], out["du0du_prev"] = S[:, :, :nx], S[:, :, nx:]
+        return out
+
+    def differentiate_batch_device(self, x, lam_g, stats, p, rows=None, cols=None, out=None) -> dict:
+        """`differentiate_batch` on tensors that live where the solver runs (torch, float64; `stats`: the uint8 tensor of B dompc_stats
+        records `solve_batch_device` filled) - no host copies, asynchronous on the current stream.  Returns tensors dxdp [B, n_rows,
+        n_cols], residual_step [B], ok [B] (bool); `out`: a dict of such tensors from an earlier call to write into."""
+        import torch
+        from .solver import STATS_DTYPE
+        self._refuse_batch_checks()
+        mpc = self.optimizer
+        sel, col, row_plan, col_plan, default = self._batch_plan(rows, cols)
+        dev = x.device
+        B = int(x.shape[0])
+        res_ = self.__dict__.setdefault("_resident", {})
+        key = (str(dev), id(sel))
+        if key not in res_:
+            up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(a, dtype=dt)).to(dev)      # noqa: E731
+            res_[key] = dict(sel=up(sel, np.int32), rows=up(row_plan, np.int32), cols=up(col_plan, np.int32),
+                             scale=up(self.x_scaling_factors[sel], np.float64).reshape(1, -1, 1),
+                             lbx=up(mpc._lb_opt_x.master, np.float64), ubx=up(mpc._ub_opt_x.master, np.float64),
+                             lbg=up(mpc._nlp_cons_lb, np.float64), ubg=up(mpc._nlp_cons_ub, np.float64))
+        r = res_[key]
+        nd_ = STATS_DTYPE.itemsize // 8
+        sd = stats.view(torch.float64).reshape(B, nd_)
+        success = stats.view(torch.int32).reshape(B, 2 * nd_)[:, STATS_DTYPE.fields["success"][1] // 4] != 0
+        mu = torch.where(success, sd[:, STATS_DTYPE.fields["mu"][1] // 8] / sd[:, STATS_DTYPE.fields["obj_scaling"][1] // 8],
+                         torch.full((), float("nan"), dtype=torch.float64, device=dev)).contiguous()
+        if out is None:
+            out = {"dxdp": torch.empty((B, sel.size, col.size), dtype=torch.float64, device=dev),
+                   "residual_step": torch.empty(B, dtype=torch.float64, device=dev), "_ok": torch.empty(B, dtype=torch.int32, device=dev)}
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        cfg = self.settings
+        mpc.S.sens_batch_device(B, x.data_ptr(), lam_g.data_ptr(), mu.data_ptr(), p.data_ptr(), r["lbx"].data_ptr(), r["ubx"].data_ptr(),
+                                r["lbg"].data_ptr(), r["ubg"].data_ptr(), r["sel"].data_ptr(), sel.size, r["rows"].data_ptr(),
+                                row_plan.shape[0], r["cols"].data_ptr(), col_plan.shape[0], cfg.fd_step, cfg.active_set_reduction,
+                                cfg.active_set_tol, out["dxdp"].data_ptr(), out["residual_step"].data_ptr(), out["_ok"].data_ptr(), stream=stream)
+        out["dxdp"].mul_(r["scale"])
+        out["ok"] = (out["_ok"] != 0) & success
+        out["_keep"] = mu                      # (the launch is asynchronous: its inputs stay alive with the result)
+        return out
 
 
 class NLPDifferentiator:

@@ -24,10 +24,12 @@ def sampling_plan_box(lbx, ubx, lbu, ubu, n_samples: int, seed: Optional[int] = 
             "u_prev": rng.uniform(lbu, ubu, size=(n_samples, lbu.size))}
 
 
-def open_loop_samples(mpc, plan: Dict[str, np.ndarray], chunk: Optional[int] = None) -> Dict[str, np.ndarray]:
+def open_loop_samples(mpc, plan: Dict[str, np.ndarray], chunk: Optional[int] = None, sensitivities: bool = False) -> Dict[str, np.ndarray]:
     """One cold `make_step` per entry of the plan, all entries of a chunk in one launch.  Returns the columns of the
     reference's result table (_ampc_sampler.py:322-345): x0, u_prev, u0, status (= solver success), iter_count,
-    t_wall (kernel time of the launch divided by its samples), t_make_step (host wall time likewise)."""
+    t_wall (kernel time of the launch divided by its samples), t_make_step (host wall time likewise).
+    sensitivities=True: also du0dx0 [n, n_u, n_x] and du0du_prev [n, n_u, n_u] of every sample (`differentiate_batch`; NaN where the
+    solve or the differentiation of a sample failed)."""
     X0 = np.asarray(plan["x0"], float)
     UP = np.asarray(plan["u_prev"], float)
     n = X0.shape[0]
@@ -38,10 +40,13 @@ def open_loop_samples(mpc, plan: Dict[str, np.ndarray], chunk: Optional[int] = N
     for lo in range(0, n, chunk):
         hi = min(n, lo + chunk)
         t0 = time.perf_counter()
-        r = mpc.make_step_batch(X0[lo:hi], U_prev=UP[lo:hi])
+        r = mpc.make_step_batch(X0[lo:hi], U_prev=UP[lo:hi], **({"sensitivities": True} if sensitivities else {}))
         dt = time.perf_counter() - t0
         st = r["stats"]
         out["u0"][lo:hi] = r["u0"]
+        if sensitivities:
+            for k in ("du0dx0", "du0du_prev"):
+                out.setdefault(k, np.zeros((n,) + r[k].shape[1:]))[lo:hi] = r[k]
         out["status"][lo:hi] = st["success"] != 0
         out["iter_count"][lo:hi] = st["iter_count"]
         out["t_wall"][lo:hi] = float(np.max(st["t_wall_total"])) / (hi - lo)
@@ -406,6 +411,7 @@ class SamplerSettings:
     lbp: list = None
     ubp: list = None
     chunk: int = None                      # (addition) rows per launch; default: the controller's `max_batch`
+    store_sensitivities: bool = False      # (addition) open-loop sampling: du0dx0 and du0du_prev per row of the data files
 
     def check_for_mandatory_settings(self):
         if self.n_samples is None:
@@ -515,15 +521,22 @@ class AMPCSampler:
             x0, u_prev = x0.reshape(len(x0), -1), u_prev.reshape(len(u_prev), -1)
             out = []
             for lo, hi in self._chunks(len(x0)):
-                r = open_loop_samples(mpc, {"x0": x0[lo:hi], "u_prev": u_prev[lo:hi]})
-                out += [(r["u0"][i].reshape(-1, 1), {"t_make_step": float(r["t_make_step"][i]), "success": bool(r["status"][i]),
+                r = open_loop_samples(mpc, {"x0": x0[lo:hi], "u_prev": u_prev[lo:hi]}, sensitivities=sens)
+                rows = [(r["u0"][i].reshape(-1, 1), {"t_make_step": float(r["t_make_step"][i]), "success": bool(r["status"][i]),
                                                     "iter_count": int(r["iter_count"][i]), "t_wall_total": float(r["t_wall"][i])})
                         for i in range(hi - lo)]
+                if sens:
+                    rows = [row + ({"du0dx0": r["du0dx0"][i].copy(), "du0du_prev": r["du0du_prev"][i].copy()},) for i, row in enumerate(rows)]
+                out += rows
             return out
 
-        self._run(solve_rows, {"u0": lambda x: x[0], "status": lambda x: x[1]["success"],
-                               "t_make_step": lambda x: x[1]["t_make_step"], "t_wall": lambda x: x[1]["t_wall_total"],
-                               "iter_count": lambda x: x[1]["iter_count"]})
+        sens = bool(self._settings.store_sensitivities)
+        post = {"u0": lambda x: x[0], "status": lambda x: x[1]["success"],
+                "t_make_step": lambda x: x[1]["t_make_step"], "t_wall": lambda x: x[1]["t_wall_total"],
+                "iter_count": lambda x: x[1]["iter_count"]}
+        if sens:
+            post.update(du0dx0=lambda x: x[2]["du0dx0"], du0du_prev=lambda x: x[2]["du0du_prev"])
+        self._run(solve_rows, post)
 
     def approx_mpc_closed_loop_sampling(self):
         """_ampc_sampler.py:362-526: per row the closed-loop trajectory from (x0, u_prev); table columns x0 (states along the

@@ -112,6 +112,11 @@ def _load(lib_path: str) -> C.CDLL:
     lib.dompc_newton_step_at_solution.restype = C.c_int
     lib.dompc_newton_steps_at_solution.argtypes = [vp, C.c_int32] + [vp] * 9 + [C.c_double] + [vp] * 2
     lib.dompc_newton_steps_at_solution.restype = C.c_int
+    sens = [vp, C.c_int32] + [vp] * 9 + [C.c_int32, vp, C.c_int32, vp, C.c_int32, C.c_double, C.c_int32, C.c_double] + [vp] * 3
+    lib.dompc_sens_batch_device.argtypes = sens + [vp]
+    lib.dompc_sens_batch_device.restype = C.c_int
+    lib.dompc_sens_batch.argtypes = sens
+    lib.dompc_sens_batch.restype = C.c_int
     lib.dompc_debug_get_trace.argtypes = [vp, vp, C.c_int32]
     lib.dompc_debug_get_trace.restype = C.c_int
     lib.dompc_abort.argtypes = [vp, C.c_int32]
@@ -452,6 +457,36 @@ class HipIpmSolver:
         self._check(self._lib.dompc_newton_steps_at_solution(self._h, B, *[_ptr(v) for v in a], _ptr(P), float(mu), _ptr(dx), _ptr(dlam)))
         return dx, dlam
 
+    # ------------------------------------------------------------------ sensitivities at B points
+    def sens_batch(self, X, LG, MU, P, lbx, ubx, lbg, ubg, sel, row_plan, col_plan, fd_step, reduce=False, active_set_tol=1e-6):
+        """`dompc_sens_batch` (host arrays): S [B, n_sel, n_cols] in scaled variables, residual_step [B], ok [B] - include/dompc_ipm.h"""
+        ps = self.structure
+        X = np.ascontiguousarray(X, dtype=np.float64).reshape(-1, ps.n_opt_x)
+        B = X.shape[0]
+        LG = np.ascontiguousarray(LG, dtype=np.float64).reshape(B, ps.n_g)
+        MU = np.ascontiguousarray(MU, dtype=np.float64).reshape(B)
+        P = np.ascontiguousarray(P, dtype=np.float64).reshape(B, ps.n_opt_p)
+        lbx, ubx, lbg, ubg = _f64(lbx, ps.n_opt_x), _f64(ubx, ps.n_opt_x), _f64(lbg, ps.n_g), _f64(ubg, ps.n_g)
+        sel = np.ascontiguousarray(sel, dtype=np.int32).reshape(-1)
+        row_plan = np.ascontiguousarray(row_plan, dtype=np.int32).reshape(-1, 2)
+        col_plan = np.ascontiguousarray(col_plan, dtype=np.int32).reshape(-1, 3)
+        S = np.empty((B, sel.size, col_plan.shape[0]))
+        res = np.empty(B)
+        ok = np.zeros(B, dtype=np.int32)
+        self._check(self._lib.dompc_sens_batch(self._h, B, *[_ptr(v) for v in (X, LG, MU, P, lbx, ubx, lbg, ubg, sel)], sel.size,
+                                               _ptr(row_plan), row_plan.shape[0], _ptr(col_plan), col_plan.shape[0], float(fd_step),
+                                               1 if reduce else 0, float(active_set_tol), _ptr(S), _ptr(res), _ptr(ok)))
+        return S, res, ok
+
+    def sens_batch_device(self, B, x, lam_g, mu, p, lbx, ubx, lbg, ubg, sel, n_sel, row_plan, n_rows, col_plan, n_cols, fd_step, reduce,
+                          active_set_tol, S, residual_step, ok, stream=0):
+        """`dompc_sens_batch_device`: all array arguments are raw device addresses; asynchronous on `stream`."""
+        a = [C.c_void_p(int(v)) for v in (x, lam_g, mu, p, lbx, ubx, lbg, ubg, sel)]
+        self._check(self._lib.dompc_sens_batch_device(self._h, int(B), *a, int(n_sel), C.c_void_p(int(row_plan)), int(n_rows),
+                                                      C.c_void_p(int(col_plan)), int(n_cols), float(fd_step), 1 if reduce else 0,
+                                                      float(active_set_tol), C.c_void_p(int(S)), C.c_void_p(int(residual_step)),
+                                                      C.c_void_p(int(ok)), C.c_void_p(int(stream) if stream else None)))
+
     def debug_newton_step(self, x, lam_g, zl, zu, lbx, ubx, lbg, ubg, p, mu, delta_w=0.0):
         ps = self.structure
         a = [_f64(v) for v in (x, lam_g, zl, zu, lbx, ubx, lbg, ubg, p)]
@@ -488,7 +523,8 @@ class RowMappedSolver:
         self._runs = [(int(a), int(m[a]), int(b - a)) for a, b in zip(starts, ends)]      # (first reference row, first internal row, length)
 
     def __getattr__(self, name):
-        if name in ("solve_batch_device", "sweep_batch_device", "enable_sharding", "newton_step", "newton_steps_at_solution", "debug_newton_step"):
+        if name in ("solve_batch_device", "sweep_batch_device", "enable_sharding", "newton_step", "newton_steps_at_solution", "debug_newton_step", "sens_batch",
+                    "sens_batch_device"):
             raise NotImplementedError("structured HIP backend: %s with node-local rows appended to nlp_cons (internal row layout); "
                                       "use make_step / make_step_batch" % name)
         return getattr(self.inner, name)

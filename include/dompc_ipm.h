@@ -425,6 +425,32 @@ int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const doubl
 int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, int32_t clip_to_bounds,
                                  void* stream);
 
+/* ---- batched parametric sensitivities of the MPC solution (mode 3 of csrc/dompc_device.hip, sens_newton in csrc/dompc_driver.h):
+ * d x*[sel] / d p[cols] at B solutions of one problem class, from Newton directions of the solver's own structured KKT factorisation.
+ * The points are what dompc_solve_batch(_device) returned: x [B][n_opt_x], lam_g [B][n_g], mu [B] = stats.mu / stats.obj_scaling (a
+ * value that is not a positive finite number marks a member to skip, e.g. one whose solve did not succeed), p [B][n_opt_p] the
+ * parameters it was solved with; lbx / ubx / lbg / ubg one shared copy.  The bound multipliers are rebuilt as mu / distance to the
+ * bounds the solver relaxed.  flags bit 0: active-set reduction with active_set_tol (inactive bounds and nl_cons rows leave the
+ * system, active ones are held like equalities).
+ * sel [n_sel]: indices into opt_x of the wanted rows.  row_plan [n_rows][2] = (j, kind): the parameter rows a point is solved for -
+ * kind 0 the base row (must be row 0), 1: p_j + h with h = max(1, |p_j|) (a parameter that enters the optimality conditions
+ * linearly), 2 / -2: p_j + h / p_j - h with h = fd_step max(1, |p_j|).  col_plan [n_cols][3] = (j, ip, im): column c of the result is
+ * (D[ip] - D[0]) / h for im < 0 and (D[ip] - D[im]) / 2h otherwise, D[r] the direction of row r.
+ * Results: S [B][n_sel][n_cols] in the solver's scaled variables, residual_step [B] = max |dx| of the base row over the variables that
+ * appear in the problem, ok [B] = 1 when every direction of the point was computed; a point that is not strictly inside its relaxed
+ * bounds or a KKT matrix with the wrong inertia gives ok = 0 and NaN in S and residual_step.  Nothing of size n_opt_x leaves the GPU.
+ * All pointers of dompc_sens_batch_device are DEVICE addresses, the call is asynchronous on `stream`; dompc_sens_batch takes host
+ * pointers and returns when the results are there.  Not available on a sharded handle. */
+int dompc_sens_batch_device(dompc_handle* h, int32_t B, const double* x, const double* lam_g, const double* mu, const double* p,
+                            const double* lbx, const double* ubx, const double* lbg, const double* ubg, const int32_t* sel,
+                            int32_t n_sel, const int32_t* row_plan, int32_t n_rows, const int32_t* col_plan, int32_t n_cols,
+                            double fd_step, int32_t flags, double active_set_tol, double* S, double* residual_step, int32_t* ok,
+                            void* stream);
+int dompc_sens_batch(dompc_handle* h, int32_t B, const double* x, const double* lam_g, const double* mu, const double* p,
+                     const double* lbx, const double* ubx, const double* lbg, const double* ubg, const int32_t* sel,
+                     int32_t n_sel, const int32_t* row_plan, int32_t n_rows, const int32_t* col_plan, int32_t n_cols,
+                     double fd_step, int32_t flags, double active_set_tol, double* S, double* residual_step, int32_t* ok);
+
 #ifdef __cplusplus
 }
 #endif
