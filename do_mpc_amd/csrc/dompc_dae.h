@@ -579,7 +579,7 @@ DOMPC_PHASE int eval_edge_dae(const Thr& T, const Prob& Q, int e, double mu, int
         for (int c = 0; c < NW; ++c) rdn += Ld[DG_JDW + i * NW + c] * Wm(c, NA);       // the row in the reduced variables: + Jd_w w0
         S_[ES_RDN + i] = rdn;
         S_[ES_SIGS + i] = sigma_of(sv, l, u, Q.zsl[si], Q.zsu[si]);
-        S_[ES_RSN + i] = -yd[i] + bar_grad(sv, l, u, mu);
+        S_[ES_RSN + i] = -yd[i] + bar_grad(sv, l, u, mu, !(Q.soc & 2));
       }
       for (int q = 0; q < NSE; ++q) obj += Q.sf * DOMPC_EPS_PEN[q] * eps[q];
     }

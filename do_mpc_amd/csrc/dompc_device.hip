@@ -43,6 +43,11 @@ DOMPC_HD inline void model_info(const int32_t* in, int64_t* out) {
   out[17] = EL_SIZE;                                                       // LDS doubles per wavefront (edge / node working set)
   out[19] = QUAD_EDGE ? 4 : 1;                                             // edges per wavefront in the derivative sweep (4: dompc_quad.h)
   out[18] = (int64_t)DOMPC_SRC_DIGEST;                                     // digest of the kernel sources this object was compiled from (build.py)
+#ifndef DOMPC_HOST_EMU
+  out[20] = r16::ENABLED ? 1 : 0;                                          // backward Riccati pass: 1 = matrix-core tile (dompc_riccati16.h), 0 = generic
+#else
+  out[20] = 0;                                                             // (the host emulation always runs the generic recursion)
+#endif
 }
 }  // namespace dompc
 

@@ -176,16 +176,30 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
   // (singular0: every iteration is regularised and delta_w is known before its sweep - folded into the condensed blocks
   //  there, Prob::dsw, instead of W'W being formed on demand by the Riccati pass: that path costs as much as the pass)
   auto delta_after = [&](double last) { return last == 0.0 ? O.delta_w_0 : fmax(O.delta_w_min, O.kappa_w_minus * last); };
-  // ---- first sweep: gradient-based objective scaling and, for models without nl_cons rows, the least-squares estimate of
+  // ---- first sweep: gradient-based objective scaling and the least-squares estimate of
   // the constraint multipliers at the starting point (IPOPT section 3.6, option constr_mult_init_max):
   //     [I A'; A 0] (w, y) = -(grad f - z_L + z_U, 0),   y discarded if |y|_inf is above the limit.
   // The same structured solve as a Newton step, on a system in which the Hessian block is the identity: lambda = 0 (no
   // constraint curvature), objective Hessians left out (Prob::soc bit 1), z = 0 (no Sigma), delta = dsw = 1; the residual
   // is an input and zero (bit 0); the barrier gradient -mu/(x-l) + mu/(u-x) is the wanted -z_L + z_U = -1 + 1 when every
-  // finite bound is moved one unit away from the point and mu = 1.  (nl_cons rows: their slack variables would need the
-  // same treatment; IPOPT discards the estimate on the CSTR and kite examples anyway.)  The sweep of that solve is the one
-  // that delivers the gradient for the objective scaling, so the estimate costs two Riccati passes and no extra sweep.
-  const bool ls_init = NE == 0 && O.constr_mult_init_max > 0.0;
+  // finite bound is moved one unit away from the point and mu = 1.  The slack variables of the nl_cons rows get the same
+  // treatment (their block of the system is the identity as well: no Sigma_s, bounds one unit away from s; IPOPT discards
+  // the estimate on the CSTR and kite examples, not on every model with such rows).  Not with shared slack variables
+  // (EPS_GLOBAL: the Schur complement on top of the structured solve is not formed for this system) and not in estimators
+  // with nl_cons rows (FREE_ROOT: they start from lambda = 0 as before).  The sweep of that solve is the one that delivers
+  // the gradient for the objective scaling, so the estimate costs two Riccati passes and no extra sweep.
+  const bool ls_init = (NE == 0 || (!EPS_GLOBAL && !FREE_ROOT)) && O.constr_mult_init_max > 0.0;
+  auto ls_slacks = [&]() {
+    if (NE > 0) {
+      for (int si = T.tid; si < A.n_edges * NE1; si += T.nt) {
+        if (si % NE1 >= NE) continue;
+        if (Q.sl[si] > -INFINITY) Q.sl[si] = Q.s[si] - 1.0;
+        if (Q.su[si] < INFINITY) Q.su[si] = Q.s[si] + 1.0;
+        Q.zsl[si] = 0.0; Q.zsu[si] = 0.0;
+      }
+      T.sync();
+    }
+  };
   if (ls_init) {
     for (int g = T.tid; g < nX; g += T.nt) {
       if (Q.lb_own[g] > -INFINITY) Q.lb_own[g] = Q.x[g] - 1.0;
@@ -194,6 +208,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     }
     for (int r = T.tid; r < A.n_g; r += T.nt) Q.c[r] = 0.0;
     T.sync();
+    ls_slacks();
   }
   auto first_sweep = [&]() {
     ++n_sweeps;
@@ -303,6 +318,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     if (any[0] > 0.0) {
       T.sync();
       init_slacks(true);
+      if (ls_init) ls_slacks();
       bad = first_sweep();
     }
   }
@@ -341,6 +357,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
       Q.zl[g] = hl ? 1.0 : 0.0; Q.zu[g] = hu ? 1.0 : 0.0;
     }
     T.sync();
+    if (NE > 0) init_slacks(true);                       // (slack bounds and their multipliers likewise; s itself has not moved)
     bad = run_sweep(T, Q, b, slot, mu, 0, singular0 ? delta_after(0.0) : 0.0);
     ++n_sweeps;
   }

@@ -1529,7 +1529,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
           if (!Q.soc) Q.c[row0 + NW + NX + i] = rdn;
           S_[ES_RDN + i] = rdn;
           S_[ES_SIGS + i] = sigma_of(sv, l, u, Q.zsl[si], Q.zsu[si]);
-          S_[ES_RSN + i] = -yd[i] + bar_grad(sv, l, u, mu);
+          S_[ES_RSN + i] = -yd[i] + bar_grad(sv, l, u, mu, !(Q.soc & 2));
         }
         for (int q = 0; q < NSE; ++q) obj += Q.sf * DOMPC_EPS_PEN[q] * eps[q];
       }

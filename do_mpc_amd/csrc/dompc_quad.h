@@ -570,7 +570,7 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
           if (!soc) Q.c[pk.row0 + NW + NX + i] = rdn;
           S_[ES_RDN + i] = rdn;
           S_[ES_SIGS + i] = sigma_of(slv[i], sllv[i], sluv[i], zslv[i], zsuv[i]);
-          S_[ES_RSN + i] = -ydv[i] + bar_grad(slv[i], sllv[i], sluv[i], mu);
+          S_[ES_RSN + i] = -ydv[i] + bar_grad(slv[i], sllv[i], sluv[i], mu, !(Q.soc & 2));
         }
       }
     }

@@ -31,7 +31,7 @@ struct dompc_handle : dompc_host::Context {
   bool batch_object_stale = false;       // a `_batch` sibling exists but was built from other sources / another model: not used
   bool block_auto = true;          // threads per problem chosen per call from the batch size
   int32_t slots64 = 0, slots256 = 0;   // resident workgroups at 64 / 256 threads
-  int64_t ws_stride = 0, sweep_block = 0, el_size = 0, edges_per_wave = 1;
+  int64_t ws_stride = 0, sweep_block = 0, el_size = 0, edges_per_wave = 1, riccati_kind = 0;
   dompc::KArgs base;       // tables + workspace filled in, I/O pointers zero
   // staging for host-pointer calls
   double *s_x0 = nullptr, *s_lbx = nullptr, *s_ubx = nullptr, *s_lbg = nullptr, *s_ubg = nullptr, *s_p = nullptr;
@@ -274,7 +274,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   h->e_pad = ((d.n_edges + 15) / 16) * 16;
   // ---- model info from the code object
   int32_t in_h[5] = {d.n_opt_x, d.n_g, d.n_edges, h->e_pad, d.n_nodes};
-  int64_t info[20] = {0};
+  int64_t info[24] = {0};
   char hash[64] = {0};
 #ifndef DOMPC_HOST_EMU
   auto query_info = [&](hipFunction_t fn, int64_t* info_o, char* hash_o) -> int {
@@ -294,11 +294,11 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
     // sources and the same model (a handle with a small max_batch rebuilds only the general object after a kernel change;
     // a stale sibling with another KArgs layout would then be launched for every 64-thread batch).  A sibling that does not match is
     // not used - the general object runs those launches instead.
-    int64_t info_b[20] = {0};
+    int64_t info_b[24] = {0};
     char hash_b[64] = {0};
     hipFunction_t fn_info_b = nullptr;
     bool same = hipModuleGetFunction(&fn_info_b, h->module_batch, "dompc_model_info_kernel") == hipSuccess && !query_info(fn_info_b, info_b, hash_b);
-    for (int i = 0; same && i < 20; ++i) same = info_b[i] == info[i];
+    for (int i = 0; same && i < 24; ++i) same = info_b[i] == info[i];
     same = same && strncmp(hash, hash_b, 63) == 0;
     if (!same) {
       h->unload_module(h->module_batch);
@@ -319,6 +319,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   h->shard_capable = info[16] != 0;
   h->el_size = info[17];
   h->edges_per_wave = info[19] > 0 ? info[19] : 1;
+  h->riccati_kind = info[20];
   // ---- slots: one per workgroup the device can keep resident (occupancy of the solver kernel at this block size
   //      and LDS pool, times the number of CUs); more problems than slots are pulled from a work counter
   int max_batch = d.max_batch > 0 ? d.max_batch : 1;
@@ -624,6 +625,7 @@ static int serve_exchanges(dompc_handle* h, hipStream_t st) {
 extern "C" int64_t dompc_last_exchange_count(const dompc_handle* h) { return h ? h->n_exchanges : 0; }
 
 extern "C" int dompc_edges_per_wavefront(const dompc_handle* h) { return h ? (int)h->edges_per_wave : 0; }
+extern "C" int dompc_riccati_kind(const dompc_handle* h) { return h ? (int)h->riccati_kind : 0; }
 extern "C" int dompc_batch_object_state(const dompc_handle* h) {
   if (!h) return -1;
 #ifndef DOMPC_HOST_EMU

@@ -135,6 +135,8 @@ def _load(lib_path: str) -> C.CDLL:
     lib.dompc_batch_object_state.restype = C.c_int
     lib.dompc_edges_per_wavefront.argtypes = [vp]
     lib.dompc_edges_per_wavefront.restype = C.c_int
+    lib.dompc_riccati_kind.argtypes = [vp]
+    lib.dompc_riccati_kind.restype = C.c_int
     lib.dompc_rccl_unique_id.argtypes = [vp, C.c_char_p, vp]
     lib.dompc_rccl_unique_id.restype = C.c_int
     lib.dompc_rccl_init.argtypes = [vp, C.c_char_p, vp, C.c_int32, C.c_int32]
@@ -224,6 +226,7 @@ class HipIpmSolver:
         # 0: no launch-shape-specific sibling code object, 1: loaded, 2: found but stale (other sources / model) and therefore not used
         self.batch_object_state = int(self._lib.dompc_batch_object_state(h))
         self.edges_per_wavefront = int(self._lib.dompc_edges_per_wavefront(h))      # 4: quad sweep (csrc/dompc_quad.h)
+        self.riccati_kind = int(self._lib.dompc_riccati_kind(h))      # 1: matrix-core tile recursion (csrc/dompc_riccati16.h), 0: generic
         if self.batch_object_state == 2:
             import warnings
             warnings.warn("dompc: the `_batch` code object next to %s was built from other sources and is not used "

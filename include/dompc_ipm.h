@@ -250,6 +250,9 @@ int dompc_batch_object_state(const dompc_handle* h);
 /* edges a wavefront handles at a time in the derivative sweep of this model class: 4 = the quad sweep (csrc/dompc_quad.h: single finite
  * element, no nl_cons rows, at most 14 stage variables), 1 = the wavefront-per-edge paths */
 int dompc_edges_per_wavefront(const dompc_handle* h);
+/* backward Riccati pass of this model class as the code object reports it: 1 = the matrix-core recursion on one 16x16 tile per node
+ * (csrc/dompc_riccati16.h: at most 16 node variables, 4 decision variables and 4 nl_cons rows per node), 0 = the generic recursion */
+int dompc_riccati_kind(const dompc_handle* h);
 
 /* ---- batched plant integration ---------------------------------------------------------
  * Replaces the integrator object of do_mpc.simulator.Simulator (do_mpc/simulator.py:381-416:

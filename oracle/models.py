@@ -408,9 +408,56 @@ def case_dip(**over):
     return d
 
 
+SHAPE_FAMILY = {"s1": (1, 1, 0, 0), "s2": (3, 1, 0, 0), "s3": (5, 2, 1, 1), "s4": (6, 2, 2, 2), "s5": (8, 4, 0, 0),
+                "s6": (10, 2, 2, 1), "s7": (14, 1, 0, 0), "s8": (9, 4, 0, 0), "s9": (4, 2, 1, 4)}      # id -> (nx, nu, n_soft, n_hard)
+
+
+# ub_q of the family's rows = (value of the row at x0 with u = 0) + offset: 0.51 (soft) / 0.53 (hard) leave the row's input free to reach
+# its upper bound at the first stage (0.5 u <= offset) and the rows end active at later stages, where the states have risen; the two
+# members in which one input is shared by a soft and a hard row need the row that is to end active to be the tighter of the two
+SF_OFFSET = {(10, 2, 2, 1): (0.8, 0.51, 0.51), (4, 2, 1, 4): (0.4, 0.53, 0.53, 0.53, 0.53)}
+
+
+def case_shape_family(nx, nu, n_soft=0, n_hard=0, **over):
+    """The synthetic shape family of do_mpc_amd/examples/shape_family.py, restated here from its description.  NOT A PROBLEM OF THE
+    REFERENCE (nothing to cite): a ring of nx states, x_i' = -a_i x_i + b_i x_(i+1) + 0.1 p x_i x_(i-1) + (B u)_i, coefficients from
+    default_rng(nx * 100 + nu), p in {1, 1.2, 0.8}; tracking of 1.2 on every state, boxes, and the rows
+    x_q^2 + x_(q+1) + 0.5 u_(q mod nu) <= ub_q, the first n_soft soft (own slack, penalty 10), then n_hard hard ones."""
+    x = sp.symbols("x0:%d" % nx)
+    u = sp.symbols("u0:%d" % nu)
+    p = (sp.Symbol("p"),)
+    rng = np.random.default_rng(nx * 100 + nu)
+    a = rng.uniform(0.5, 1.5, nx)
+    b = rng.uniform(-0.5, 0.5, nx)
+    B = rng.uniform(0.3, 1.0, (nx, nu))
+    rhs = [-a[i] * x[i] + b[i] * x[(i + 1) % nx] + 0.1 * p[0] * x[i] * x[(i - 1) % nx] + sum(B[i, j] * u[j] for j in range(nu))
+           for i in range(nx)]
+    cost = sum((xi - 1.2) ** 2 for xi in x)
+    x0 = 0.5 + 0.3 * np.cos(np.arange(nx))
+    nl = []
+    off = SF_OFFSET.get((nx, nu, n_soft, n_hard), (0.51,) * n_soft + (0.53,) * n_hard)
+    for q in range(n_soft + n_hard):
+        at_x0 = x0[q % nx] ** 2 + x0[(q + 1) % nx]
+        expr = x[q % nx] ** 2 + x[(q + 1) % nx] + 0.5 * u[q % nu]
+        if q < n_soft:
+            nl.append(dict(name="row%d" % q, expr=expr, ub=float(at_x0 + off[q]), soft=True, penalty=10.0, max_violation=INF))
+        else:
+            nl.append(dict(name="row%d" % q, expr=expr, ub=float(at_x0 + off[q]), soft=False))
+    d = _base(name="shape_family", x=x, u=u, p=p, rhs=rhs, lterm=cost, mterm=cost, rterm=0.02 * np.ones(nu), n_horizon=4, n_robust=1,
+              t_step=0.2, x_lb=-2.0 * np.ones(nx), x_ub=2.0 * np.ones(nx), u_lb=-np.ones(nu), u_ub=np.ones(nu),
+              x_scaling=np.ones(nx), u_scaling=np.ones(nu), nl_cons=nl, uncertainty=dict(p=[1.0, 1.2, 0.8]), x0=x0, aux={})
+    d.update(over)
+    return d
+
+
+def _shape_member(mid):
+    return lambda **over: case_shape_family(*SHAPE_FAMILY[mid], **over)
+
+
 CASES = {"oscillating_masses_dae": case_oscillating_masses_dae, "dip": case_dip, "rotating_masses": case_rotating_masses, "industrial_poly": case_industrial_poly, "CSTR": case_CSTR,
          "batch_reactor": case_batch_reactor, "oscillating_masses": case_oscillating_masses,
          "kinematic_bicycle": case_kinematic_bicycle, "dynamic_bicycle": case_dynamic_bicycle, "kite": case_kite}
+CASES.update({"shape_family:" + mid: _shape_member(mid) for mid in SHAPE_FAMILY})
 
 
 def p_scenarios(case):

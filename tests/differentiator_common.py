@@ -24,7 +24,8 @@ def solved(make_mpc, name, **over):
 
 def oracle_sensitivity(mpc, name, cols, **over):
     """d opt_x / d opt_p[cols] (scaled variables) from a sparse LU of the oracle's KKT matrix at the product's solution,
-    for parameters that enter linearly (difference of two oracle Newton directions, exact)."""
+    for parameters that enter linearly (difference of two oracle Newton directions, exact).  Problems with nl_cons rows: the
+    slack formulation as one general sparse system (slack block Sigma_s, -I coupling to the inequality rows)."""
     nlp = pc.oracle_nlp(name, **over)
     nd = DoMPCDifferentiator(mpc)
     x, lam, zl, zu, lb, ub, mu = nd._point()
@@ -36,12 +37,41 @@ def oracle_sensitivity(mpc, name, cols, **over):
     pin = np.zeros(x.size)
     pin[dummy] = (sig[dummy] == 0)
     W, A = nlp.hess(x, p0, 1.0, lam), nlp.jac(x, p0)
-    K = sps.bmat([[W + sps.diags(sig + pin), A.T], [A, None]], format="csc")
+    if nlp.ne == 0:
+        K = sps.bmat([[W + sps.diags(sig + pin), A.T], [A, None]], format="csc")
+        slack_rows = None
+    else:
+        # nl_cons rows: one slack variable per row with lbg != ubg, d(x) - s = 0, as in parity_common.newton_reference - here by the
+        # rule of `dompc_newton_steps_at_solution` (csrc/dompc_driver.h: newton_slack_setup, at_solution): s = d(x) at the point,
+        # kept strictly inside the bounds the solver relaxed, multipliers mu / distance
+        opt = mpc.S.options
+        ineq = np.flatnonzero(nlp.lbg != nlp.ubg)
+        l, u = nlp.lbg[ineq], nlp.ubg[ineq]
+        sl, su = np.isfinite(l), np.isfinite(u)
+        l = np.where(sl, l - np.minimum(opt.constr_viol_tol, opt.bound_relax_factor * np.maximum(1.0, np.abs(np.where(sl, l, 0.0)))), l)
+        u = np.where(su, u + np.minimum(opt.constr_viol_tol, opt.bound_relax_factor * np.maximum(1.0, np.abs(np.where(su, u, 0.0)))), u)
+        s = nlp.g(x, p0)[ineq]
+        tiny = 1e-12 * np.maximum(1.0, np.abs(s))
+        s = np.where(sl, np.maximum(s, l + tiny), s)
+        s = np.where(su, np.minimum(s, u - tiny), s)
+        dsl, dsu = np.where(sl, s - l, 1.0), np.where(su, u - s, 1.0)
+        sig_s = sl * mu / dsl ** 2 + su * mu / dsu ** 2
+        E = sps.csr_matrix((np.ones(ineq.size), (ineq, np.arange(ineq.size))), shape=(nlp.n_g, ineq.size))
+        K = sps.bmat([[W + sps.diags(sig + pin), None, A.T], [None, sps.diags(sig_s), -E.T], [A, -E, None]], format="csc")
+        rs = -lam[ineq] - np.where(sl, mu / dsl, 0.0) + np.where(su, mu / dsu, 0.0)
+        rs = rs + pc.ipm.DEFAULTS["kappa_d"] * mu * ((sl & ~su).astype(float) - (su & ~sl).astype(float))
+        slack_rows = (ineq, s, rs)
     lu = spla.splu(K)
 
     def direction(p):
         rx = nlp.grad(x, p) + nlp.jac(x, p).T @ lam - np.where(hl, mu / dl, 0.0) + np.where(hu, mu / du, 0.0)
-        rhs = -np.concatenate([rx, nlp.g(x, p) - nlp.lbg])
+        if slack_rows is None:
+            rhs = -np.concatenate([rx, nlp.g(x, p) - nlp.lbg])
+        else:
+            ineq, s, rs = slack_rows
+            c = nlp.g(x, p) - np.where(nlp.lbg == nlp.ubg, nlp.lbg, 0.0)
+            c[ineq] -= s
+            rhs = -np.concatenate([rx, rs, c])
         sol = lu.solve(rhs)
         for _ in range(2):
             sol += lu.solve(rhs - K @ sol)

@@ -157,8 +157,8 @@ def check_against_oracle_solve(make_mpc, name, x0_scale=1.0, oracle_opts=None, *
     return mpc
 
 
-def check_same_iterates_as_oracle(make_mpc, name, oracle_opts=None, tol=1e-8, **over):
-    """Cold solve of golden step 0: the product and the oracle take the SAME iterations (count, every variable of the final
+def check_same_iterates_as_oracle(make_mpc, name, oracle_opts=None, tol=1e-8, x0=None, **over):
+    """Cold solve of golden step 0 (or from `x0`: cases without a golden): the product and the oracle take the SAME iterations (count, every variable of the final
     iterate incl. the unused ones, multipliers) - every algorithmic detail of the device driver against the restatement
     that is pinned to IPOPT's goldens.  industrial_poly is the case on which IPOPT keeps its least-squares multiplier
     estimate of the starting point (discarded on the others: max-norm above constr_mult_init_max).  CSTR: nl_cons rows,
@@ -166,14 +166,14 @@ def check_same_iterates_as_oracle(make_mpc, name, oracle_opts=None, tol=1e-8, **
     inertia count give the same iterates since the decoupled unused variables are left out of the test)."""
     mpc = make_mpc(name, **over)
     nlp = oracle_nlp(name, **over)
-    x0 = golden(name)["mpc._x"][0]
+    x0 = golden(name)["mpc._x"][0] if x0 is None else np.asarray(x0, float)
     mpc.x0 = x0
     mpc.set_initial_guess()
     mpc.make_step(x0)
     st = mpc.solver_stats
     r = ipm.solve(nlp, nlp.initial_guess(x0), mpc.opt_p_num.master.copy(), opts=oracle_opts)
     assert st["success"] and r["stats"]["success"]
-    assert st["iter_count"] == r["stats"]["iter_count"] and st["n_reg"] == r["stats"]["n_reg"]
+    assert st["iter_count"] == r["stats"]["iter_count"] and st["n_reg"] == r["stats"]["n_reg"], (st["iter_count"], r["stats"]["iter_count"], st["n_reg"], r["stats"]["n_reg"])
     used = np.ones(nlp.n_opt_x, bool)
     if name == "CSTR":     # (its one-sided unused slack slots end 6e-4 apart: the very first step sizes differ by 3e-5 relative;
         used[mpc.structure.tables["dummy_idx"]] = False      # every variable of the NLP proper agrees to 6e-15)
@@ -364,14 +364,14 @@ def check_big_tree_against_stored_oracle_solve(make_mpc, leaves, shard=None):
     return mpc
 
 
-def check_newton_step(make_mpc, name, oracle_iters=6, delta=0.0):
+def check_newton_step(make_mpc, name, oracle_iters=6, delta=0.0, step_tol=STEP_TOL, report=None):
     """One Newton direction of the structured solve (condensing + tree Riccati) against a general sparse
     LU of the same KKT system, at an interior iterate produced by the oracle.  delta > 0: the inertia-correction
-    path (delta_w on every primal variable, IPOPT's first diagonal block W + Sigma + delta I)."""
+    path (delta_w on every primal variable, IPOPT's first diagonal block W + Sigma + delta I).  Problems with nl_cons rows:
+    newton_reference states their slack variables (the rule of the kernel's debug entry point, see there)."""
     ex = CASES[name]
     mpc = make_mpc(name)
     nlp = oracle_nlp(name)
-    assert nlp.ne == 0, "equality-constrained cases only"
     p = nlp.opt_p(ex.X0, np.zeros(nlp.nu))
     r = ipm.solve(nlp, nlp.initial_guess(ex.X0), p, opts=dict(max_iter=oracle_iters))
     x, lam, mu = r["x"], r["lam_g"] * r["stats"]["obj_scaling"], r["stats"]["mu"]
@@ -379,17 +379,32 @@ def check_newton_step(make_mpc, name, oracle_iters=6, delta=0.0):
     hl, hu = np.isfinite(lb), np.isfinite(ub)
     lb[hl] -= 1e-8 * np.maximum(1, np.abs(lb[hl]))
     ub[hu] += 1e-8 * np.maximum(1, np.abs(ub[hu]))
-    check_newton_step_at(mpc, nlp, x, lam, lb, ub, mu, delta, p)
+    check_newton_step_at(mpc, nlp, x, lam, lb, ub, mu, delta, p, step_tol=step_tol, report=report)
+    return mpc
 
 
 def newton_reference(mpc, nlp, x, lam, lb, ub, mu, delta, p):
     """The KKT system of one Newton direction at (x, lam) in the box [lb, ub] with z_L, z_U = mu / distance, as the oracle states it:
-    dict(zl, zu, cv, rd, H, A, K, rhs, dx, dlam), the solution by a general sparse LU with three steps of refinement."""
+    dict(zl, zu, cv, rd, H, A, K, rhs, dx, dlam), the solution by a general sparse LU with three steps of refinement.
+
+    Problems with nl_cons rows (nlp.ne > 0): every row  lbg <= d(x) <= ubg  with lbg != ubg gets a slack variable s, d(x) - s = 0 and
+    lbg <= s <= ubg, and the system grows by one column and one row per slack - ONE general sparse system over (dx, ds, dlam),
+
+        [ W + Sigma_x + delta                        A'  ] [ dx   ]     [ r_x ]
+        [                   Sigma_s + delta         -E'  ] [ ds   ] = - [ r_s ]          (E: picks the inequality rows)
+        [ A                 -E                           ] [ dlam ]     [ c   ]
+
+    with r_s = -lam_E + the barrier gradient of s (damping term of one-sided bounds included) and c_E = d(x) - s.  delta sits on
+    the slacks too, as IPOPT's first diagonal block does.  `dompc_debug_newton_step` neither takes nor returns slack values or their
+    multipliers; it builds them by the rule of newton_slack_setup (csrc/dompc_driver.h) for a starting point, restated here:
+    s = d(x) pushed inside [lbg, ubg] by bound_push max(1, |bound|) - on two-sided rows at most bound_frac (ubg - lbg) - with
+    bound_push / bound_frac from the solver's options, and multipliers 1 on the finite sides (Sigma_s = 1 / distance per side).
+    The dict then also holds s, Sigma_s + delta (`sig_s`), r_s and the inequality rows `ineq`; `cv` and `dlam` include those rows."""
     hl, hu = np.isfinite(lb), np.isfinite(ub)
     dl, du = np.where(hl, x - lb, 1.0), np.where(hu, ub - x, 1.0)
     assert dl.min() > 0 and du.min() > 0
     zl, zu = np.where(hl, mu / dl, 0.0), np.where(hu, mu / du, 0.0)
-    W, A, gf, cv = nlp.hess(x, p, 1.0, lam), nlp.jac(x, p), nlp.grad(x, p), nlp.g(x, p) - nlp.lbg
+    W, A, gf = nlp.hess(x, p, 1.0, lam), nlp.jac(x, p), nlp.grad(x, p)
     sig = zl / dl * hl + zu / du * hu
     rx = gf + A.T @ lam - np.where(hl, mu / dl, 0.0) + np.where(hu, mu / du, 0.0)
     rx = rx + ipm.DEFAULTS["kappa_d"] * mu * ((hl & ~hu).astype(float) - (hu & ~hl).astype(float))   # damping of one-sided bounds
@@ -397,24 +412,66 @@ def newton_reference(mpc, nlp, x, lam, lb, ub, mu, delta, p):
     pin = np.zeros(x.size)
     pin[dummy] = (sig[dummy] == 0)
     H = (W + sps.diags(sig + pin + delta)).tocsc()
-    K = sps.bmat([[H, A.T], [A, None]], format="csc")
-    rhs = -np.concatenate([rx, cv])
+    if nlp.ne == 0:
+        cv = nlp.g(x, p) - nlp.lbg
+        K = sps.bmat([[H, A.T], [A, None]], format="csc")
+        rhs = -np.concatenate([rx, cv])
+        lu = spla.splu(K)
+        sol = lu.solve(rhs)
+        for _ in range(3):
+            sol += lu.solve(rhs - K @ sol)
+        return dict(zl=zl, zu=zu, cv=cv, rd=gf + A.T @ lam - zl + zu, H=H, A=A, K=K, rhs=rhs, dx=sol[:x.size], dlam=sol[x.size:])
+    lg, ug = np.asarray(nlp.lbg, float), np.asarray(nlp.ubg, float)
+    ineq = np.flatnonzero(lg != ug)
+    l, u = lg[ineq], ug[ineq]
+    sl, su = np.isfinite(l), np.isfinite(u)
+    opt = mpc.S.options
+    pl = np.where(sl, opt.bound_push * np.maximum(1.0, np.abs(np.where(sl, l, 0.0))), 0.0)
+    pu = np.where(su, opt.bound_push * np.maximum(1.0, np.abs(np.where(su, u, 0.0))), 0.0)
+    both = sl & su
+    pl[both] = np.minimum(pl[both], opt.bound_frac * (u[both] - l[both]))
+    pu[both] = np.minimum(pu[both], opt.bound_frac * (u[both] - l[both]))
+    gv = nlp.g(x, p)
+    s = gv[ineq].copy()
+    s[sl] = np.maximum(s[sl], (l + pl)[sl])
+    s[su] = np.minimum(s[su], (u - pu)[su])
+    dsl, dsu = np.where(sl, s - l, 1.0), np.where(su, u - s, 1.0)
+    assert dsl.min() > 0 and dsu.min() > 0
+    sig_s = sl / dsl + su / dsu + delta                                    # multipliers 1 on the finite sides
+    rs = -lam[ineq] - np.where(sl, mu / dsl, 0.0) + np.where(su, mu / dsu, 0.0)
+    rs = rs + ipm.DEFAULTS["kappa_d"] * mu * ((sl & ~su).astype(float) - (su & ~sl).astype(float))
+    cv = gv - np.where(lg == ug, lg, 0.0)
+    cv[ineq] -= s
+    n, m, k = x.size, nlp.n_g, ineq.size
+    E = sps.csr_matrix((np.ones(k), (ineq, np.arange(k))), shape=(m, k))
+    K = sps.bmat([[H, None, A.T], [None, sps.diags(sig_s), -E.T], [A, -E, None]], format="csc")
+    rhs = -np.concatenate([rx, rs, cv])
     lu = spla.splu(K)
     sol = lu.solve(rhs)
     for _ in range(3):
         sol += lu.solve(rhs - K @ sol)
-    return dict(zl=zl, zu=zu, cv=cv, rd=gf + A.T @ lam - zl + zu, H=H, A=A, K=K, rhs=rhs, dx=sol[:x.size], dlam=sol[x.size:])
+    return dict(zl=zl, zu=zu, cv=cv, rd=gf + A.T @ lam - zl + zu, H=H, A=A, K=K, rhs=rhs, dx=sol[:n], ds=sol[n:n + k], dlam=sol[n + k:],
+                s=s, sig_s=sig_s, rs=rs, ineq=ineq)
 
 
-def check_newton_step_at(mpc, nlp, x, lam, lb, ub, mu, delta, p, ref=None):
-    """the kernel's Newton direction (debug_newton_step) against newton_reference() of the same arguments; returns the kernel's dx"""
+def check_newton_step_at(mpc, nlp, x, lam, lb, ub, mu, delta, p, ref=None, step_tol=STEP_TOL, report=None):
+    """the kernel's Newton direction (debug_newton_step) against newton_reference() of the same arguments; returns the kernel's dx.
+    step_tol: bound on max |dx - dx_ref| / max |dx_ref| (never above STEP_TOL); report: a dict that receives the measured figures.
+    Problems with nl_cons rows: the kernel returns no slack step - the residual of the full system is formed with the ds that the
+    kernel's own dlam gives through the slack rows, (Sigma_s + delta) ds - dlam_E = -r_s; the rows A dx - ds = -c then test it."""
+    assert step_tol <= STEP_TOL
     ref = newton_reference(mpc, nlp, x, lam, lb, ub, mu, delta, p) if ref is None else ref
     dx, dlam, rd, c = mpc.S.debug_newton_step(x, lam, ref["zl"], ref["zu"], lb, ub, nlp.lbg, nlp.ubg, p, mu, delta)
     cv, dxo, K, rhs = ref["cv"], ref["dx"], ref["K"], ref["rhs"]
+    err_dx = np.max(np.abs(dx - dxo)) / max(1e-12, np.max(np.abs(dxo)))
+    sol = [dx, dlam] if "ineq" not in ref else [dx, (dlam[ref["ineq"]] - ref["rs"]) / ref["sig_s"], dlam]
+    res = K @ np.concatenate(sol) - rhs
+    if report is not None:
+        report.update(c=np.max(np.abs(c - cv)), rd=np.max(np.abs(rd - ref["rd"])), dx=err_dx, res=np.max(np.abs(res)),
+                      dlam=np.max(np.abs(dlam - ref["dlam"])) / max(1.0, np.max(np.abs(ref["dlam"]))))
     assert np.max(np.abs(c - cv)) < 1e-10 * max(1.0, np.max(np.abs(cv)))
     assert np.max(np.abs(rd - ref["rd"])) < 1e-9 * max(1.0, np.max(np.abs(rd)))
-    assert np.max(np.abs(dx - dxo)) < STEP_TOL * max(1e-12, np.max(np.abs(dxo))), np.max(np.abs(dx - dxo)) / np.max(np.abs(dxo))
-    res = K @ np.concatenate([dx, dlam]) - rhs
+    assert err_dx < step_tol, err_dx
     assert np.max(np.abs(res)) < 1e-7 * max(1.0, np.max(np.abs(rhs)))
     return dx
 

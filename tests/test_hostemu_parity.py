@@ -24,12 +24,12 @@ def test_golden_replay(name, steps):
 
 
 @pytest.mark.parametrize("name", ["oscillating_masses", "batch_reactor", "industrial_poly", "rotating_masses",
-                                  "oscillating_masses_dae"])
+                                  "oscillating_masses_dae", "CSTR"])      # (CSTR: nl_cons row and slack in the sparse reference)
 def test_newton_direction_matches_sparse_kkt_solve(name):
     pc.check_newton_step(make_mpc, name)
 
 
-@pytest.mark.parametrize("name", ["batch_reactor", "industrial_poly"])
+@pytest.mark.parametrize("name", ["batch_reactor", "industrial_poly", "CSTR"])
 def test_newton_direction_with_inertia_correction(name):
     """delta_w > 0: W'W and W'w0 of every edge are formed on demand from the stored W"""
     pc.check_newton_step(make_mpc, name, delta=0.05)
