@@ -1,0 +1,289 @@
+"""Sensitivity-based MPC for B loops: solve and differentiate every `resolve_every`-th step, in between continue the optimal input to
+first order in the state - on the device.
+
+The controller is the class ASMPC of the reference's examples/batch_reactor_differentiator
+(its examples/batch_reactor_differentiator/main.py:87-177):
+
+    u = (I - G)^-1 (u0 + J (x - x_prev) - G u0),      J = du0/dx0, G = du0/du_prev at the last solution (main.py:170-172).
+
+Since (I - G)^-1 (u0 - G u0) = u0 this is the affine state feedback u = u0 + M (x - x_prev), M = (I - G)^-1 J.  `solve` runs
+`MPC.make_step_batch` and `DoMPCDifferentiator.differentiate_batch` and hands their result to the law preparation of
+csrc/dompc_asmpc.hip, which forms M for every loop (Gauss-Jordan with partial pivoting on a row of 16 lanes); `make_step_batch` is one
+launch of the law step, u = sat(u_ref + M (x - x_ref)).  The law record lives on the device; `Simulator.rollout_affine_device` reads it
+to run K control steps law -> plant in one launch (closed_loop.BatchClosedLoopASMPC).
+
+Flags of the law [B]: bit 0 - the member's solve or sensitivities failed, or J / G is not finite; bit 1 - I - G is singular.  Either
+gives M = 0: the law holds u0, the input a plain MPC loop would have applied.  Status of a step [B]: bits 0 and 1 copied from the flags,
+bit 2 - an input was clipped to `mpc.bounds[..., '_u']`, bit 3 - max |x - x_ref| / x_scaling > settings.max_dx (it only flags; nothing
+re-solves by itself).
+
+There is no CPU fallback: without a HIP device the calls raise.  Limits of the kernels: n_x <= 64, n_u <= 16; larger models are refused
+by name, and so is everything `make_step_batch(..., sensitivities=True)` refuses.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from dataclasses import dataclass
+
+import numpy as np
+
+from . import _native, build, lowering
+from .differentiator import DoMPCDifferentiator
+
+
+@dataclass
+class ASMPCSettings:
+    resolve_every: int = 1               # solve and differentiate on every resolve_every-th step (make_step, BatchClosedLoopASMPC)
+    clip_to_bounds: bool = True          # clip the inputs to mpc.bounds[..., '_u'] (physical units; infinite bounds never clip)
+    max_dx: float = float("inf")         # infinity norm of (x - x_ref) / x_scaling beyond which a step is flagged (status bit 3)
+    active_set_reduction: bool = False   # handed to the differentiator
+
+
+class AffineLaw(C.Structure):
+    """dompc_affine_law of include/dompc_ipm.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("x_ref", "u_ref", "M", "flags", "lb", "ub", "x_scale")] + \
+               [("ld", C.c_int64), ("max_dx", C.c_double), ("clip", C.c_int32), ("pad", C.c_int32)]
+
+
+class ASMPCDesc(C.Structure):
+    _fields_ = [("nx", C.c_int32), ("nu", C.c_int32), ("code_object_path", C.c_char_p), ("model_hash", C.c_char_p), ("device", C.c_int32)]
+
+
+def _bind(lib_path: str) -> C.CDLL:
+    lib = C.CDLL(lib_path)
+    vp, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    lib.dompc_asmpc_create.argtypes = [C.POINTER(ASMPCDesc), C.POINTER(vp)]
+    lib.dompc_asmpc_destroy.argtypes = [vp]
+    lib.dompc_asmpc_destroy.restype = None
+    lib.dompc_asmpc_last_error.argtypes = [vp]
+    lib.dompc_asmpc_last_error.restype = C.c_char_p
+    lib.dompc_asmpc_set_options.argtypes = [vp, vp, vp, vp, i32, C.c_double]
+    lib.dompc_asmpc_prepare_device.argtypes = [vp, i32, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]
+    lib.dompc_asmpc_set_law.argtypes = [vp, i32, vp, vp, vp, vp, vp]
+    lib.dompc_asmpc_get_law.argtypes = [vp, vp, vp, vp, vp]
+    lib.dompc_asmpc_law_batch.argtypes = [vp]
+    lib.dompc_asmpc_law_batch.restype = i32
+    lib.dompc_asmpc_law.argtypes = [vp, C.POINTER(AffineLaw)]
+    lib.dompc_asmpc_step_batch.argtypes = [vp, i32, vp, vp, vp]
+    lib.dompc_asmpc_step_batch_device.argtypes = [vp, i32, vp, vp, vp, vp]
+    for name in ("create", "set_options", "prepare_device", "set_law", "get_law", "law", "step_batch", "step_batch_device"):
+        getattr(lib, "dompc_asmpc_" + name).restype = C.c_int
+    return lib
+
+
+def _ptr(a):
+    return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+class ASMPC:
+    def __init__(self, mpc, _lib_path=None, _code_object=None):
+        """TEST-ONLY: `_lib_path` (a path, or a callable (header, hash) -> path) with `_code_object=""` selects the host emulation of
+        the kernels."""
+        assert mpc.flags["setup"] is True, "MPC was not setup yet. Please call MPC.setup()."
+        self.mpc = mpc
+        self.settings = ASMPCSettings()
+        m = mpc.model
+        if getattr(mpc, "structure", None) is not None:                    # (a stand-in that carries sizes and bounds only: set_law and the law step)
+            DoMPCDifferentiator(mpc)                                       # refuses what make_step_batch(..., sensitivities=True) refuses
+        self.generated_header = lowering.lower_asmpc(m.n_x, m.n_u)         # refuses n_x > 64 and n_u > 16, by name
+        self.model_hash = self.generated_header.rsplit('ASMPC_MODEL_HASH "', 1)[1].split('"')[0]
+        self._emu = None
+        if _lib_path is not None:
+            assert _code_object == "", "a library of its own is the host emulation: _code_object must be \"\""
+            self._emu = _lib_path if callable(_lib_path) else (lambda header, model_hash: _lib_path)
+        self._lib = None
+        self._h = None
+        self._options = None             # what the handle's bounds, scaling, clip and max_dx were set from
+        self._nd = None                  # (solver, active_set_reduction, differentiator)
+        self._resident = {}              # device -> the solver's bounds and the input scaling as tensors (solve_device)
+        self._keep = None                # inputs of an asynchronous law preparation
+        self.last = None                 # result of the last solve()
+        self._k = 0                      # make_step: calls so far
+        self._u_data = [np.asarray(mpc.u0.master, dtype=float).reshape(-1, 1).copy()]
+
+    # ------------------------------------------------------------------ native side
+    def _handle(self):
+        """the runtime handle (created on first use) with the CURRENT options: bounds, scaling, clip and max_dx are uploaded again
+        when one of them changed since the last call"""
+        m, st = self.mpc.model, self.settings
+        if self._h is None:
+            if self._lib is None:
+                self._lib = _bind(self._emu(self.generated_header, self.model_hash) if self._emu else _native.runtime_library())
+            code_object = "" if self._emu else build.asmpc_code_object(self.generated_header, self.model_hash)
+            desc = ASMPCDesc(nx=m.n_x, nu=m.n_u, code_object_path=code_object.encode(), model_hash=self.model_hash.encode(),
+                             device=int(self.mpc.settings.gpu_index))
+            h = C.c_void_p()
+            _native.check(self._lib.dompc_asmpc_create(C.byref(desc), C.byref(h)), "dompc_asmpc_create failed: ", self._lib.dompc_asmpc_last_error)
+            self._h = h
+        if int(st.resolve_every) < 1:
+            raise ValueError("ASMPC.settings.resolve_every must be an integer >= 1")
+        lb, ub, xs = (np.ascontiguousarray(v.master, dtype=np.float64).reshape(-1) for v in (self.mpc._u_lb, self.mpc._u_ub, self.mpc._x_scaling))
+        key = (bool(st.clip_to_bounds), float(st.max_dx), lb.tobytes(), ub.tobytes(), xs.tobytes())
+        if key != self._options:
+            self._check(self._lib.dompc_asmpc_set_options(self._h, _ptr(lb), _ptr(ub), _ptr(xs), 1 if st.clip_to_bounds else 0, float(st.max_dx)))
+            self._options = key
+        return self._h
+
+    def _check(self, rc):
+        _native.check(rc, "dompc_asmpc: ", self._lib.dompc_asmpc_last_error, self._h)
+
+    def close(self):
+        if getattr(self, "_h", None) is not None:
+            self._lib.dompc_asmpc_destroy(self._h)
+            self._h = None
+            self._options = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _differentiator(self):
+        red = bool(self.settings.active_set_reduction)
+        if self._nd is None or self._nd[0] is not self.mpc.S or self._nd[1] != red:
+            self._nd = (self.mpc.S, red, DoMPCDifferentiator(self.mpc, active_set_reduction=red))
+        return self._nd[2]
+
+    # ------------------------------------------------------------------ solve: the expansion point and the law
+    def solve(self, X0, U_prev=None) -> dict:
+        """B cold solves at the states X0 [B][n_x] with their sensitivities (`MPC.make_step_batch(..., sensitivities=True)`; with
+        settings.active_set_reduction the differentiator runs with it), then the law preparation on the device.  Returns the solve's
+        result; it is the expansion point of `make_step_batch` from now on."""
+        if self.settings.active_set_reduction:
+            r = self.mpc.make_step_batch(X0, U_prev=U_prev)
+            r.update(self._differentiator().differentiate_batch(r))
+        else:
+            r = self.mpc.make_step_batch(X0, U_prev=U_prev, sensitivities=True)
+        self.set_law(r["p"][:, :self.mpc.model.n_x], r["u0"], r["du0dx0"], r["du0du_prev"], r["ok"])
+        self.last = r
+        return r
+
+    def solve_device(self, guess, P, sol, lam_g, f, stats) -> dict:
+        """`solve` on tensors that live where the solver runs (torch, float64; `stats`: uint8, B dompc_stats records): guess and sol
+        [B][n_opt_x], P [B][n_opt_p] (the states in its first n_x columns, u_prev in its last n_u), lam_g [B][n_g], f [B].  Chains
+        `solve_batch_device` -> `differentiate_batch_device` -> law preparation on the current stream; nothing is copied to the host.
+        Returns the tensors u0 [B][n_u] (physical units) and what differentiate_batch_device returns."""
+        import torch
+        mpc, ps = self.mpc, self.mpc.structure
+        h = self._handle()
+        dev = P.device
+        B = int(P.shape[0])
+        if str(dev) not in self._resident:
+            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
+            self._resident[str(dev)] = dict(lbx=up(mpc._lb_opt_x.master), ubx=up(mpc._ub_opt_x.master), lbg=up(mpc._nlp_cons_lb),
+                                            ubg=up(mpc._nlp_cons_ub), us=up(mpc._u_scaling.master))
+        r = self._resident[str(dev)]
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        mpc.S.solve_batch_device(B, guess.data_ptr(), r["lbx"].data_ptr(), r["ubx"].data_ptr(), r["lbg"].data_ptr(), r["ubg"].data_ptr(),
+                                 P.data_ptr(), sol.data_ptr(), 0, 0, lam_g.data_ptr(), f.data_ptr(), stats.data_ptr(), stream=stream)
+        out = self._differentiator().differentiate_batch_device(sol, lam_g, stats, P)
+        nx, nu, iu = ps.nx, ps.nu, ps.iu(0, 0)
+        u0 = torch.mul(sol[:, iu:iu + nu], r["us"])                     # u0 in physical units
+        x_prev = P[:, :nx].contiguous()
+        ok = out["ok"].to(torch.int32)
+        S = out["dxdp"]                                                 # [B][n_u][n_x + n_u]: J and G are views into it
+        assert S.is_contiguous() and tuple(S.shape) == (B, nu, nx + nu)
+        self._check(self._lib.dompc_asmpc_prepare_device(h, B, x_prev.data_ptr(), u0.data_ptr(), S.data_ptr(), nx + nu, nu * (nx + nu),
+                                                         S.data_ptr() + 8 * nx, nx + nu, nu * (nx + nu), ok.data_ptr(),
+                                                         C.c_void_p(int(stream) if stream else None)))
+        self._keep = (x_prev, u0, ok, out)                              # (the launch is asynchronous: its inputs stay alive)
+        out = dict(out)
+        out["u0"] = u0
+        return out
+
+    def set_law(self, x_prev, u0, du0dx0, du0du_prev, ok=None) -> None:
+        """The law from given host arrays: x_prev [B][n_x], u0 [B][n_u], du0dx0 [B][n_u][n_x], du0du_prev [B][n_u][n_u], ok [B] (default:
+        all True) - e.g. sensitivities stored by `AMPCSampler`."""
+        m = self.mpc.model
+        h = self._handle()
+        f = lambda a, *shape: np.ascontiguousarray(np.asarray(a, dtype=np.float64)).reshape(-1, *shape)      # noqa: E731
+        x_prev, u0, J, G = f(x_prev, m.n_x), f(u0, m.n_u), f(du0dx0, m.n_u, m.n_x), f(du0du_prev, m.n_u, m.n_u)
+        B = x_prev.shape[0]
+        if not (u0.shape[0] == J.shape[0] == G.shape[0] == B):
+            raise ValueError("ASMPC.set_law: x_prev, u0, du0dx0 and du0du_prev must have the same number of members")
+        okv = None if ok is None else np.ascontiguousarray(np.asarray(ok).reshape(B) != 0, dtype=np.int32)
+        self._check(self._lib.dompc_asmpc_set_law(h, B, _ptr(x_prev), _ptr(u0), _ptr(J), _ptr(G), _ptr(okv)))
+
+    @property
+    def batch(self) -> int:
+        """loops of the current law (0: none yet)"""
+        return int(self._lib.dompc_asmpc_law_batch(self._h)) if self._h is not None else 0
+
+    @property
+    def law(self) -> dict:
+        """the law record copied to the host: x_ref [B][n_x], u_ref [B][n_u], M [B][n_u][n_x], flags [B]"""
+        B = self.batch
+        if B <= 0:
+            raise RuntimeError("ASMPC.law: no solution to expand about (call solve or set_law first)")
+        m = self.mpc.model
+        out = {"x_ref": np.empty((B, m.n_x)), "u_ref": np.empty((B, m.n_u)), "M": np.empty((B, m.n_u, m.n_x)), "flags": np.zeros(B, dtype=np.int32)}
+        self._check(self._lib.dompc_asmpc_get_law(self._h, *[_ptr(out[k]) for k in ("x_ref", "u_ref", "M", "flags")]))
+        return out
+
+    def law_record(self) -> AffineLaw:
+        """the device-side record (dompc_affine_law) for `Simulator.rollout_affine_device`; valid until the next solve / set_law"""
+        self._handle()
+        rec = AffineLaw()
+        self._check(self._lib.dompc_asmpc_law(self._h, C.byref(rec)))
+        return rec
+
+    # ------------------------------------------------------------------ the law step
+    def make_step_batch(self, X):
+        """inputs U [B][n_u] for the states X [B][n_x] from the last solve, and the status [B] (bits: module docstring)"""
+        h = self._handle()
+        if self.batch <= 0:
+            raise RuntimeError("ASMPC.make_step_batch: no solution to expand about (call solve or set_law first)")
+        m = self.mpc.model
+        X = np.ascontiguousarray(np.asarray(X, dtype=np.float64)).reshape(-1, m.n_x)
+        B = X.shape[0]
+        U = np.empty((B, m.n_u))
+        status = np.zeros(B, dtype=np.int32)
+        self._check(self._lib.dompc_asmpc_step_batch(h, B, _ptr(X), _ptr(U), _ptr(status)))
+        return U, status
+
+    def make_step_batch_device(self, B, X_ptr, U_ptr, status_ptr=0, stream=0) -> None:
+        """make_step_batch on raw device addresses (ints, e.g. torch tensor .data_ptr()) of X [B][n_x] and U [B][n_u] (float64) and
+        status [B] (int32, or 0); asynchronous on `stream`"""
+        h = self._handle()
+        self._check(self._lib.dompc_asmpc_step_batch_device(h, int(B), C.c_void_p(int(X_ptr)), C.c_void_p(int(U_ptr)),
+                                                            C.c_void_p(int(status_ptr) if status_ptr else None),
+                                                            C.c_void_p(int(stream) if stream else None)))
+
+    # ------------------------------------------------------------------ one loop, the reference class's surface
+    def make_step(self, x0):
+        """One loop with the reference class's semantics: on every settings.resolve_every-th call (the first included) the controller
+        is solved at x0 - `mpc.make_step`, warm start and u_prev as in a plain MPC loop - and differentiated; otherwise the input is
+        the continuation from the last solve.  Returns the input as a column; `u_data` records every one."""
+        mpc, m = self.mpc, self.mpc.model
+        x0 = np.asarray(x0, dtype=float).reshape(-1, 1)
+        if self._k % int(self.settings.resolve_every) == 0:
+            u0 = mpc.make_step(x0)
+            if not mpc.solver_stats.get("success", False):
+                self.set_law(x0.ravel(), u0.ravel(), np.zeros((1, m.n_u, m.n_x)), np.zeros((1, m.n_u, m.n_u)), [False])
+            else:
+                nd = self._differentiator()
+                r = {"x": mpc.opt_x_num.master[None, :].copy(), "lam_g": np.asarray(mpc.lam_g_num, float).reshape(1, -1).copy(),
+                     "p": mpc.opt_p_num.master[None, :].copy(), "stats": self._stats_row()}
+                s = nd.differentiate_batch(r)
+                self.set_law(x0.ravel(), u0.ravel(), s["du0dx0"], s["du0du_prev"], s["ok"])
+        else:
+            mpc._t0 = mpc._t0 + mpc.settings.t_step               # (a control step without a solve: the controller's clock moves on)
+        u, _ = self.make_step_batch(x0.reshape(1, -1))
+        self._k += 1
+        u = u.reshape(-1, 1)
+        mpc._u0.master[:] = u.ravel()                             # u_prev of the next solve: the input that was applied
+        self._u_data.append(u.copy())
+        return u
+
+    def _stats_row(self):
+        from .solver import STATS_DTYPE
+        st = np.zeros(1, dtype=STATS_DTYPE)
+        s = self.mpc.solver_stats
+        st["success"], st["mu"], st["obj_scaling"] = 1, float(s["mu"]), float(s.get("obj_scaling", 1.0))
+        return st
+
+    @property
+    def u_data(self) -> np.ndarray:
+        """the inputs computed so far, one column each, after the controller's initial u0 (the reference's `u_data`)"""
+        return np.hstack(self._u_data)

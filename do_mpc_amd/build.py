@@ -106,7 +106,7 @@ def runtime_library(force: bool = False) -> str:
         cmd = [_hipcc(), "-O2", "-std=c++17", "-fPIC", "-shared", "-D__HIP_PLATFORM_AMD__",
                os.path.join(CSRC, "dompc_runtime.cpp"), os.path.join(CSRC, "dompc_plant_runtime.cpp"),
                os.path.join(CSRC, "dompc_ekf_runtime.cpp"), os.path.join(CSRC, "dompc_lqr_runtime.cpp"),
-               os.path.join(CSRC, "dompc_ampc_runtime.cpp"), "-ldl"]
+               os.path.join(CSRC, "dompc_ampc_runtime.cpp"), os.path.join(CSRC, "dompc_asmpc_runtime.cpp"), "-ldl"]
         _compile_to(cmd, out, "building libdompc_ipm.so")
         _write_atomic(stamp, dig)
     return out
@@ -235,3 +235,9 @@ def ampc_code_object(header_text: str, model_hash: str, force: bool = False, rem
     """gfx950 code object of the batched approximate-MPC step (csrc/dompc_ampc.hip) for one lowered network shape (sizes, activations,
     scaling; the weights are runtime data).  remarks=True: as ekf_code_object (profiles/ampc_resource_usage.txt)."""
     return _kernel_code_object("ampc", "dompc_ampc.hip", "DOMPC_AMPC_HEADER", "ampc_gen.h", "network", header_text, model_hash, force, remarks)
+
+
+def asmpc_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
+    """gfx950 code object of the sensitivity-based MPC law (csrc/dompc_asmpc.hip: law preparation and law step) for one pair of sizes
+    (n_x, n_u); no model in it, the law is runtime data.  remarks=True: as ekf_code_object (profiles/asmpc_resource_usage.txt)."""
+    return _kernel_code_object("asmpc", "dompc_asmpc.hip", "DOMPC_ASMPC_HEADER", "asmpc_gen.h", "law", header_text, model_hash, force, remarks)

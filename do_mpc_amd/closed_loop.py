@@ -543,3 +543,182 @@ class BatchClosedLoopAMPC:
             st.append(r["plant_status"])
         return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, self.B, self.sim.model.n_u)),
                 "plant_status": np.stack(st) if st else np.zeros((0, self.B), dtype=np.int32)}
+
+
+class BatchClosedLoopASMPC:
+    """B closed loops sensitivity-based MPC -> plant advancing together, everything resident in device memory (do_mpc_amd/asmpc.py).  On
+    every `asmpc.settings.resolve_every`-th control step the controller is solved at the current states - warm start, u_prev and the
+    _tvp / _p refresh exactly those of BatchClosedLoop.step -, differentiated and the law prepared (`ASMPC.solve_device`: three device
+    calls on one stream, no host copy); every step then applies the law u = sat(u_ref + M (x - x_ref)) and the plant step.  With
+    resolve_every = 1 this is the MPC loop (the law at x = x_ref adds an exact zero).  Between two solves the law needs nothing from the
+    host: `run(n, fused=True)` covers those steps with ONE launch each (`Simulator.rollout_affine_device`).
+    X0: [B][nx]; U_prev0: [B][nu], the inputs before the first step (default 0).  device: index of the HIP device, or "cpu" with a
+    controller, a law and a plant on the host emulation (tests).  State feedback: the plant's measurement must be its state."""
+
+    def __init__(self, asmpc, simulator, X0, U_prev0=None, device=0):
+        import torch
+        self.torch = torch
+        self.asmpc, self.sim = asmpc, simulator
+        mpc = self.mpc = asmpc.mpc
+        ps = self.ps = mpc.structure
+        if getattr(ps, "open_loop_stack", False):
+            raise NotImplementedError("structured HIP backend: the device-resident closed loop with open_loop and several scenarios")
+        if getattr(mpc.S, "row_mapped", False):
+            raise NotImplementedError("structured HIP backend: the device-resident closed loop with rows appended to nlp_cons")
+        m = simulator.model
+        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
+        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
+        X0 = np.asarray(X0, dtype=float).reshape(-1, ps.nx)
+        self.B = B = X0.shape[0]
+        dev = self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
+        t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)      # noqa: E731  (a copy, also on the host)
+        t0 = float(mpc._t0[0])
+        P = np.tile(mpc.opt_p_num.master, (B, 1))
+        P[:, :ps.nx] = X0
+        P[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(t0).master
+        P[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(t0).master
+        P[:, ps.p_off_uprev:] = 0.0 if U_prev0 is None else np.asarray(U_prev0, float).reshape(B, ps.nu)
+        Xi = np.zeros((B, ps.n_opt_x))
+        Xi[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (X0 / mpc._x_scaling.master)[:, None, :]
+        Xi[:, ps.off_u:ps.off_eps].reshape(B, -1, ps.nu)[:] = (P[:, ps.p_off_uprev:] / mpc._u_scaling.master)[:, None, :]
+        self.P, self.guess = t(P), t(Xi)
+        self.X = t(X0)
+        self.Xn = torch.empty_like(self.X)
+        self.U = t(P[:, ps.p_off_uprev:])                     # the inputs applied last (u_prev of the next solve)
+        self.Un = torch.empty_like(self.U)
+        self.sol = torch.empty((B, ps.n_opt_x), dtype=torch.float64, device=dev)
+        self.lam_g = torch.empty((B, ps.n_g), dtype=torch.float64, device=dev)
+        self.f = torch.empty(B, dtype=torch.float64, device=dev)
+        self.stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.lstat = torch.zeros(B, dtype=torch.int32, device=dev)
+        ts = float(simulator._t0[0])
+        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
+        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
+        self.t_mpc0, self.t_sim0 = t0, ts
+        self.dt_mpc, self.dt_sim = float(mpc.settings.t_step), float(simulator.settings.t_step)
+        self._p_row = P[0].copy()
+        self.k = 0
+        self._since = None                                    # control steps since the last solve (None: never solved)
+
+    def resolve(self) -> None:
+        """forces a solve at the next step"""
+        self._since = None
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else 0
+
+    def _sync(self):
+        if self.dev.type == "cuda":
+            self.torch.cuda.synchronize(self.dev)
+
+    def _due(self) -> bool:
+        return self._since is None or self._since >= int(self.asmpc.settings.resolve_every)
+
+    def _solve(self):
+        """the solve of BatchClosedLoop.step at the current states, then sensitivities and law: x0 <- plant state, u_prev <- applied
+        input, initial guess <- previous solution, the controller's _tvp / _p at the current loop time"""
+        torch, ps = self.torch, self.ps
+        if self.k > 0 and (ps.ntvp or ps.np_):
+            tm = self.t_mpc0 + self.k * self.dt_mpc
+            row = self._p_row
+            row[ps.p_off_tvp:ps.p_off_p] = self.mpc.tvp_fun(tm).master
+            row[ps.p_off_p:ps.p_off_uprev] = self.mpc.p_fun(tm).master
+            self.P[:, ps.p_off_tvp:ps.p_off_uprev] = torch.from_numpy(row[ps.p_off_tvp:ps.p_off_uprev].copy()).to(self.dev)
+        self.P[:, :ps.nx] = self.X
+        self.P[:, ps.p_off_uprev:] = self.U
+        self.asmpc.solve_device(self.guess, self.P, self.sol, self.lam_g, self.f, self.stats)
+        self.guess.copy_(self.sol)
+        self._since = 0
+
+    def _plant_rows(self, K):
+        """the plant's _tvp / _p at the K loop times ahead: [K][n] each (one zero per row without such parameters)"""
+        m = self.sim.model
+        ts = [self.t_sim0 + (self.k + j) * self.dt_sim for j in range(K)]
+        # (a copy per row: a tvp_fun / p_fun usually fills and returns one template)
+        tv = np.array([np.array(self.sim.tvp_fun(s).master, dtype=float).reshape(-1) for s in ts]) if m.n_tvp else np.zeros((K, 1))
+        pp = np.array([np.array(self.sim.p_fun(s).master, dtype=float).reshape(-1) for s in ts]) if m.n_p else np.zeros((K, 1))
+        return tv, pp
+
+    def _stats_host(self):
+        return np.frombuffer(self.stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
+
+    def step(self) -> dict:
+        """one control step of all B loops; returns the inputs applied, the new states, the plant status, the law status, whether the
+        step solved and - then - the solver statistics"""
+        torch, m = self.torch, self.sim.model
+        solved = self._due()
+        if solved:
+            self._solve()
+        if self.k > 0 and (m.n_p or m.n_tvp):      # the plant's parameters at the current loop time (simulator.py:790-800)
+            tv, pp = self._plant_rows(1)
+            if m.n_p:
+                self.p_plant.copy_(torch.from_numpy(np.ascontiguousarray(pp[0])).to(self.dev))
+            if m.n_tvp:
+                self.tvp_plant.copy_(torch.from_numpy(np.ascontiguousarray(tv[0])).to(self.dev))
+        stream = self._stream()
+        self.asmpc.make_step_batch_device(self.B, self.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
+        self.U, self.Un = self.Un, self.U
+        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
+                                   self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16, stream=stream)
+        self.X, self.Xn = self.Xn, self.X
+        self.k += 1
+        self._since += 1
+        self._sync()
+        out = {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1),
+               "law_status": self.lstat.cpu().numpy().copy(), "solved": solved}
+        if solved:
+            out["stats"] = self._stats_host()
+        return out
+
+    def _rollout(self, K):
+        """K control steps between two solves in one launch; returns (x [K][B][nx], u [K][B][nu], plant status, law status)"""
+        torch, m, B = self.torch, self.sim.model, self.B
+        if m.n_z:
+            raise NotImplementedError("BatchClosedLoopASMPC.run(fused=True): plants with algebraic states are not served by the rollout "
+                                      "(run(n, fused=False) steps them)")
+        tv, pp = self._plant_rows(K)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
+        tv, pp = up(tv), up(pp)
+        Xt = torch.empty((K + 1, B, m.n_x), dtype=torch.float64, device=self.dev)
+        Ut = torch.empty((K, B, m.n_u), dtype=torch.float64, device=self.dev)
+        ps_, ls_ = (torch.zeros((K, B), dtype=torch.int32, device=self.dev) for _ in range(2))
+        Xt[0].copy_(self.X)
+        law = self.asmpc.law_record()
+        self.sim.rollout_affine_device(B, K, law, Xt.data_ptr(), Ut.data_ptr(), tv.data_ptr(), pp.data_ptr(), ps_.data_ptr(), ls_.data_ptr(),
+                                       stream=self._stream())
+        self.X.copy_(Xt[K])
+        self.U.copy_(Ut[K - 1])
+        self.k += K
+        self._since += K
+        self._sync()
+        return Xt[1:].cpu().numpy(), Ut.cpu().numpy(), ps_.cpu().numpy() & 1, ls_.cpu().numpy()
+
+    def run(self, n: int, fused: bool = True) -> dict:
+        """n control steps.  fused=True: the steps between two solves in one launch each; fused=False: step() n times - the same
+        numbers bit for bit.  Returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu], 'plant_status' and 'law_status'
+        [n][B], 'solve_steps' (indices of the steps that solved) and 'stats' (their solver statistics, one record array each)."""
+        n = int(n)
+        m = self.sim.model
+        xs, us, pst, lst, solve_steps, stats = [self.X.cpu().numpy().copy()[None]], [], [], [], [], []
+        i = 0
+        while i < n:
+            if not fused:
+                r = self.step()
+                xs.append(r["x"].copy()[None]); us.append(r["u0"].copy()[None])
+                pst.append(r["plant_status"][None]); lst.append(r["law_status"][None])
+                if r["solved"]:
+                    solve_steps.append(i); stats.append(r["stats"])
+                i += 1
+                continue
+            if self._due():
+                self._solve()
+                self._sync()
+                solve_steps.append(i); stats.append(self._stats_host())
+            K = min(int(self.asmpc.settings.resolve_every) - self._since, n - i)
+            x, u, p_, l_ = self._rollout(K)
+            xs.append(x); us.append(u); pst.append(p_); lst.append(l_)
+            i += K
+        cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dtype=dt)      # noqa: E731
+        return {"x": np.concatenate(xs), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(pst, (0, self.B), np.int32),
+                "law_status": cat(lst, (0, self.B), np.int32), "solve_steps": solve_steps, "stats": stats}

@@ -9,7 +9,10 @@
 #ifdef DOMPC_HOST_EMU
 extern "C" void dompc_plant_hostemu_info(int64_t* out, char* hash);
 extern "C" void dompc_plant_hostemu_run(const dompc_plantk::Args* A);
+extern "C" void dompc_plant_hostemu_rollout(const dompc_plantk::RolloutArgs* R);
 #endif
+
+static_assert(sizeof(dompc_affine_law) == sizeof(dompc_affine::Law), "dompc_affine_law of the C ABI and the kernels' law record");
 
 static thread_local std::string g_plant_create_error;
 
@@ -27,7 +30,7 @@ struct dompc_plant : dompc_host::Context {
   bool z_reseed_next = false;
 #ifndef DOMPC_HOST_EMU
   hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr, fn_info = nullptr;
+  hipFunction_t fn = nullptr, fn_info = nullptr, fn_rollout = nullptr;
 #endif
 };
 
@@ -60,6 +63,12 @@ extern "C" int dompc_plant_create(const dompc_plant_desc* desc, dompc_plant** ou
 #endif
   const int64_t want[8] = {desc->nx, desc->nu, desc->np, desc->ntvp, desc->nw, desc->nv, desc->ny, desc->discrete ? 1 : 0};
   if (h->check_info("plant ", info, want, 8, 8, sizeof(dompc_plantk::Args), hash, desc->model_hash)) return fail();
+  if (info[9] == 0) {                    // (the rollout entry exists for plants without algebraic states only)
+    if (info[10] != (int64_t)sizeof(dompc_plantk::RolloutArgs)) { h->error = "plant rollout argument layout mismatch between runtime and code object"; return fail(); }
+#ifndef DOMPC_HOST_EMU
+    if (hipModuleGetFunction(&h->fn_rollout, h->module, "dompc_plant_rollout_kernel") != hipSuccess) { h->error = "code object lacks the plant kernels"; return fail(); }
+#endif
+  }
   h->d.code_object_path = nullptr; h->d.model_hash = nullptr;
   h->nz = (int32_t)info[9];
   h->z0.assign((size_t)(h->nz > 0 ? h->nz : 0), 0.0);
@@ -179,4 +188,37 @@ extern "C" int dompc_plant_step_batch(dompc_plant* h, int32_t B, const double* x
     return 1;
   if (down(x_next, h->s_xn, D * B * d.nx) || down(y, h->s_y, D * B * d.ny) || down(status, h->s_st, sizeof(int32_t) * (size_t)B)) return 1;
   return h->sync();
+}
+
+extern "C" int dompc_plant_rollout_affine_device(dompc_plant* h, int32_t B, int32_t K, const dompc_affine_law* law, double* X_traj,
+                                                 double* U_traj, const double* tvp_rows, const double* p_rows, int32_t* plant_status,
+                                                 int32_t* law_status, void* stream) {
+  if (!h) return 1;
+  if (B <= 0 || K <= 0) return 0;
+  const dompc_plant_desc& d = h->d;
+  if (h->nz > 0) {
+    h->error = "dompc_plant_rollout_affine_device: plants with algebraic states are not served by the rollout (use dompc_plant_step_batch_device per step)";
+    return 1;
+  }
+  if (d.nu <= 0) { h->error = "dompc_plant_rollout_affine_device: the plant has no inputs"; return 1; }
+  if (!law || !X_traj || !U_traj || (d.ntvp && !tvp_rows) || (d.np && !p_rows)) { h->error = "null pointer"; return 1; }
+  if (!law->x_ref || !law->u_ref || !law->M || !law->x_scale || (law->clip && (!law->lb || !law->ub)) || law->ld < B) {
+    h->error = "dompc_plant_rollout_affine_device: incomplete law record (x_ref, u_ref, M, x_scale, with clip lb and ub; ld >= B)";
+    return 1;
+  }
+  if (h->set_device()) return 1;
+  dompc_plantk::RolloutArgs R;
+  memset(&R, 0, sizeof(R));
+  fill_args(h, R.plant, B, 2 | 4 | 8 | 16);
+  R.plant.z_guess = nullptr;
+  memcpy(&R.law, law, sizeof(R.law));
+  R.X_traj = X_traj; R.U_traj = U_traj; R.tvp_rows = tvp_rows; R.p_rows = p_rows;
+  R.plant_status = plant_status; R.law_status = law_status; R.K = K;
+#ifndef DOMPC_HOST_EMU
+  return h->launch(h->fn_rollout, (unsigned)((B + 63) / 64), 64, 0, (hipStream_t)stream, &R, sizeof(R));
+#else
+  (void)stream;
+  dompc_plant_hostemu_rollout(&R);
+  return 0;
+#endif
 }

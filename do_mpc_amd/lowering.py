@@ -783,3 +783,21 @@ def lower_ampc(n_in, n_out, n_hidden_layers, n_neurons, act_fn, output_act_fn, s
     text = "\n".join(hdr)
     digest = hashlib.sha256(text.encode()).hexdigest()[:16]
     return text + f"\n#define AMPC_MODEL_HASH \"{digest}\"\n"
+
+
+ASMPC_LIMITS = {"n_x": 64, "n_u": 16}
+
+
+def lower_asmpc(n_x, n_u) -> str:
+    """Header for the sensitivity-based MPC law (csrc/dompc_asmpc.hip): the two sizes.  The law itself - expansion point, M, flags,
+    bounds - is runtime data.  Sizes beyond ASMPC_LIMITS (the preparation keeps a row of du0/dx0 in the registers of one lane and one
+    loop in a row of 16 lanes) are refused by name."""
+    sizes = {"n_x": int(n_x), "n_u": int(n_u)}
+    for key, v in sizes.items():
+        if not 1 <= v <= ASMPC_LIMITS[key]:
+            raise NotImplementedError(f"structured HIP backend: sensitivity-based MPC with {key} = {v} (the law kernels take "
+                                      f"1 <= {key} <= {ASMPC_LIMITS[key]})")
+    text = "\n".join(["// GENERATED by do_mpc_amd/lowering.py:lower_asmpc - do not edit.", "#pragma once",
+                      f"#define ASMPC_NX {sizes['n_x']}", f"#define ASMPC_NU {sizes['n_u']}", ""])
+    digest = hashlib.sha256(text.encode()).hexdigest()[:16]
+    return text + f"\n#define ASMPC_MODEL_HASH \"{digest}\"\n"

@@ -69,6 +69,8 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_plant_set_z_carry.restype = C.c_int
     lib.dompc_plant_num_alg_states.argtypes = [vp]
     lib.dompc_plant_num_alg_states.restype = C.c_int32
+    lib.dompc_plant_rollout_affine_device.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 8
+    lib.dompc_plant_rollout_affine_device.restype = C.c_int
     return lib
 
 
@@ -277,6 +279,23 @@ class Simulator:
         outs = [C.c_void_p(int(a) if a else None) for a in (x_next, y, status)]
         rc = self._lib.dompc_plant_step_batch_device(self._h, int(B), *args, int(shared_mask), *outs,
                                                      C.c_void_p(int(stream) if stream else None))
+        self._check(rc)
+
+    def rollout_affine_device(self, B, K, law, X_traj, U_traj, tvp_rows=0, p_rows=0, plant_status=0, law_status=0, stream=0):
+        """K control steps affine law -> plant step in ONE launch for B loops (`dompc_plant_rollout_affine_device`): for k = 0 .. K-1 the
+        input u = sat(u_ref + M (x - x_ref)) at X_traj[k] goes to U_traj[k] and the plant step - the one of `step_batch_device` - from
+        X_traj[k] with U_traj[k] to X_traj[k + 1].  `law`: a ctypes `dompc_affine_law` record (include/dompc_ipm.h; `ASMPC.law_record()`,
+        or one filled by hand - an LQR gain schedule is such a law: x_ref = xss, u_ref = uss, M = K, arrays with the loops innermost).
+        The other arguments are raw device addresses: X_traj [K + 1][B][nx] with row 0 filled, U_traj [K][B][nu], tvp_rows [K][n_tvp]
+        and p_rows [K][n_p] (the plant's parameters of each step, shared by the batch), plant_status and law_status [K][B] int32 (or
+        0).  No noise, no measurement; a loop whose plant step fails goes on.  Asynchronous on `stream`.  Plants with algebraic states
+        are refused: step them with `step_batch_device`."""
+        if self.model.n_z:
+            raise NotImplementedError("Simulator.rollout_affine_device: plants with algebraic states are not served by the rollout "
+                                      "(the step-wise path, step_batch_device, serves them)")
+        ptrs = [C.c_void_p(int(a) if a else None) for a in (X_traj, U_traj, tvp_rows, p_rows, plant_status, law_status)]
+        rc = self._lib.dompc_plant_rollout_affine_device(self._h, int(B), int(K), C.c_void_p(C.addressof(law)), *ptrs,
+                                                         C.c_void_p(int(stream) if stream else None))
         self._check(rc)
 
     def make_step(self, u0=None, v0=None, w0=None) -> np.ndarray:

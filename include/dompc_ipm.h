@@ -428,6 +428,69 @@ int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const doubl
 int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, int32_t clip_to_bounds,
                                  void* stream);
 
+/* ---- affine state feedback  u = sat(u_ref + M (x - x_ref))  for B loops (csrc/dompc_affine.h) --------------------------------
+ * The law record.  Every pointer is a DEVICE address; arrays are laid out with the loops innermost, so that one thread per loop reads
+ * them coalesced over the batch: x_ref [nx][ld], u_ref [nu][ld], M [nu][nx][ld] (entry of loop b at ... * ld + b), flags [ld] (NULL:
+ * all zero), lb / ub [nu] in physical units (may be infinite; read only with clip != 0), x_scale [nx].  Status bits of a step: 0 and 1
+ * copied from flags, 2 = an input was clipped, 3 = max_k |x_k - x_ref_k| / x_scale_k > max_dx.  The arithmetic is fixed - u_i =
+ * fma(M[i][k], x_k - x_ref_k, u_i) for k ascending from u_ref_i, the clip as two comparisons (a NaN stays a NaN) - and the same in
+ * dompc_asmpc_step_batch_device and dompc_plant_rollout_affine_device: the two give equal bits.  An LQR gain schedule is such a law
+ * (x_ref = xss, u_ref = uss, M = K). */
+typedef struct dompc_affine_law {
+  const double *x_ref, *u_ref, *M;
+  const int32_t* flags;
+  const double *lb, *ub, *x_scale;
+  int64_t ld;
+  double max_dx;
+  int32_t clip, pad;
+} dompc_affine_law;
+
+/* K control steps law -> plant in ONE launch (dompc_plant_rollout_kernel), one thread per loop: for k = 0 .. K-1 the input of the law
+ * at X_traj[k] goes to U_traj[k], the plant step (the step of dompc_plant_step_batch_device, unchanged) from X_traj[k] with U_traj[k]
+ * to X_traj[k+1].  X_traj [K+1][B][nx] with row 0 filled by the caller, U_traj [K][B][nu], plant_status [K][B] (as status of
+ * dompc_plant_step_batch_device) and law_status [K][B] (bits above; either may be NULL); tvp_rows [K][ntvp] / p_rows [K][np]: the
+ * plant's parameters of step k, shared by the batch.  No process or measurement noise, no measurement.  A loop whose plant step fails
+ * goes on from the state it reached.  Plants with algebraic states are refused: dompc_plant_step_batch_device serves them.
+ * DEVICE buffers, asynchronous on `stream`. */
+int dompc_plant_rollout_affine_device(dompc_plant* h, int32_t B, int32_t K, const dompc_affine_law* law, double* X_traj, double* U_traj,
+                                      const double* tvp_rows, const double* p_rows, int32_t* plant_status, int32_t* law_status,
+                                      void* stream);
+
+/* ---- sensitivity-based MPC between two solves (csrc/dompc_asmpc.hip): the class ASMPC of the reference's
+ * examples/batch_reactor_differentiator, u = (I - G)^-1 (u0 + J (x - x_prev) - G u0) with J = du0/dx0, G = du0/du_prev - the affine law
+ * u = u0 + M (x - x_prev), M = (I - G)^-1 J - for B loops.  The code object is built for the sizes (nx <= 64, nu <= 16); the law
+ * record, the bounds and the scaling are data of the handle.
+ * dompc_asmpc_prepare_device forms M for every loop and writes the law record (x_ref = x_prev, u_ref = u0): entry (r, c) of loop b's J
+ * at J + b * batch_J + r * row_J + c, G alike - so both may be views into the [B][nu][nx + nu] result of dompc_sens_batch_device;
+ * ok [B] (NULL: all 1).  flags bit 0: ok = 0 or J / G not finite, bit 1: I - G singular or a non-finite pivot; either gives M = 0, the
+ * law then holds u0.  dompc_asmpc_set_law: the same from contiguous HOST arrays J [B][nu][nx], G [B][nu][nu]; returns when the law is
+ * there.  dompc_asmpc_get_law copies the record to host arrays x_ref [B][nx], u_ref [B][nu], M [B][nu][nx], flags [B] (any may be
+ * NULL).  dompc_asmpc_law fills `out` with the record for dompc_plant_rollout_affine_device; it is valid until the next preparation.
+ * dompc_asmpc_set_options: bounds of the inputs in physical units (infinite allowed), x_scale [nx], clip on / off, max_dx (INFINITY:
+ * never flagged); host pointers.  Defaults: no bounds, x_scale = 1, clip on, max_dx = INFINITY. */
+typedef struct dompc_asmpc dompc_asmpc;
+typedef struct dompc_asmpc_desc {
+  int32_t nx, nu;
+  const char* code_object_path;      /* gfx950 code object built for the sizes                                   */
+  const char* model_hash;            /* ASMPC_MODEL_HASH of the header the code object was built from            */
+  int32_t device;
+} dompc_asmpc_desc;
+int  dompc_asmpc_create(const dompc_asmpc_desc* desc, dompc_asmpc** out);
+void dompc_asmpc_destroy(dompc_asmpc* h);
+const char* dompc_asmpc_last_error(const dompc_asmpc* h);     /* h may be NULL: error of the last failed create */
+int dompc_asmpc_set_options(dompc_asmpc* h, const double* lbu, const double* ubu, const double* x_scale, int32_t clip, double max_dx);
+int dompc_asmpc_prepare_device(dompc_asmpc* h, int32_t B, const double* x_prev, const double* u0, const double* J, int64_t row_J,
+                               int64_t batch_J, const double* G, int64_t row_G, int64_t batch_G, const int32_t* ok, void* stream);
+int dompc_asmpc_set_law(dompc_asmpc* h, int32_t B, const double* x_prev, const double* u0, const double* J, const double* G,
+                        const int32_t* ok);
+int dompc_asmpc_get_law(dompc_asmpc* h, double* x_ref, double* u_ref, double* M, int32_t* flags);
+int32_t dompc_asmpc_law_batch(const dompc_asmpc* h);          /* loops of the current law record, 0 = none */
+int dompc_asmpc_law(dompc_asmpc* h, dompc_affine_law* out);
+/* one step U = sat(u_ref + M (X - x_ref)) for the B loops of the law; status [B] may be NULL.  Host buffers: */
+int dompc_asmpc_step_batch(dompc_asmpc* h, int32_t B, const double* x, double* u_out, int32_t* status);
+/* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*) */
+int dompc_asmpc_step_batch_device(dompc_asmpc* h, int32_t B, const double* x, double* u, int32_t* status, void* stream);
+
 /* ---- batched parametric sensitivities of the MPC solution (mode 3 of csrc/dompc_device.hip, sens_newton in csrc/dompc_driver.h):
  * d x*[sel] / d p[cols] at B solutions of one problem class, from Newton directions of the solver's own structured KKT factorisation.
  * The points are what dompc_solve_batch(_device) returned: x [B][n_opt_x], lam_g [B][n_g], mu [B] = stats.mu / stats.obj_scaling (a
