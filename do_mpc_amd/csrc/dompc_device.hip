@@ -48,6 +48,7 @@ DOMPC_HD inline void model_info(const int32_t* in, int64_t* out) {
 #else
   out[20] = 0;                                                             // (the host emulation always runs the generic recursion)
 #endif
+  out[21] = NW;                                                            // rows of an edge's square block (KArgs::node_pack: NP_NUROW)
 }
 }  // namespace dompc
 

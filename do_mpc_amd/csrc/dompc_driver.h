@@ -112,6 +112,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     if (sh_cnt(A, mk_x(A, g))) cnt[0] += (hl ? 1.0 : 0.0) + (hu ? 1.0 : 0.0);
   }
   for (int r = T.tid; r < A.n_g; r += T.nt) Q.lam[r] = 0.0;
+  gf_zero_edge_unknowns(T, Q);
   T.sync();
   // Variables that appear in no constraint and no cost term (unused scenario slots of the reference's opt_x struct,
   // SURVEY.md App. A.7) are not determined by the NLP, only by the barrier terms of their bounds.  Under `singular0` they
@@ -422,6 +423,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
   for (int g = T.tid; g < nSl; g += T.nt) { Q.st[g] = Q.s[g]; Q.zslt[g] = Q.zsl[g]; Q.zsut[g] = Q.zsu[g]; }
   T.sync();
   Comp Cp{-INFINITY, INFINITY, 0.0};      // complementarity partials of the last evaluated trial point (this thread's share)
+  double Sy = 0.0;                        // ... and its partial of the sum of the constraint multipliers' magnitudes
 
   while (true) {
     bool skip_first = false;
@@ -541,7 +543,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     // objective, constraint violation and barrier sum of the trial point x + al * dx; the point itself, with the multipliers it would have as
     // the next iterate (bound multipliers: step az), is left in the second copy of the iterate, its constraint values in Q.ct
     auto eval_trial = [&](double al, double az, double& obj_o, double& th_o, double& bar_o) {
-      run_eval_trial(T, Q, b, slot, al, az, mu, obj_o, th_o, bar_o, Cp);
+      run_eval_trial(T, Q, b, slot, al, az, mu, obj_o, th_o, bar_o, Cp, Sy);
       ++n_trials;
     };
     // filter / sufficient-decrease tests of a trial point reached with step size al (IPOPT eqs. (18)-(20))
@@ -694,7 +696,7 @@ DOMPC_DEV inline void solve_problem(const Thr& T, const KArgs& A, int b, int slo
     ++n_sweeps;
     if (EPS_GLOBAL) epsg_grad(T, Q);
     if (KAPPA_D != 0.0) Q.mu = mu;
-    c_t = prof_clock(); g_t = T.gen; E = measure(T, Q, &Cp); c_meas += prof_clock() - c_t; g_meas += T.gen - g_t;
+    c_t = prof_clock(); g_t = T.gen; E = measure(T, Q, &Cp, Sy); c_meas += prof_clock() - c_t; g_meas += T.gen - g_t;
   }
 
   // ---- nothing outside this loop knows about the two copies: the final iterate goes to the primary arrays
@@ -802,6 +804,7 @@ DOMPC_DEV inline void debug_newton(const Thr& T, const KArgs& A, int b = 0, int 
     Q.zl[g] = A.dbg_zl[g]; Q.zu[g] = A.dbg_zu[g];
   }
   for (int r = T.tid; r < A.n_g; r += T.nt) Q.lam[r] = A.dbg_lam[r];
+  gf_zero_edge_unknowns(T, Q);
   T.sync();
   newton_slack_setup(T, A, Q, A.dbg_at_solution, A.dbg_mu, false, 0.0);
   Q.sf = 1.0;
@@ -858,6 +861,7 @@ DOMPC_DEV inline void sens_newton(const Thr& T, const KArgs& A, int b, int slot)
     Q.x[g] = xv; Q.lb[g] = lr; Q.ub[g] = ur; Q.zl[g] = zl; Q.zu[g] = zu;
   }
   for (int i = T.tid; i < A.n_g; i += T.nt) Q.lam[i] = lin[i];
+  gf_zero_edge_unknowns(T, Q);
   {
     const int ops[1] = {R_MAX};
     wg_reduce(T, bad, ops);
@@ -937,6 +941,7 @@ DOMPC_DEV inline void sweep_problem(const Thr& T, const KArgs& A, int b, int slo
     Q.x[g] = xin[g]; Q.lb[g] = -INFINITY; Q.ub[g] = INFINITY; Q.zl[g] = 0.0; Q.zu[g] = 0.0;
   }
   for (int r = T.tid; r < A.n_g; r += T.nt) Q.lam[r] = lin[r];
+  gf_zero_edge_unknowns(T, Q);
   for (int g = T.tid; g < A.n_edges * NE; g += T.nt) {
     const int si = (g / NE1) * NE1 + g % NE1;
     Q.s[si] = 0.0; Q.sl[si] = -INFINITY; Q.su[si] = INFINITY; Q.zsl[si] = 0.0; Q.zsu[si] = 0.0; Q.sgn[si] = 1.0;

@@ -88,6 +88,47 @@ DOMPC_DEV inline double eval_edge_f_t(const Prob& Q, int e, const double* xv, co
 }
 DOMPC_PHASE double eval_edge_f(const Prob& Q, int e, const double* xv, const double* sv, double* cv) { return eval_edge_f_t<false>(Q, e, xv, sv, cv, -1); }
 
+// Indices of node n for the node updates of the two Riccati passes: picks from the node's packed record (KArgs::node_pack, one read
+// per node) or, -DDOMPC_NODE_PACK=0, the look-ups in the tables it was built from (the comparison build of tests/test_node_pack.py).
+#ifndef DOMPC_NODE_PACK
+#define DOMPC_NODE_PACK 1
+#endif
+constexpr bool NODE_PACK = DOMPC_NODE_PACK != 0;
+DOMPC_DEV inline int np_of(const KArgs& A, int n, int f) { return A.node_pack[n * NP_N + f]; }
+DOMPC_DEV inline int node_xoff(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_XOFF) : A.node_x_off[n]; }
+DOMPC_DEV inline int node_uoff(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_UOFF) : A.node_u_off[n]; }
+DOMPC_DEV inline int node_epsoff(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_EPSOFF) : A.node_eps_off[n]; }
+DOMPC_DEV inline int node_inedge(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_INEDGE) : A.node_in_edge[n]; }
+DOMPC_DEV inline int node_cstart(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_CHILD_START) : A.node_child_start[n]; }
+DOMPC_DEV inline int node_ccount(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_CHILD_COUNT) : A.node_child_count[n]; }
+// first row in g (and lam) of the continuity rows that END in node n; the root: the rows of the initial condition
+DOMPC_DEV inline int node_nurow(const KArgs& A, int n) {
+  if (NODE_PACK) return np_of(A, n, NP_NUROW);
+  const int ie = A.node_in_edge[n];
+  return ie >= 0 ? A.edge_row0[ie] + NW : 0;
+}
+// offset of the parent's u in opt_x, or -1: node n is the root and u_prev comes from the parameters
+DOMPC_DEV inline int node_uoff_parent(const KArgs& A, int n) {
+  if (NODE_PACK) return np_of(A, n, NP_UOFF_PARENT);
+  const int pn = A.node_parent[n];
+  return pn >= 0 ? A.node_u_off[pn] : -1;
+}
+// first child edge of a node that has one: the child node, its x offset, the edge's first row in g
+DOMPC_DEV inline int node_child0(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_CHILD0) : A.edge_child[A.node_child_start[n]]; }
+DOMPC_DEV inline int node_xoff_child0(const KArgs& A, int n) {
+  return NODE_PACK ? np_of(A, n, NP_XOFF_CHILD0) : A.node_x_off[A.edge_child[A.node_child_start[n]]];
+}
+DOMPC_DEV inline int node_row0_child0(const KArgs& A, int n) { return NODE_PACK ? np_of(A, n, NP_ROW0_CHILD0) : A.edge_row0[A.node_child_start[n]]; }
+
+// The objective has no term in the unknowns an edge eliminates, except on the dense edge path (dompc_dae.h), which stores its gradient
+// per sweep: everywhere else their gf entries are zeroed here, once per problem and before its first sweep, instead of by every sweep
+DOMPC_DEV inline void gf_zero_edge_unknowns(const Thr& T, const Prob& Q) {
+  const KArgs& A = *Q.A;
+  constexpr int NW1 = NW > 0 ? NW : 1;
+  if (!DENSE_EDGE && NW > 0)
+    for (int it = T.tid; it < A.n_edges * NW; it += T.nt) Q.gf[A.edge_w_off[it / NW1] + it % NW1] = 0.0;
+}
+
 // rterm share of node n (all outgoing edges): sum_b omega_k r'(u_n - u_prev)^2  (_mpc.py:1271-1275)
 DOMPC_DEV inline const double* uprev_ptr(const Prob& Q, int n, const double* xv, double* tmp) {
   const KArgs& A = *Q.A;
@@ -98,8 +139,8 @@ DOMPC_DEV inline const double* uprev_ptr(const Prob& Q, int n, const double* xv,
 }
 DOMPC_DEV inline double node_rweight(const Prob& Q, int n) {
   const KArgs& A = *Q.A;
-  const int cc = A.node_child_count[n];
-  return cc > 0 ? cc * A.edge_omega[A.node_child_start[n]] * Q.sf : 0.0;
+  const int cc = node_ccount(A, n);
+  return cc > 0 ? cc * A.edge_omega[NODE_PACK ? np_of(A, n, NP_RW_EDGE) : A.node_child_start[n]] * Q.sf : 0.0;
 }
 DOMPC_DEV inline double node_rterm_f(const Prob& Q, int n, const double* xv) {
   const KArgs& A = *Q.A;

@@ -531,7 +531,6 @@ DOMPC_DEV inline int edge_factor_body(const Prob& Q, int e, double mu, int lane,
         t -= DOMPC_D[cx / NX + 1] * Ld[EL_T0 + R + cx % NX];   // (measured: neither a select chain nor a load of the coefficient in the first batch of the edge pays - both slow the elimination that follows by more than the round trip they save)
         const int gi = woff + cx;
         const double xv = vx[q][0], l = vx[q][1], u = vx[q][2], zl_ = vx[q][3], zu_ = vx[q][4];
-        Q.gf[gi] = 0.0;
         Q.rd[gi] = t - zl_ + zu_;
         Ld[EL_RW + cx] = t + bar_grad(xv, l, u, mu, !(Q.soc & 2));
         Ld[EL_BB + cx] = bar_grad(xv, l, u, 1.0);
@@ -548,7 +547,6 @@ DOMPC_DEV inline int edge_factor_body(const Prob& Q, int e, double mu, int lane,
       double xv, l, u, zl_, zu_;
       if (GS > 1) { xv = ex[0]; l = ex[1]; u = ex[2]; zl_ = ex[3]; zu_ = ex[4]; }
       else { xv = Q.x[gi]; l = Q.lb[gi]; u = Q.ub[gi]; zl_ = Q.zl[gi]; zu_ = Q.zu[gi]; }
-      Q.gf[gi] = 0.0;
       Q.rd[gi] = t - zl_ + zu_;
       Ld[EL_RW + col] = t + bar_grad(xv, l, u, mu, !(Q.soc & 2));
       Ld[EL_BB + col] = bar_grad(xv, l, u, 1.0);
@@ -1019,7 +1017,7 @@ DOMPC_PHASE int eval_edge_coop(const Thr& T, const Prob& Q, int e, int e_next, d
 #pragma unroll
       for (int q = 0; q < G_WPL; ++q) {
         const int col = lane + q * GS;
-        if (col < NW) { Q.gf[woff + col] = 0.0; Q.rd[woff + col] = gp_x[q]; }
+        if (col < NW) Q.rd[woff + col] = gp_x[q];
       }
       if (!Q.soc) {
 #pragma unroll

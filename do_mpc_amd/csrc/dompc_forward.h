@@ -75,11 +75,11 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
 #pragma unroll
       for (int a = 0; a < NA; ++a) t += Nd[ND_K + i * NA + a] * Ld[RF_DX + a];
       Ld[RF_DV + i] = t;
-      if (i < NU) Q.dx[A.node_u_off[n] + i] = t;
-      else Q.dx[A.node_eps_off[n] + i - NU] = t;
+      if (i < NU) Q.dx[node_uoff(A, n) + i] = t;
+      else Q.dx[node_epsoff(A, n) + i - NU] = t;
     }
     T.gsync();
-    const int cs = A.node_child_start[n], cc = A.node_child_count[n];
+    const int cs = node_cstart(A, n), cc = node_ccount(A, n);
     for (int it = lane; it < cc * NA; it += GS) {
       const int e = cs + it / NA, a = it % NA, cn = A.edge_child[e];
       if (!mk_e(A, e)) continue;                       // another rank's sub-tree
@@ -91,7 +91,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
         for (int b = 0; b < NX; ++b) t += S_[ES_AB + a * NA + b] * Ld[RF_DX + b];
 #pragma unroll
         for (int b = 0; b < NU; ++b) t += S_[ES_AB + a * NA + NX + b] * Ld[RF_DV + b];
-        Q.dx[A.node_x_off[cn] + a] = t;
+        Q.dx[node_xoff(A, cn) + a] = t;
       } else {
         t = Ld[RF_DV + a - NX];
       }
@@ -102,8 +102,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
   // chain node (one child): operands requested one node ahead (load_step), staged through LDS; also forms the
   // multiplier step of the child's incoming continuity rows  d nu = P_c dx~_c + p_c  (x rows)
   auto load_step = [&](int n, double (&v)[FW_PL]) {
-    const int e = A.node_child_start[n];
-    const double *Nd = Q.ND(n), *S_ = Q.ES(e), *Nc = Q.ND(A.edge_child[e]);
+    const double *Nd = Q.ND(n), *S_ = Q.ES(node_cstart(A, n)), *Nc = Q.ND(node_child0(A, n));
 #pragma unroll
     for (int q = 0; q < FW_PL; ++q) {
       const int i = lane + q * GS;
@@ -118,7 +117,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
     }
   };
   auto chain_step = [&](int n, const double (&v)[FW_PL]) {      // dx~ of node n is in Ld[RF_DX]
-    const int e = A.node_child_start[n], cn = A.edge_child[e];
+    const int cn = node_child0(A, n);
 #pragma unroll
     for (int q = 0; q < FW_PL; ++q) {
       const int i = lane + q * GS;
@@ -132,8 +131,8 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
 #pragma unroll
       for (int a = 0; a < NA; ++a) t += K_[i * NA + a] * Ld[RF_DX + a];
       Ld[RF_DV + i] = t;
-      if (i < NU) Q.dx[A.node_u_off[n] + i] = t;
-      else Q.dx[A.node_eps_off[n] + i - NU] = t;
+      if (i < NU) Q.dx[node_uoff(A, n) + i] = t;
+      else Q.dx[node_epsoff(A, n) + i - NU] = t;
     }
     T.gsync();
     for (int a = lane; a < NA; a += GS) {
@@ -144,7 +143,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
         for (int b = 0; b < NX; ++b) t += AB_[a * NA + b] * Ld[RF_DX + b];
 #pragma unroll
         for (int b = 0; b < NU; ++b) t += AB_[a * NA + NX + b] * Ld[RF_DV + b];
-        Q.dx[A.node_x_off[cn] + a] = t;
+        Q.dx[node_xoff_child0(A, n) + a] = t;
       } else {
         t = Ld[RF_DV + a - NX];
       }
@@ -156,7 +155,7 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
       double t = PV_[a];
 #pragma unroll
       for (int b = 0; b < NA; ++b) t += PC_[a * NA + b] * Ld[RF_DXN + b];
-      Q.dlam[A.edge_row0[e] + NW + a] = t;
+      Q.dlam[node_row0_child0(A, n) + NW + a] = t;
     }
     for (int a = lane; a < NA; a += GS) Ld[RF_DX + a] = Ld[RF_DXN + a];
     T.gsync();
@@ -215,11 +214,24 @@ DOMPC_PHASE void riccati_forward_t(const Thr& T, const Prob& Q, double mu, doubl
           cn_[q] = A.level_node_start[kq + 1] + scq;
           e_[q] = scq;
         }
+        if (NODE_PACK) {
+          // the node's record: its one child edge is node_child_start[(k, 0)] + s and leads to (k + 1, s) (checked by the runtime when it
+          // sets chain_level), so NP_CHILD_START and NP_CHILD0 are the numbers the table walk below forms
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { e_[q] += A.node_child_start[n_[q]]; n_[q] += deep ? s0 : ((q < cw && s0 + q < S) ? s0 + q : S - 1); }
+          for (int q = 0; q < 4; ++q) n_[q] += deep ? s0 : ((q < cw && s0 + q < S) ? s0 + q : S - 1);
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          uo_[q] = A.node_u_off[n_[q]]; eo_[q] = NS > 0 ? A.node_eps_off[n_[q]] : 0; xoc_[q] = A.node_x_off[cn_[q]]; row0_[q] = A.edge_row0[e_[q]];
+          for (int q = 0; q < 4; ++q) {
+            const auto* np = A.node_pack + n_[q] * NP_N;
+            e_[q] = np[NP_CHILD_START]; cn_[q] = np[NP_CHILD0];
+            uo_[q] = np[NP_UOFF]; eo_[q] = NS > 0 ? np[NP_EPSOFF] : 0; xoc_[q] = np[NP_XOFF_CHILD0]; row0_[q] = np[NP_ROW0_CHILD0];
+          }
+        } else {
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { e_[q] += A.node_child_start[n_[q]]; n_[q] += deep ? s0 : ((q < cw && s0 + q < S) ? s0 + q : S - 1); }
+#pragma unroll
+          for (int q = 0; q < 4; ++q) {
+            uo_[q] = A.node_u_off[n_[q]]; eo_[q] = NS > 0 ? A.node_eps_off[n_[q]] : 0; xoc_[q] = A.node_x_off[cn_[q]]; row0_[q] = A.edge_row0[e_[q]];
+          }
         }
         auto pick = [&](const int (&a)[4]) { return c4 == 0 ? a[0] : (c4 == 1 ? a[1] : (c4 == 2 ? a[2] : a[3])); };
         const unsigned nd0 = (unsigned)pick(n_) * (unsigned)ND_SIZE, es0 = (unsigned)pick(e_) * (unsigned)ES_SIZE, nc0 = (unsigned)pick(cn_) * (unsigned)ND_SIZE;

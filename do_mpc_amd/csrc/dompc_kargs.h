@@ -8,6 +8,12 @@ namespace dompc {
 enum { WIDE_BAR_STRIDE = 64 };
 enum { EP_PARENT = 0, EP_CHILD, EP_LEVEL, EP_WOFF, EP_PIDX, EP_ROW0, EP_XOFF_PARENT, EP_UOFF_PARENT, EP_XOFF_CHILD, EP_EPSOFF_PARENT,
        EP_OMEGA_LO, EP_OMEGA_HI, EP_N = 16 };
+// ... and the indices a node update needs (KArgs::node_pack).  NP_NUROW: first row of the node's incoming continuity rows in g
+// (edge_row0[in_edge] + NW; the root: row 0 of the initial condition), NP_UOFF_PARENT: -1 at the root (u_prev comes from the parameters),
+// NP_CHILD0 / NP_XOFF_CHILD0 / NP_ROW0_CHILD0: child node, its x offset and edge_row0 of the FIRST child edge (-1 at a leaf),
+// NP_RW_EDGE: the edge whose omega weighs the node's rterm (node_rweight; -1 at a leaf)
+enum { NP_XOFF = 0, NP_UOFF, NP_EPSOFF, NP_INEDGE, NP_NUROW, NP_PARENT, NP_UOFF_PARENT, NP_CHILD_START, NP_CHILD_COUNT, NP_CHILD0,
+       NP_XOFF_CHILD0, NP_ROW0_CHILD0, NP_LEVEL, NP_RW_EDGE, NP_N = 16 };
 // Structure tables of the problem class: written once by dompc_create(), never by a kernel.  In device code they are
 // pointers into the CONSTANT address space, which is what lets the compiler read them with scalar loads (s_load through
 // the scalar cache, result in SGPRs) wherever the index is wave-uniform - with plain global pointers every look-up is a
@@ -28,6 +34,9 @@ struct KArgs {
   // the indices an edge needs, resolved and side by side (EP_N ints per edge, written by dompc_create from the tables above): one
   // scalar load instead of seven look-ups of which three depend on the first - and one table pointer in registers instead of ten
   itab_t edge_pack;
+  // the same for the nodes (NP_N ints per node): the chain walks of the two Riccati passes read one record per node instead of up to
+  // seven tables in three dependent levels
+  itab_t node_pack;
   int32_t N, n_nodes, n_edges, n_dummy, n_opt_x, n_opt_p, n_g, e_pad;
   int32_t p_off_tvp, p_off_p, p_off_uprev;
   int32_t chain_level;      // first stage from which every node has exactly one child of the same scenario index (= n_robust)

@@ -97,9 +97,10 @@ DOMPC_DEV inline void step_rules_pass(const Thr& T, const Prob& Q, double mu, do
 // objective, constraint violation and barrier sum of the trial point x + al * dx, and the trial point itself in full: x, s (Q.xt / Q.st),
 // bound multipliers (step a_z, safeguarded: Q.zlt / Q.zut / Q.zslt / Q.zsut) and constraint multipliers (step al: Q.lamt), constraint
 // values in Q.ct.  Accepting the point is a flip of the slot's parity (prob_flip, solve_problem); a rejected one is overwritten by the
-// next trial.  Cp: this thread's complementarity statistics of the trial point (consumed by measure() after the sweep of the new iterate).
+// next trial.  Cp: this thread's complementarity statistics of the trial point, Sy: its partial of sum |lamt| over the rows it counts (both
+// consumed by measure() after the sweep of the new iterate).
 template <bool FINE>
-DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, double a_z, double mu, double& obj_o, double& th_o, double& bar_o, Comp& Cp) {
+DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, double a_z, double mu, double& obj_o, double& th_o, double& bar_o, Comp& Cp, double& Sy) {
   const KArgs& A = *Q.A;
   const int nX = A.n_opt_x, nSl = A.n_edges * NE;
   const double ks = 1e10;
@@ -165,9 +166,11 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
   }
   {
     double y_[DOMPC_FW], dy_[DOMPC_FW];
+    double sy = 0.0;
 #define L_(u, g) y_[u] = Q.lam[g]; dy_[u] = Q.dlam[g];
-#define B_(u, g) if (mk_g(A, g)) Q.lamt[g] = y_[u] + al * dy_[u];
+#define B_(u, g) if (mk_g(A, g)) { const double yt_ = y_[u] + al * dy_[u]; Q.lamt[g] = yt_; if (sh_cnt(A, mk_g(A, g))) sy += fabs(yt_); }
     DOMPC_FOR4(A.n_g, L_, B_)
+    Sy = sy;
 #undef L_
 #undef B_
   }
@@ -199,7 +202,7 @@ DOMPC_DEV inline void eval_trial_pass(const Thr& T, const Prob& Q, double al, do
 }
 struct PhaseRet { unsigned gen, nred, xseq; int rc; };
 struct PhaseRet3 { unsigned gen, nred, xseq; double v0, v1, v2; };
-struct PhaseRet6 { unsigned gen, nred, xseq; double v0, v1, v2, c0, c1, c2; };      // c*: thread-local Comp partials
+struct PhaseRet6 { unsigned gen, nred, xseq; double v0, v1, v2, c0, c1, c2, sy; };      // c*: thread-local Comp partials, sy: of sum |lamt|
 #ifndef DOMPC_HOST_EMU
 #define DOMPC_PHASE_PROLOGUE                                                        \
   const KArgs A = kernel_args(kp);                                                  \
@@ -254,15 +257,17 @@ __device__ __attribute__((noinline)) PhaseRet6 phase_eval_trial(const void* kp, 
   DOMPC_PHASE_PROLOGUE
   double o = 0.0, th = 0.0, br = 0.0;
   Comp C;
-  eval_trial_pass<false>(T, Q, ufl(al), ufl(a_z), ufl(mu), o, th, br, C);
-  return PhaseRet6{T.gen, T.nred, T.xseq, o, th, br, C.smax, C.smin, C.sum_z};
+  double sy;
+  eval_trial_pass<false>(T, Q, ufl(al), ufl(a_z), ufl(mu), o, th, br, C, sy);
+  return PhaseRet6{T.gen, T.nred, T.xseq, o, th, br, C.smax, C.smin, C.sum_z, sy};
 }
 __device__ __attribute__((noinline)) PhaseRet6 phase_eval_trial_fine(const void* kp, int b, int slot, double sf, double al, double a_z, double mu, unsigned gen, unsigned nred, unsigned xseq) {
   DOMPC_PHASE_PROLOGUE
   double o = 0.0, th = 0.0, br = 0.0;
   Comp C;
-  eval_trial_pass<true>(T, Q, ufl(al), ufl(a_z), ufl(mu), o, th, br, C);
-  return PhaseRet6{T.gen, T.nred, T.xseq, o, th, br, C.smax, C.smin, C.sum_z};
+  double sy;
+  eval_trial_pass<true>(T, Q, ufl(al), ufl(a_z), ufl(mu), o, th, br, C, sy);
+  return PhaseRet6{T.gen, T.nred, T.xseq, o, th, br, C.smax, C.smin, C.sum_z, sy};
 }
 #undef DOMPC_PHASE_PROLOGUE
 #define DOMPC_PHASE_CALL(fn, ...)                                                   \
@@ -322,15 +327,15 @@ DOMPC_DEV inline void run_step_rules(const Thr& T, const Prob& Q, int b, int slo
   step_rules_pass(T, Q, mu, r5);
 #endif
 }
-DOMPC_DEV inline void run_eval_trial(const Thr& T, const Prob& Q, int b, int slot, double al, double a_z, double mu, double& obj_o, double& th_o, double& bar_o, Comp& Cp) {
+DOMPC_DEV inline void run_eval_trial(const Thr& T, const Prob& Q, int b, int slot, double al, double a_z, double mu, double& obj_o, double& th_o, double& bar_o, Comp& Cp, double& Sy) {
 #ifndef DOMPC_HOST_EMU
-  if (fine_items(T, *Q.A)) { DOMPC_PHASE_CALL(phase_eval_trial_fine, al, a_z, mu) obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); Cp = Comp{r_.c0, r_.c1, r_.c2}; return; }
+  if (fine_items(T, *Q.A)) { DOMPC_PHASE_CALL(phase_eval_trial_fine, al, a_z, mu) obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); Cp = Comp{r_.c0, r_.c1, r_.c2}; Sy = r_.sy; return; }
   if (DOMPC_REPEAT_PHASE & 8) { DOMPC_PHASE_CALL(phase_eval_trial, al, a_z, mu) }
   DOMPC_PHASE_CALL(phase_eval_trial, al, a_z, mu)
-  obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); Cp = Comp{r_.c0, r_.c1, r_.c2};
+  obj_o = ufl(r_.v0); th_o = ufl(r_.v1); bar_o = ufl(r_.v2); Cp = Comp{r_.c0, r_.c1, r_.c2}; Sy = r_.sy;
 #else
   (void)b; (void)slot;
-  if (fine_items(T, *Q.A)) eval_trial_pass<true>(T, Q, al, a_z, mu, obj_o, th_o, bar_o, Cp); else eval_trial_pass<false>(T, Q, al, a_z, mu, obj_o, th_o, bar_o, Cp);
+  if (fine_items(T, *Q.A)) eval_trial_pass<true>(T, Q, al, a_z, mu, obj_o, th_o, bar_o, Cp, Sy); else eval_trial_pass<false>(T, Q, al, a_z, mu, obj_o, th_o, bar_o, Cp, Sy);
 #endif
 }
 DOMPC_DEV inline void run_forward(const Thr& T, const Prob& Q, int b, int slot, double mu, double delta) {

@@ -347,7 +347,6 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
 #pragma unroll
     for (int s = 0; s < M; ++s) {
       const int gi = pk.woff + s * NX + (int)b;
-      Q.gf[gi] = 0.0;
       Q.rd[gi] = RDv[s];
     }
     double* ew = Q.ew + (int64_t)e * EW_SIZE;

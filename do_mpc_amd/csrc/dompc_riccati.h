@@ -56,11 +56,11 @@ DOMPC_DEV inline double node_nl_load(const Prob& Q, int e, int it) {
 
 DOMPC_DEV inline void node_prefetch(const Prob& Q, int n, double delta, int lane, int GS, NodePre& R) {
   const KArgs& A = *Q.A;
-  const int e = A.node_child_start[n];
+  const int e = node_cstart(A, n);
   const double* S_ = Q.ES(e);
-  const int xo = A.node_x_off[n], uo = A.node_u_off[n];
-  const int eo = NS > 0 ? A.node_eps_off[n] : -1;
-  const int ie = A.node_in_edge[n], pn = A.node_parent[n];
+  const int xo = node_xoff(A, n), uo = node_uoff(A, n);
+  const int eo = NS > 0 ? node_epsoff(A, n) : -1;
+  const int nurow = node_nurow(A, n), upo = node_uoff_parent(A, n);
   (void)delta;
 #pragma unroll
   for (int q = 0; q < RN_IPL; ++q) {
@@ -82,10 +82,10 @@ DOMPC_DEV inline void node_prefetch(const Prob& Q, int n, double delta, int lane
     R.pv[v][2] = Q.ub[g];
     R.pv[v][3] = Q.zl[g];
     R.pv[v][4] = Q.zu[g];
-    R.pv[v][5] = (i < NX) ? ((ie >= 0) ? Q.lam[A.edge_row0[ie] + NW + i] : Q.lam[i]) : 0.0;
+    R.pv[v][5] = (i < NX) ? Q.lam[nurow + i] : 0.0;
     const int iu = is_up ? i - NX : (i >= NA && i < NA + NU ? i - NA : 0);
     const bool hu = i >= NX && i < NA + NU;
-    R.pv[v][6] = hu ? (pn >= 0 ? Q.x[A.node_u_off[pn] + iu] : Q.P[A.p_off_uprev + iu] / DOMPC_SU[iu]) : 0.0;
+    R.pv[v][6] = hu ? (upo >= 0 ? Q.x[upo + iu] : Q.P[A.p_off_uprev + iu] / DOMPC_SU[iu]) : 0.0;
     R.pv[v][7] = 0.0;
     R.pv[v][8] = yi >= 0 ? S_[ES_QV + yi] : 0.0;
     R.pv[v][9] = 0.0;
@@ -114,7 +114,7 @@ DOMPC_DEV inline int riccati_node(const Thr& T, const Prob& Q, int n, double mu,
   using namespace rb;
   const KArgs& A = *Q.A;
   double* Nd = Q.ND(n);
-  const int cs = A.node_child_start[n], cc = A.node_child_count[n];
+  const int cs = node_cstart(A, n), cc = node_ccount(A, n);
   const double rw = node_rweight(Q, n);
   const double rwh = (Q.soc & 2) ? 0.0 : rw;          // weight of the rterm HESSIAN (Prob::soc bit 1)
   long long pc0 = prof_clock();
@@ -160,7 +160,7 @@ DOMPC_DEV inline int riccati_node(const Thr& T, const Prob& Q, int n, double mu,
     } else {
       dg = sigma_of(xv, lo, hi, zlo, zhi) + delta;
       gv = bar_grad(xv, lo, hi, mu, !(Q.soc & 2));
-      if (i < NX) gv += (A.node_in_edge[n] >= 0) ? -R.pv[v][5] : R.pv[v][5];
+      if (i < NX) gv += (node_inedge(A, n) >= 0) ? -R.pv[v][5] : R.pv[v][5];
       else if (i < NA + NU) {
         if (!RT_CUSTOM) {    // (user-defined: the (x, u) part of the gradient is in the edges' r_y)
           dg += 2.0 * rwh * DOMPC_RTERM[i - NA];
@@ -732,9 +732,8 @@ DOMPC_PHASE int riccati_backward(const Thr& T, const Prob& Q, double mu, double 
       const int r = it % (NA * (NA + 1));
       const int i = r / (NA + 1), j = r % (NA + 1);
       double* Nd = Q.ND(n);
-      const int ie = A.node_in_edge[n];
-      const double* S_ = Q.ES(ie);
-      const int xo = A.node_x_off[n];
+      const double* S_ = Q.ES(node_inedge(A, n));
+      const int xo = node_xoff(A, n);
       if (j < NA) {
         double v = 0.0;
         if (i < NX && j < NX) {
@@ -745,7 +744,7 @@ DOMPC_PHASE int riccati_backward(const Thr& T, const Prob& Q, double mu, double 
       } else {
         double v = 0.0;
         if (i < NX)
-          v = S_[ES_MG + i] - Q.lam[A.edge_row0[ie] + NW + i] + bar_grad(Q.x[xo + i], Q.lb[xo + i], Q.ub[xo + i], mu, !(Q.soc & 2));
+          v = S_[ES_MG + i] - Q.lam[node_nurow(A, n) + i] + bar_grad(Q.x[xo + i], Q.lb[xo + i], Q.ub[xo + i], mu, !(Q.soc & 2));
         Nd[ND_PV + i] = v;
       }
     }

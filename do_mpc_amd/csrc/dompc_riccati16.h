@@ -102,14 +102,16 @@ __device__ inline Val load_val(const Prob& Q, int n, int lane) {
   }
   return V;
 }
-__device__ inline void store_val(const Prob& Q, int n, const Val& V, int lane) {
+// `rows`: NA, or NX for a node whose parent takes the value function from registers (chain walk): the record is then read by the forward
+// pass alone - d nu = P dx~ + p of the node's incoming continuity rows and the adjoint shares kept in the p slot, rows / entries < NX
+__device__ inline void store_val(const Prob& Q, int n, const Val& V, int lane, int rows) {
   const int g = lane >> 4, j = lane & 15;
   double* Nd = Q.ND(n);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int i = g + 4 * r;
-    if (i < NA && j < NA) Nd[ND_P + i * NA + j] = V[r];
-    if (i < NA && j == NA) Nd[ND_PV + i] = V[r];
+    if (i < rows && j < NA) Nd[ND_P + i * NA + j] = V[r];
+    if (i < rows && j == NA) Nd[ND_PV + i] = V[r];
   }
 }
 
@@ -117,13 +119,12 @@ __device__ inline void store_val(const Prob& Q, int n, const Val& V, int lane) {
 __device__ inline Val leaf(const Prob& Q, int n, double mu, double delta, int lane) {
   const KArgs& A = *Q.A;
   const int g = lane >> 4, j = lane & 15;
-  const int ie = A.node_in_edge[n];
-  const double* S_ = Q.ES(ie);
-  const int xo = A.node_x_off[n];
+  const double* S_ = Q.ES(node_inedge(A, n));
+  const int xo = node_xoff(A, n);
   const int jj = j < NX ? j : 0;
   const double xv = Q.x[xo + jj], lo = Q.lb[xo + jj], hi = Q.ub[xo + jj];
   const double dg = sigma_of(xv, lo, hi, Q.zl[xo + jj], Q.zu[xo + jj]) + delta;
-  const double gv = (j < NX) ? S_[ES_MG + jj] - Q.lam[A.edge_row0[ie] + NW + jj] + bar_grad(xv, lo, hi, mu, !(Q.soc & 2)) : 0.0;
+  const double gv = (j < NX) ? S_[ES_MG + jj] - Q.lam[node_nurow(A, n) + jj] + bar_grad(xv, lo, hi, mu, !(Q.soc & 2)) : 0.0;
   Val V = col_to_tile(gv, lane, NA, NX);
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
@@ -161,17 +162,17 @@ __device__ inline void staged_ready() { asm volatile("s_waitcnt vmcnt(0)" ::: "m
 __device__ inline void load_node(const Prob& Q, int n, int lane, NodeIn& R) {
   const KArgs& A = *Q.A;
   const int j = lane & 15;
-  const int xo = A.node_x_off[n], uo = A.node_u_off[n];
-  const int ie = A.node_in_edge[n], pn = A.node_parent[n];
+  const int xo = node_xoff(A, n), uo = node_uoff(A, n);
+  const int upo = node_uoff_parent(A, n);
   const bool is_up = (j >= NX && j < NA);
   const int jj = j < NYT ? j : 0;
-  const int eo = NS > 0 ? A.node_eps_off[n] : 0;
+  const int eo = NS > 0 ? node_epsoff(A, n) : 0;
   const bool is_eps = NS > 0 && jj >= NA + NU;
   const int gi = (jj < NX) ? xo + jj : (is_up ? uo + (jj - NX) : (is_eps ? eo + (jj - NA - NU) : uo + (jj - NA)));
   R.xv = Q.x[gi]; R.lo = Q.lb[gi]; R.hi = Q.ub[gi]; R.zlo = Q.zl[gi]; R.zhi = Q.zu[gi];
   const int iu = is_up ? jj - NX : ((jj >= NA && !is_eps) ? jj - NA : 0);
-  R.upv = (jj >= NX && !is_eps) ? (pn >= 0 ? Q.x[A.node_u_off[pn] + iu] : Q.P[A.p_off_uprev + iu] / tab_sel(DOMPC_SU, iu)) : 0.0;
-  R.nu = (jj < NX) ? ((ie >= 0) ? Q.lam[A.edge_row0[ie] + NW + jj] : Q.lam[jj]) : 0.0;
+  R.upv = (jj >= NX && !is_eps) ? (upo >= 0 ? Q.x[upo + iu] : Q.P[A.p_off_uprev + iu] / tab_sel(DOMPC_SU, iu)) : 0.0;
+  R.nu = (jj < NX) ? Q.lam[node_nurow(A, n) + jj] : 0.0;
 }
 // tiles of the staged first child edge (LDS reads)
 __device__ inline void staged_tiles(const ldsd* Ls, int lane, d4& qt, d4& F, d4& cvr, double& fu, double& qv) {
@@ -202,11 +203,12 @@ __device__ inline void staged_tiles(const ldsd* Ls, int lane, d4& qt, d4& F, d4&
 }
 
 // One node update.  `first`: value function of the first child when it is already in registers (chain walk), else
-// null and every child's value function is read from its node record.  Returns 1 if Q_vv is not positive definite.
-__device__ inline int node(const Prob& Q, int n, double mu, double delta, int lane, const NodeIn& R, const ldsd* Ls, const Val* first, Val& out) {
+// null and every child's value function is read from its node record.  `val_rows`: rows of the value function that go to the node
+// record (store_val).  Returns 1 if Q_vv is not positive definite.
+__device__ inline int node(const Prob& Q, int n, double mu, double delta, int lane, const NodeIn& R, const ldsd* Ls, const Val* first, int val_rows, Val& out) {
   const KArgs& A = *Q.A;
   const int g = lane >> 4, j = lane & 15;
-  const int cs = A.node_child_start[n], cc = A.node_child_count[n];
+  const int cs = node_cstart(A, n), cc = node_ccount(A, n);
   const double rw = node_rweight(Q, n);
   const double rwh = (Q.soc & 2) ? 0.0 : rw;          // weight of the rterm HESSIAN (Prob::soc bit 1: least-squares multiplier solve)
   long long pc0 = prof_clock();
@@ -222,7 +224,7 @@ __device__ inline int node(const Prob& Q, int n, double mu, double delta, int la
   // ---- own quadratic: per-variable terms in column layout (lane: z-entry j)
   double dg = 0.0, gv = 0.0;
   {
-    const int ie = A.node_in_edge[n];
+    const int ie = node_inedge(A, n);
     const bool is_up = (j >= NX && j < NA);
     const int jj = j < NYT ? j : 0;
     const bool is_eps = NS > 0 && jj >= NA + NU;
@@ -424,7 +426,7 @@ __device__ inline int node(const Prob& Q, int n, double mu, double delta, int la
   if (lane == 0)
 #pragma unroll
     for (int u = 0; u < NV; ++u) Nd[ND_KV + u] = kv[u];
-  store_val(Q, n, out, lane);
+  store_val(Q, n, out, lane, val_rows);
   R16_PN(26)
 #undef R16_PN
   return bad;
@@ -444,10 +446,10 @@ __device__ inline int backward(const Thr& T, const Prob& Q, double mu, double de
     if (A.N - 1 >= cl) {
       const int n1 = A.level_node_start[A.N - 1] + s_;
       load_node(Q, n1, lane, in);
-      stage_edge(Q, A.node_child_start[n1], lane, Ld);
+      stage_edge(Q, node_cstart(A, n1), lane, Ld);
     }
     Val V = leaf(Q, A.level_node_start[A.N] + s_, mu, delta, lane);
-    store_val(Q, A.level_node_start[A.N] + s_, V, lane);
+    store_val(Q, A.level_node_start[A.N] + s_, V, lane, A.N - 1 >= cl ? NX : NA);
     staged_ready();              // the staged record of the first node has landed (later ones: waited for inside node())
     for (int k = A.N - 1; k >= cl; --k) {
       NodeIn nx;                 // the parent's operands: in flight while this node is updated
@@ -457,13 +459,13 @@ __device__ inline int backward(const Thr& T, const Prob& Q, double mu, double de
       if (k > cl) {
         const int np = A.level_node_start[k - 1] + s_;
         load_node(Q, np, lane, nx);
-        stage_edge(Q, A.node_child_start[np], lane, Ld + (buf ^ 1) * ES_STAGE);
+        stage_edge(Q, node_cstart(A, np), lane, Ld + (buf ^ 1) * ES_STAGE);
       }
 #if DOMPC_PROFILE
       if (threadIdx.x == 0) lds_prof[27] += prof_clock() - pcl;
 #endif
       Val Vn;
-      if (node(Q, A.level_node_start[k] + s_, mu, delta, lane, in, Ld + buf * ES_STAGE, &V, Vn)) { T.fset(0, FSET); break; }
+      if (node(Q, A.level_node_start[k] + s_, mu, delta, lane, in, Ld + buf * ES_STAGE, &V, k > cl ? NX : NA, Vn)) { T.fset(0, FSET); break; }
       V = Vn;
       if (k > cl) in = nx;
       buf ^= 1;
@@ -476,10 +478,10 @@ __device__ inline int backward(const Thr& T, const Prob& Q, double mu, double de
     for (int n = n0 + gid; n < n1; n += ng) {
       NodeIn in;
       load_node(Q, n, lane, in);
-      stage_edge(Q, A.node_child_start[n], lane, Ld);
+      stage_edge(Q, node_cstart(A, n), lane, Ld);
       staged_ready();
       Val Vn;
-      if (node(Q, n, mu, delta, lane, in, Ld, nullptr, Vn)) T.fset(0, FSET);
+      if (node(Q, n, mu, delta, lane, in, Ld, nullptr, NA, Vn)) T.fset(0, FSET);
     }
     T.sync();
     if ((T.fget(0) == FSET)) return 1;

@@ -385,6 +385,22 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
     }
     if (upload(h, &A.edge_pack, pack.data(), pack.size())) return fail(1);
   }
+  {
+    const int32_t nw = (int32_t)info[21];
+    std::vector<int32_t> pack((size_t)d.n_nodes * dompc::NP_N, 0);
+    for (int n = 0; n < d.n_nodes; ++n) {
+      int32_t* q = pack.data() + (size_t)n * dompc::NP_N;
+      const int ie = d.node_in_edge[n], pn = d.node_parent[n], cs = d.node_child_start[n], cc = d.node_child_count[n];
+      const int c0 = cc > 0 ? d.edge_child[cs] : -1;
+      q[dompc::NP_XOFF] = d.node_x_off[n]; q[dompc::NP_UOFF] = d.node_u_off[n]; q[dompc::NP_EPSOFF] = d.node_eps_off[n];
+      q[dompc::NP_INEDGE] = ie; q[dompc::NP_NUROW] = ie >= 0 ? d.edge_row0[ie] + nw : 0;
+      q[dompc::NP_PARENT] = pn; q[dompc::NP_UOFF_PARENT] = pn >= 0 ? d.node_u_off[pn] : -1;
+      q[dompc::NP_CHILD_START] = cs; q[dompc::NP_CHILD_COUNT] = cc; q[dompc::NP_CHILD0] = c0;
+      q[dompc::NP_XOFF_CHILD0] = cc > 0 ? d.node_x_off[c0] : -1; q[dompc::NP_ROW0_CHILD0] = cc > 0 ? d.edge_row0[cs] : -1;
+      q[dompc::NP_LEVEL] = d.node_level[n]; q[dompc::NP_RW_EDGE] = cc > 0 ? cs : -1;
+    }
+    if (upload(h, &A.node_pack, pack.data(), pack.size())) return fail(1);
+  }
   A.N = d.N; A.n_nodes = d.n_nodes; A.n_edges = d.n_edges; A.n_dummy = d.n_dummy;
   A.n_opt_x = d.n_opt_x; A.n_opt_p = d.n_opt_p; A.n_g = d.n_g; A.e_pad = h->e_pad;
   A.p_off_tvp = d.p_off_tvp; A.p_off_p = d.p_off_p; A.p_off_uprev = d.p_off_uprev;

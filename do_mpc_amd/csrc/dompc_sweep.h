@@ -176,9 +176,12 @@ DOMPC_DEV inline double comp_err(const Comp& C, double mu) { return C.smax >= C.
 
 // error measures (IPOPT eq. (5)/(6)) + objective + theta at the current iterate.  `pre`: thread-local complementarity
 // partials already accumulated by the caller (the trial evaluation that produced this iterate had x, z in registers), or null.
+// `pre_sy`: with `pre`, this thread's partial of sum |lam| from the same trial evaluation - it had every lam[g] of this thread's entries
+// of the loop below in a register (same thread mapping, same order of the sum); the tree-sharding path reads lam as before.
 struct Errs { double e_d, e_p, sum_y, obj, theta; Comp C; };
-DOMPC_PHASE Errs measure(const Thr& T, const Prob& Q, const Comp* pre) {
+DOMPC_PHASE Errs measure(const Thr& T, const Prob& Q, const Comp* pre, double pre_sy = 0.0) {
   const KArgs& A = *Q.A;
+  const bool sy_pre = pre && !sh_on(A);
   double v[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // e_d, e_p, sum|y|, obj, theta, smax, -smin, sum z
   Comp C = pre ? *pre : Comp{-INFINITY, INFINITY, 0.0};
   if (pre) {
@@ -213,7 +216,15 @@ DOMPC_PHASE Errs measure(const Thr& T, const Prob& Q, const Comp* pre) {
       if (u < INFINITY) comp_add(C, (u - Q.s[si]) * Q.zsu[si], Q.zsu[si]);
     }
   }
-  {
+  if (sy_pre) {
+    double c_[DOMPC_FW];
+    v[2] = pre_sy;
+#define L_(u, g) c_[u] = Q.c[g];
+#define B_(u, g) if (sh_cnt(A, mk_g(A, g))) { v[1] = fmax(v[1], fabs(c_[u])); v[4] += fabs(c_[u]); }
+    DOMPC_FOR4(A.n_g, L_, B_)
+#undef L_
+#undef B_
+  } else {
     double c_[DOMPC_FW], y_[DOMPC_FW];
 #define L_(u, g) c_[u] = Q.c[g]; y_[u] = Q.lam[g];
 #define B_(u, g) if (sh_cnt(A, mk_g(A, g))) { v[1] = fmax(v[1], fabs(c_[u])); v[2] += fabs(y_[u]); v[4] += fabs(c_[u]); }
