@@ -14,8 +14,14 @@ to run K control steps law -> plant in one launch (closed_loop.BatchClosedLoopAS
 
 Flags of the law [B]: bit 0 - the member's solve or sensitivities failed, or J / G is not finite; bit 1 - I - G is singular.  Either
 gives M = 0: the law holds u0, the input a plain MPC loop would have applied.  Status of a step [B]: bits 0 and 1 copied from the flags,
-bit 2 - an input was clipped to `mpc.bounds[..., '_u']`, bit 3 - max |x - x_ref| / x_scaling > settings.max_dx (it only flags; nothing
-re-solves by itself).
+bit 2 - an input was clipped to `mpc.bounds[..., '_u']`, bit 3 - max |x - x_ref| / x_scaling > settings.max_dx, bit 4 (value 16; set
+by the loops in the status they record, never by the law step) - the member was re-solved by an event at this step.
+
+Event-triggered re-solves (settings.event_triggered, off by default).  Bit 3 alone only flags.  With the setting a member whose step
+status carries a bit of settings.event_mask - far from its expansion point, or holding u0 after a failed solve - is solved again at
+once, alone or with the other members flagged at that step: `select_device` lists them on the device (an ordered compaction),
+`solve_members_device` gathers their rows, solves and differentiates the sub-batch and `update_law_device` writes their columns of
+the resident law record; the other columns are not touched.  `make_step` and closed_loop.BatchClosedLoopASMPC.step act on it.
 
 There is no CPU fallback: without a HIP device the calls raise.  Limits of the kernels: n_x <= 64, n_u <= 16; larger models are refused
 by name, and so is everything `make_step_batch(..., sensitivities=True)` refuses.
@@ -31,12 +37,17 @@ from . import _native, build, lowering
 from .differentiator import DoMPCDifferentiator
 
 
+SELECT_SPAN = 1024                       # loops per workgroup of `select_device` (csrc/dompc_asmpc_args.h)
+
+
 @dataclass
 class ASMPCSettings:
     resolve_every: int = 1               # solve and differentiate on every resolve_every-th step (make_step, BatchClosedLoopASMPC)
     clip_to_bounds: bool = True          # clip the inputs to mpc.bounds[..., '_u'] (physical units; infinite bounds never clip)
     max_dx: float = float("inf")         # infinity norm of (x - x_ref) / x_scaling beyond which a step is flagged (status bit 3)
     active_set_reduction: bool = False   # handed to the differentiator
+    event_triggered: bool = False        # a member whose step status carries a bit of event_mask is solved again in the same step
+    event_mask: int = 8 | 1 | 2          # "far" (bit 3) and the two fallback bits: such a member holds u0, an MPC loop would solve it again
 
 
 class AffineLaw(C.Structure):
@@ -66,7 +77,11 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_asmpc_law.argtypes = [vp, C.POINTER(AffineLaw)]
     lib.dompc_asmpc_step_batch.argtypes = [vp, i32, vp, vp, vp]
     lib.dompc_asmpc_step_batch_device.argtypes = [vp, i32, vp, vp, vp, vp]
-    for name in ("create", "set_options", "prepare_device", "set_law", "get_law", "law", "step_batch", "step_batch_device"):
+    lib.dompc_asmpc_select_device.argtypes = [vp, i32, vp, i32, vp, vp, vp]
+    lib.dompc_asmpc_update_device.argtypes = [vp, i32, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]
+    lib.dompc_asmpc_update_law.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    for name in ("create", "set_options", "prepare_device", "set_law", "get_law", "law", "step_batch", "step_batch_device", "select_device",
+                 "update_device", "update_law"):
         getattr(lib, "dompc_asmpc_" + name).restype = C.c_int
     return lib
 
@@ -97,6 +112,8 @@ class ASMPC:
         self._nd = None                  # (solver, active_set_reduction, differentiator)
         self._resident = {}              # device -> the solver's bounds and the input scaling as tensors (solve_device)
         self._keep = None                # inputs of an asynchronous law preparation
+        self._keep_update = None         # ... and of an asynchronous update of some of its columns
+        self._work = None                # compact tensors of solve_members_device
         self.last = None                 # result of the last solve()
         self._k = 0                      # make_step: calls so far
         self._u_data = [np.asarray(mpc.u0.master, dtype=float).reshape(-1, 1).copy()]
@@ -164,11 +181,27 @@ class ASMPC:
         [B][n_opt_x], P [B][n_opt_p] (the states in its first n_x columns, u_prev in its last n_u), lam_g [B][n_g], f [B].  Chains
         `solve_batch_device` -> `differentiate_batch_device` -> law preparation on the current stream; nothing is copied to the host.
         Returns the tensors u0 [B][n_u] (physical units) and what differentiate_batch_device returns."""
+        ps = self.mpc.structure
+        h = self._handle()
+        B = int(P.shape[0])
+        out, x_prev, u0, ok, stream = self._solve_and_differentiate(B, guess, P, sol, lam_g, f, stats)
+        nx, nu = ps.nx, ps.nu
+        S = out["dxdp"]                                                 # [B][n_u][n_x + n_u]: J and G are views into it
+        assert S.is_contiguous() and tuple(S.shape) == (B, nu, nx + nu)
+        self._check(self._lib.dompc_asmpc_prepare_device(h, B, x_prev.data_ptr(), u0.data_ptr(), S.data_ptr(), nx + nu, nu * (nx + nu),
+                                                         S.data_ptr() + 8 * nx, nx + nu, nu * (nx + nu), ok.data_ptr(),
+                                                         C.c_void_p(int(stream) if stream else None)))
+        self._keep = (x_prev, u0, ok, out)                              # (the launch is asynchronous: its inputs stay alive)
+        out = dict(out)
+        out["u0"] = u0
+        return out
+
+    def _solve_and_differentiate(self, B, guess, P, sol, lam_g, f, stats):
+        """`solve_batch_device` -> `differentiate_batch_device` for the B rows of the tensors; returns what the law preparation reads:
+        (result of the differentiator, x_prev [B][n_x], u0 [B][n_u] in physical units, ok [B] int32, the stream)"""
         import torch
         mpc, ps = self.mpc, self.mpc.structure
-        h = self._handle()
         dev = P.device
-        B = int(P.shape[0])
         if str(dev) not in self._resident:
             up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
             self._resident[str(dev)] = dict(lbx=up(mpc._lb_opt_x.master), ubx=up(mpc._ub_opt_x.master), lbg=up(mpc._nlp_cons_lb),
@@ -182,12 +215,98 @@ class ASMPC:
         u0 = torch.mul(sol[:, iu:iu + nu], r["us"])                     # u0 in physical units
         x_prev = P[:, :nx].contiguous()
         ok = out["ok"].to(torch.int32)
-        S = out["dxdp"]                                                 # [B][n_u][n_x + n_u]: J and G are views into it
-        assert S.is_contiguous() and tuple(S.shape) == (B, nu, nx + nu)
-        self._check(self._lib.dompc_asmpc_prepare_device(h, B, x_prev.data_ptr(), u0.data_ptr(), S.data_ptr(), nx + nu, nu * (nx + nu),
-                                                         S.data_ptr() + 8 * nx, nx + nu, nu * (nx + nu), ok.data_ptr(),
-                                                         C.c_void_p(int(stream) if stream else None)))
-        self._keep = (x_prev, u0, ok, out)                              # (the launch is asynchronous: its inputs stay alive)
+        return out, x_prev, u0, ok, stream
+
+    # ------------------------------------------------------------------ event-triggered re-solves of some members
+    def select_device(self, B, status_ptr, idx_ptr, count_ptr, stream=0) -> None:
+        """the members whose step status carries a bit of settings.event_mask, on raw device addresses: status [B] (int32, what
+        `make_step_batch_device` wrote) -> idx [B] (int32: those members in ascending order; entries beyond count are not written) and
+        count [1] (int32); asynchronous on `stream`"""
+        h = self._handle()
+        self._check(self._lib.dompc_asmpc_select_device(h, int(B), C.c_void_p(int(status_ptr)), int(self.settings.event_mask),
+                                                        C.c_void_p(int(idx_ptr)), C.c_void_p(int(count_ptr)),
+                                                        C.c_void_p(int(stream) if stream else None)))
+
+    def update_law_device(self, n, slot, x_prev, u0, S, ok) -> None:
+        """the law preparation for n compact entries into the columns slot[:n] (int32 tensor, distinct members of the current law) of the
+        resident law record; the other columns are not touched.  Tensors where the law lives: x_prev [n][n_x], u0 [n][n_u], S [n][n_u]
+        [n_x + n_u] (the differentiator's dxdp: J and G are views into it, as in `solve_device`), ok [n] (int32).  Asynchronous on the
+        current stream."""
+        import torch
+        ps = self.mpc.structure
+        h = self._handle()
+        n = int(n)
+        if n == 0:
+            return
+        nx, nu = ps.nx, ps.nu
+        dev = S.device
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        assert slot.dtype == torch.int32 and ok.dtype == torch.int32 and slot.is_contiguous() and x_prev.is_contiguous() and u0.is_contiguous()
+        assert S.is_contiguous() and tuple(S.shape[1:]) == (nu, nx + nu) and min(int(t.shape[0]) for t in (slot, x_prev, u0, S, ok)) >= n
+        self._check(self._lib.dompc_asmpc_update_device(h, n, slot.data_ptr(), x_prev.data_ptr(), u0.data_ptr(), S.data_ptr(), nx + nu,
+                                                        nu * (nx + nu), S.data_ptr() + 8 * nx, nx + nu, nu * (nx + nu), ok.data_ptr(),
+                                                        C.c_void_p(int(stream) if stream else None)))
+        self._keep_update = (slot, x_prev, u0, S, ok)                   # (the launch is asynchronous: its inputs stay alive)
+
+    def set_law_members(self, idx, x_prev, u0, du0dx0, du0du_prev, ok=None) -> None:
+        """`set_law` for the members idx [n] of the current law only, from host arrays with n entries each: their columns of the law
+        record are replaced, the others are not touched.  idx must be distinct and inside the current law (ValueError otherwise, before
+        anything is launched)."""
+        m = self.mpc.model
+        h = self._handle()
+        idx = np.asarray(idx).reshape(-1)
+        if idx.size and not np.issubdtype(idx.dtype, np.integer):
+            raise ValueError("ASMPC.set_law_members: idx must be integers")
+        idx = idx.astype(np.int64)
+        B, n = self.batch, idx.size
+        if B <= 0:
+            raise RuntimeError("ASMPC.set_law_members: no law to update (call solve or set_law first)")
+        if n and (idx.min() < 0 or idx.max() >= B):
+            raise ValueError(f"ASMPC.set_law_members: idx must lie in [0, {B}), the members of the current law")
+        if np.unique(idx).size != n:
+            raise ValueError("ASMPC.set_law_members: idx must be distinct")
+        f = lambda a, *shape: np.ascontiguousarray(np.asarray(a, dtype=np.float64)).reshape(-1, *shape)      # noqa: E731
+        x_prev, u0, J, G = f(x_prev, m.n_x), f(u0, m.n_u), f(du0dx0, m.n_u, m.n_x), f(du0du_prev, m.n_u, m.n_u)
+        if not (x_prev.shape[0] == u0.shape[0] == J.shape[0] == G.shape[0] == n):
+            raise ValueError("ASMPC.set_law_members: idx, x_prev, u0, du0dx0 and du0du_prev must have the same number of members")
+        if n == 0:
+            return
+        okv = None if ok is None else np.ascontiguousarray(np.asarray(ok).reshape(n) != 0, dtype=np.int32)
+        slot = np.ascontiguousarray(idx, dtype=np.int32)
+        self._check(self._lib.dompc_asmpc_update_law(h, n, _ptr(slot), _ptr(x_prev), _ptr(u0), _ptr(J), _ptr(G), _ptr(okv)))
+
+    def solve_members_device(self, idx, n, guess, P, sol, lam_g, f, stats) -> dict:
+        """`solve_device` for the members idx[:n] (int32 tensor, distinct, ascending as `select_device` writes them) of the resident
+        tensors of B loops: their rows of guess and P are gathered into compact tensors (allocated once, for B rows), the sub-batch
+        is solved and differentiated, the law preparation writes the members' columns of the resident law record, and sol, lam_g, f
+        and the stats records go back to the rows idx[:n].  The other rows and columns are not touched.  Everything on the current
+        stream; `n` is a host integer.  Returns the compact u0 [n][n_u] and what differentiate_batch_device returns.
+        The solver's launch shape follows n: the bits of a member's solution are those of a solve of a batch of n."""
+        import torch
+        from .solver import STATS_DTYPE
+        ps = self.mpc.structure
+        n, B = int(n), int(P.shape[0])
+        if not 0 < n <= B:
+            raise ValueError(f"ASMPC.solve_members_device: n = {n} members of a batch of {B}")
+        if self.batch != B:
+            raise RuntimeError(f"ASMPC.solve_members_device: the law holds {self.batch} loops, the tensors {B}")
+        dev, item = P.device, STATS_DTYPE.itemsize
+        w = self._work
+        if w is None or w["B"] != B or w["dev"] != dev:
+            e = lambda *shape, dt=torch.float64: torch.empty(shape, dtype=dt, device=dev)      # noqa: E731
+            w = self._work = dict(B=B, dev=dev, guess=e(B, ps.n_opt_x), P=e(B, ps.n_opt_p), sol=e(B, ps.n_opt_x), lam_g=e(B, ps.n_g),
+                                  f=e(B), stats=torch.zeros(B * item, dtype=torch.uint8, device=dev))
+        ix = idx[:n].to(torch.int64)
+        c = {k: w[k][:n] for k in ("guess", "P", "sol", "lam_g", "f")}
+        c["stats"] = w["stats"][:n * item]
+        torch.index_select(guess, 0, ix, out=c["guess"])
+        torch.index_select(P, 0, ix, out=c["P"])
+        out, x_prev, u0, ok, _ = self._solve_and_differentiate(n, c["guess"], c["P"], c["sol"], c["lam_g"], c["f"], c["stats"])
+        self.update_law_device(n, idx[:n].contiguous(), x_prev, u0, out["dxdp"], ok)
+        sol.index_copy_(0, ix, c["sol"])
+        lam_g.index_copy_(0, ix, c["lam_g"])
+        f.index_copy_(0, ix, c["f"])
+        stats.view(B, item).index_copy_(0, ix, c["stats"].view(n, item))
         out = dict(out)
         out["u0"] = u0
         return out
@@ -254,27 +373,39 @@ class ASMPC:
     def make_step(self, x0):
         """One loop with the reference class's semantics: on every settings.resolve_every-th call (the first included) the controller
         is solved at x0 - `mpc.make_step`, warm start and u_prev as in a plain MPC loop - and differentiated; otherwise the input is
-        the continuation from the last solve.  Returns the input as a column; `u_data` records every one."""
+        the continuation from the last solve.  With settings.event_triggered a call whose continuation reports a bit of
+        settings.event_mask (x0 farther than max_dx from the last solve's state, or a fallback law) solves at this x0 in the same call,
+        as if it were due; the period goes on counting calls.  Returns the input as a column; `u_data` records every one."""
         mpc, m = self.mpc, self.mpc.model
         x0 = np.asarray(x0, dtype=float).reshape(-1, 1)
-        if self._k % int(self.settings.resolve_every) == 0:
-            u0 = mpc.make_step(x0)
-            if not mpc.solver_stats.get("success", False):
-                self.set_law(x0.ravel(), u0.ravel(), np.zeros((1, m.n_u, m.n_x)), np.zeros((1, m.n_u, m.n_u)), [False])
+        due = self._k % int(self.settings.resolve_every) == 0
+        if due:
+            self._solve_one(x0)
+        u, st = self.make_step_batch(x0.reshape(1, -1))
+        if not due:
+            if self.settings.event_triggered and int(st[0]) & int(self.settings.event_mask):
+                self._solve_one(x0)                               # the event: solved at this x0 in the same call, as if it were due
+                u, st = self.make_step_batch(x0.reshape(1, -1))
             else:
-                nd = self._differentiator()
-                r = {"x": mpc.opt_x_num.master[None, :].copy(), "lam_g": np.asarray(mpc.lam_g_num, float).reshape(1, -1).copy(),
-                     "p": mpc.opt_p_num.master[None, :].copy(), "stats": self._stats_row()}
-                s = nd.differentiate_batch(r)
-                self.set_law(x0.ravel(), u0.ravel(), s["du0dx0"], s["du0du_prev"], s["ok"])
-        else:
-            mpc._t0 = mpc._t0 + mpc.settings.t_step               # (a control step without a solve: the controller's clock moves on)
-        u, _ = self.make_step_batch(x0.reshape(1, -1))
+                mpc._t0 = mpc._t0 + mpc.settings.t_step           # (a control step without a solve: the controller's clock moves on)
         self._k += 1
         u = u.reshape(-1, 1)
         mpc._u0.master[:] = u.ravel()                             # u_prev of the next solve: the input that was applied
         self._u_data.append(u.copy())
         return u
+
+    def _solve_one(self, x0):
+        """make_step's solve at x0: `mpc.make_step`, the sensitivities and the law of the one loop"""
+        mpc, m = self.mpc, self.mpc.model
+        u0 = mpc.make_step(x0)
+        if not mpc.solver_stats.get("success", False):
+            self.set_law(x0.ravel(), u0.ravel(), np.zeros((1, m.n_u, m.n_x)), np.zeros((1, m.n_u, m.n_u)), [False])
+        else:
+            nd = self._differentiator()
+            r = {"x": mpc.opt_x_num.master[None, :].copy(), "lam_g": np.asarray(mpc.lam_g_num, float).reshape(1, -1).copy(),
+                 "p": mpc.opt_p_num.master[None, :].copy(), "stats": self._stats_row()}
+            s = nd.differentiate_batch(r)
+            self.set_law(x0.ravel(), u0.ravel(), s["du0dx0"], s["du0du_prev"], s["ok"])
 
     def _stats_row(self):
         from .solver import STATS_DTYPE

@@ -552,6 +552,11 @@ class BatchClosedLoopASMPC:
     calls on one stream, no host copy); every step then applies the law u = sat(u_ref + M (x - x_ref)) and the plant step.  With
     resolve_every = 1 this is the MPC loop (the law at x = x_ref adds an exact zero).  Between two solves the law needs nothing from the
     host: `run(n, fused=True)` covers those steps with ONE launch each (`Simulator.rollout_affine_device`).
+    With `asmpc.settings.event_triggered` a step whose law status carries a bit of `settings.event_mask` for some members (far from the
+    expansion point, or a fallback law) solves THOSE members again at once, as a sub-batch with their own previous solutions as warm
+    start, writes their columns of the law and applies the law again; the period counter goes on.  The step's record names them in
+    'resolved' and marks them with bit 4 of 'law_status'.  Such a loop is stepped (`run(n, fused=False)`): a rollout would have to be
+    rewound to the first event.
     X0: [B][nx]; U_prev0: [B][nu], the inputs before the first step (default 0).  device: index of the HIP device, or "cpu" with a
     controller, a law and a plant on the host emulation (tests).  State feedback: the plant's measurement must be its state."""
 
@@ -600,6 +605,8 @@ class BatchClosedLoopASMPC:
         self._p_row = P[0].copy()
         self.k = 0
         self._since = None                                    # control steps since the last solve (None: never solved)
+        self.ev_idx = torch.zeros(B, dtype=torch.int32, device=dev)       # event-triggered re-solves: the members selected at a step
+        self.ev_count = torch.zeros(1, dtype=torch.int32, device=dev)
 
     def resolve(self) -> None:
         """forces a solve at the next step"""
@@ -618,6 +625,13 @@ class BatchClosedLoopASMPC:
     def _solve(self):
         """the solve of BatchClosedLoop.step at the current states, then sensitivities and law: x0 <- plant state, u_prev <- applied
         input, initial guess <- previous solution, the controller's _tvp / _p at the current loop time"""
+        self._refresh_P()
+        self.asmpc.solve_device(self.guess, self.P, self.sol, self.lam_g, self.f, self.stats)
+        self.guess.copy_(self.sol)
+        self._since = 0
+
+    def _refresh_P(self):
+        """the parameters of a solve at the current states: x0 <- plant state, u_prev <- applied input, _tvp / _p at the loop time"""
         torch, ps = self.torch, self.ps
         if self.k > 0 and (ps.ntvp or ps.np_):
             tm = self.t_mpc0 + self.k * self.dt_mpc
@@ -627,9 +641,23 @@ class BatchClosedLoopASMPC:
             self.P[:, ps.p_off_tvp:ps.p_off_uprev] = torch.from_numpy(row[ps.p_off_tvp:ps.p_off_uprev].copy()).to(self.dev)
         self.P[:, :ps.nx] = self.X
         self.P[:, ps.p_off_uprev:] = self.U
-        self.asmpc.solve_device(self.guess, self.P, self.sol, self.lam_g, self.f, self.stats)
-        self.guess.copy_(self.sol)
-        self._since = 0
+
+    def _resolve_events(self, stream):
+        """after the law step: the members whose status carries a bit of settings.event_mask are solved again at their states (a
+        sub-batch solve from their own previous solutions), their law columns written, and the law applied again for the whole batch -
+        the other members see an untouched law and get the same bits, the selected ones their new u0 (the law at x = x_ref adds an
+        exact zero).  Returns the members (host array, empty if none)."""
+        torch, a = self.torch, self.asmpc
+        a.select_device(self.B, self.lstat.data_ptr(), self.ev_idx.data_ptr(), self.ev_count.data_ptr(), stream=stream)
+        n = int(self.ev_count.item())                         # (4 bytes; the step synchronises anyway)
+        if n == 0:
+            return np.zeros(0, dtype=np.int64)
+        self._refresh_P()                                     # (self.U still holds the inputs applied last: the law step wrote self.Un)
+        a.solve_members_device(self.ev_idx, n, self.guess, self.P, self.sol, self.lam_g, self.f, self.stats)
+        ix = self.ev_idx[:n].to(torch.int64)
+        self.guess.index_copy_(0, ix, self.sol.index_select(0, ix))
+        a.make_step_batch_device(self.B, self.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
+        return self.ev_idx[:n].cpu().numpy().astype(np.int64)
 
     def _plant_rows(self, K):
         """the plant's _tvp / _p at the K loop times ahead: [K][n] each (one zero per row without such parameters)"""
@@ -645,7 +673,8 @@ class BatchClosedLoopASMPC:
 
     def step(self) -> dict:
         """one control step of all B loops; returns the inputs applied, the new states, the plant status, the law status, whether the
-        step solved and - then - the solver statistics"""
+        step solved and - then - the solver statistics.  With settings.event_triggered also 'resolved': the members (int array, empty
+        if none) that an event solved again at this step; they carry bit 4 in 'law_status', and 'stats' is there when there are any."""
         torch, m = self.torch, self.sim.model
         solved = self._due()
         if solved:
@@ -658,6 +687,10 @@ class BatchClosedLoopASMPC:
                 self.tvp_plant.copy_(torch.from_numpy(np.ascontiguousarray(tv[0])).to(self.dev))
         stream = self._stream()
         self.asmpc.make_step_batch_device(self.B, self.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
+        event = bool(self.asmpc.settings.event_triggered)
+        # (on a step that has just solved the whole batch dx = 0: only a member whose solve failed there can be selected, and gets a
+        #  second solve from the iterate the first one ended at)
+        resolved = self._resolve_events(stream) if event else None
         self.U, self.Un = self.Un, self.U
         self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
                                    self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16, stream=stream)
@@ -667,7 +700,10 @@ class BatchClosedLoopASMPC:
         self._sync()
         out = {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1),
                "law_status": self.lstat.cpu().numpy().copy(), "solved": solved}
-        if solved:
+        if event:
+            out["law_status"][resolved] |= 16                 # bit 4: re-solved by an event at this step
+            out["resolved"] = resolved
+        if solved or (event and resolved.size):
             out["stats"] = self._stats_host()
         return out
 
@@ -697,9 +733,15 @@ class BatchClosedLoopASMPC:
     def run(self, n: int, fused: bool = True) -> dict:
         """n control steps.  fused=True: the steps between two solves in one launch each; fused=False: step() n times - the same
         numbers bit for bit.  Returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu], 'plant_status' and 'law_status'
-        [n][B], 'solve_steps' (indices of the steps that solved) and 'stats' (their solver statistics, one record array each)."""
+        [n][B], 'solve_steps' (indices of the steps that solved) and 'stats' (their solver statistics, one record array each).  With
+        settings.event_triggered only fused=False, and 'events' is there too: per step the members an event solved again."""
         n = int(n)
         m = self.sim.model
+        event = bool(self.asmpc.settings.event_triggered)
+        if event and fused:
+            raise NotImplementedError("BatchClosedLoopASMPC.run(fused=True): event-triggered re-solves are not served by the rollout, which "
+                                      "would have to be rewound to the first event (run(n, fused=False) steps them)")
+        events = []
         xs, us, pst, lst, solve_steps, stats = [self.X.cpu().numpy().copy()[None]], [], [], [], [], []
         i = 0
         while i < n:
@@ -709,6 +751,8 @@ class BatchClosedLoopASMPC:
                 pst.append(r["plant_status"][None]); lst.append(r["law_status"][None])
                 if r["solved"]:
                     solve_steps.append(i); stats.append(r["stats"])
+                if event:
+                    events.append(r["resolved"])
                 i += 1
                 continue
             if self._due():
@@ -720,5 +764,8 @@ class BatchClosedLoopASMPC:
             xs.append(x); us.append(u); pst.append(p_); lst.append(l_)
             i += K
         cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dtype=dt)      # noqa: E731
-        return {"x": np.concatenate(xs), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(pst, (0, self.B), np.int32),
-                "law_status": cat(lst, (0, self.B), np.int32), "solve_steps": solve_steps, "stats": stats}
+        out = {"x": np.concatenate(xs), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(pst, (0, self.B), np.int32),
+               "law_status": cat(lst, (0, self.B), np.int32), "solve_steps": solve_steps, "stats": stats}
+        if event:
+            out["events"] = events
+        return out

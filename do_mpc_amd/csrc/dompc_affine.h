@@ -11,7 +11,8 @@
 //   x_ref [nx][ld], u_ref [nu][ld], M [nu][nx][ld]  (entry of loop b at index ... * ld + b), flags [ld] (may be null: all zero),
 //   lb / ub [nu] in physical units (may be +-inf; read only with clip != 0), x_scale [nx] (read only for max_dx).
 // Status bits of a step: 0 and 1 copied from flags (the law of this loop is a fallback: M = 0), 2 = an input was clipped,
-// 3 = max_k |x_k - x_ref_k| / x_scale_k > max_dx.
+// 3 = max_k |x_k - x_ref_k| / x_scale_k > max_dx.  Bit 4 (value 16) is never written here: the event-triggered loop
+// (closed_loop.BatchClosedLoopASMPC) sets it in the status it records for a loop that it re-solved at that step.
 #pragma once
 #include <math.h>
 #include <stdint.h>

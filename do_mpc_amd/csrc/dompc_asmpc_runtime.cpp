@@ -10,6 +10,7 @@
 extern "C" void dompc_asmpc_hostemu_info(int64_t* out, char* hash);
 extern "C" void dompc_asmpc_hostemu_prepare(const dompc_asmpck::PrepArgs* A);
 extern "C" void dompc_asmpc_hostemu_step(const dompc_asmpck::StepArgs* A);
+extern "C" void dompc_asmpc_hostemu_select(const dompc_asmpck::SelectArgs* A);
 #endif
 
 static_assert(sizeof(dompc_affine_law) == sizeof(dompc_affine::Law), "dompc_affine_law of the C ABI and the kernels' law record");
@@ -28,11 +29,20 @@ struct dompc_asmpc : dompc_host::Context {
   // staging of the host entries
   int32_t cap = 0;
   double *s_x = nullptr, *s_u = nullptr, *s_J = nullptr, *s_G = nullptr;
-  int32_t *s_ok = nullptr, *s_st = nullptr;
+  int32_t *s_ok = nullptr, *s_st = nullptr, *s_slot = nullptr;
+  // per-workgroup counts of the selection: one entry per SELECT_SPAN loops
+  int32_t sel_cap = 0;
+  int32_t* sel_count = nullptr;
 #ifndef DOMPC_HOST_EMU
   hipModule_t module = nullptr;
-  hipFunction_t fn_prep = nullptr, fn_step = nullptr, fn_info = nullptr;
+  hipFunction_t fn_prep = nullptr, fn_step = nullptr, fn_info = nullptr, fn_sel_count = nullptr, fn_sel_write = nullptr;
 #endif
+  int grow_host_staging(int32_t B) {
+    const size_t D = sizeof(double);
+    return grow_staging(&cap, B, {{(void**)&s_x, D * d.nx}, {(void**)&s_u, D * d.nu}, {(void**)&s_J, D * d.nx * d.nu},
+                                  {(void**)&s_G, D * d.nu * d.nu}, {(void**)&s_ok, sizeof(int32_t)}, {(void**)&s_st, sizeof(int32_t)},
+                                  {(void**)&s_slot, sizeof(int32_t)}});
+  }
 };
 
 static const int32_t MAX_BATCH = 1 << 20;      // (index arithmetic of the law preparation: 16 * 64 * ld stays an int)
@@ -57,7 +67,9 @@ extern "C" int dompc_asmpc_create(const dompc_asmpc_desc* desc, dompc_asmpc** ou
 #ifndef DOMPC_HOST_EMU
   if (h->open_device("sensitivity-based MPC law") ||
       h->load_module(desc->code_object_path, &h->module, {{"dompc_asmpc_prepare_kernel", &h->fn_prep}, {"dompc_asmpc_step_kernel", &h->fn_step},
-                                                          {"dompc_asmpc_info_kernel", &h->fn_info}},
+                                                          {"dompc_asmpc_info_kernel", &h->fn_info},
+                                                          {"dompc_asmpc_select_count_kernel", &h->fn_sel_count},
+                                                          {"dompc_asmpc_select_write_kernel", &h->fn_sel_write}},
                      "code object lacks the law kernels") ||
       h->query_info(h->fn_info, "dompc_asmpc_info_kernel", info, hash))
     return fail();
@@ -66,7 +78,7 @@ extern "C" int dompc_asmpc_create(const dompc_asmpc_desc* desc, dompc_asmpc** ou
 #endif
   const int64_t want[2] = {desc->nx, desc->nu};
   if (h->check_info("law ", info, want, 2, 2, sizeof(dompc_asmpck::PrepArgs), hash, desc->model_hash)) return fail();
-  if (info[3] != (int64_t)sizeof(dompc_asmpck::StepArgs)) { h->error = "law argument layout mismatch between runtime and code object"; return fail(); }
+  if (info[3] != (int64_t)sizeof(dompc_asmpck::StepArgs) || info[4] != (int64_t)sizeof(dompc_asmpck::SelectArgs)) { h->error = "law argument layout mismatch between runtime and code object"; return fail(); }
   const size_t D = sizeof(double);
   if (h->alloc((void**)&h->lb, D * desc->nu) || h->alloc((void**)&h->ub, D * desc->nu) || h->alloc((void**)&h->xs, D * desc->nx)) return fail();
   std::vector<double> lo((size_t)desc->nu, -INFINITY), hi((size_t)desc->nu, INFINITY), one((size_t)desc->nx, 1.0);
@@ -111,6 +123,25 @@ extern "C" int dompc_asmpc_law(dompc_asmpc* h, dompc_affine_law* out) {
   return 0;
 }
 
+// the law preparation for n entries: into the columns 0 .. n-1 of the record (slot null) or into the columns slot[j]
+static int launch_prepare(dompc_asmpc* h, int32_t n, const int32_t* slot, const double* x_prev, const double* u0, const double* J,
+                          int64_t row_J, int64_t batch_J, const double* G, int64_t row_G, int64_t batch_G, const int32_t* ok, void* stream) {
+  dompc_asmpck::PrepArgs A;
+  memset(&A, 0, sizeof(A));
+  A.x_prev = x_prev; A.u0 = u0; A.J = J; A.G = G; A.ok = ok; A.slot = slot;
+  A.row_J = row_J; A.batch_J = batch_J; A.row_G = row_G; A.batch_G = batch_G;
+  fill_law(h, A.law);
+  A.batch = n;
+#ifndef DOMPC_HOST_EMU
+  // one wavefront per workgroup, four loops per wavefront
+  return h->launch(h->fn_prep, (unsigned)((n + 3) / 4), 64, 0, (hipStream_t)stream, &A, sizeof(A));
+#else
+  (void)stream;
+  dompc_asmpc_hostemu_prepare(&A);
+  return 0;
+#endif
+}
+
 extern "C" int dompc_asmpc_prepare_device(dompc_asmpc* h, int32_t B, const double* x_prev, const double* u0, const double* J, int64_t row_J,
                                           int64_t batch_J, const double* G, int64_t row_G, int64_t batch_G, const int32_t* ok, void* stream) {
   if (!h) return 1;
@@ -126,18 +157,71 @@ extern "C" int dompc_asmpc_prepare_device(dompc_asmpc* h, int32_t B, const doubl
                                        {(void**)&h->flags, sizeof(int32_t)}}))
     return 1;
   h->law_B = B;
-  dompc_asmpck::PrepArgs A;
-  memset(&A, 0, sizeof(A));
-  A.x_prev = x_prev; A.u0 = u0; A.J = J; A.G = G; A.ok = ok;
-  A.row_J = row_J; A.batch_J = batch_J; A.row_G = row_G; A.batch_G = batch_G;
-  fill_law(h, A.law);
-  A.batch = B;
+  return launch_prepare(h, B, nullptr, x_prev, u0, J, row_J, batch_J, G, row_G, batch_G, ok, stream);
+}
+
+extern "C" int dompc_asmpc_update_device(dompc_asmpc* h, int32_t n, const int32_t* slot, const double* x_prev, const double* u0,
+                                         const double* J, int64_t row_J, int64_t batch_J, const double* G, int64_t row_G, int64_t batch_G,
+                                         const int32_t* ok, void* stream) {
+  if (!h) return 1;
+  if (h->law_B <= 0) { h->error = "no law to update: nothing has been solved yet (dompc_asmpc_prepare_device / dompc_asmpc_set_law)"; return 1; }
+  if (n < 0 || n > h->law_B) {
+    char buf[160];
+    snprintf(buf, sizeof(buf), "the law holds %d loops, the update names %d", (int)h->law_B, (int)n);
+    h->error = buf;
+    return 1;
+  }
+  if (n == 0) return 0;
+  if (!slot || !x_prev || !u0 || !J || !G) { h->error = "null pointer"; return 1; }
+  if (row_J <= 0 || row_G <= 0 || row_J > INT32_MAX || row_G > INT32_MAX) { h->error = "row strides of J and G must be positive"; return 1; }
+  if (h->set_device()) return 1;
+  return launch_prepare(h, n, slot, x_prev, u0, J, row_J, batch_J, G, row_G, batch_G, ok, stream);
+}
+
+extern "C" int dompc_asmpc_update_law(dompc_asmpc* h, int32_t n, const int32_t* slot, const double* x_prev, const double* u0,
+                                      const double* J, const double* G, const int32_t* ok) {
+  if (!h) return 1;
+  if (h->law_B <= 0) { h->error = "no law to update: nothing has been solved yet (dompc_asmpc_prepare_device / dompc_asmpc_set_law)"; return 1; }
+  if (n < 0 || n > h->law_B) { h->error = "the update names more loops than the law holds"; return 1; }
+  if (n == 0) return 0;
+  if (!slot || !x_prev || !u0 || !J || !G) { h->error = "null pointer"; return 1; }
+  const dompc_asmpc_desc& d = h->d;
+  if (h->set_device()) return 1;
+  const size_t D = sizeof(double), N = (size_t)n;
+  if (h->grow_host_staging(n)) return 1;
+  if (h->h2d(h->s_x, x_prev, D * N * d.nx) || h->h2d(h->s_u, u0, D * N * d.nu) || h->h2d(h->s_J, J, D * N * d.nx * d.nu) ||
+      h->h2d(h->s_G, G, D * N * d.nu * d.nu) || h->h2d(h->s_slot, slot, sizeof(int32_t) * N) || (ok && h->h2d(h->s_ok, ok, sizeof(int32_t) * N)))
+    return 1;
+  if (dompc_asmpc_update_device(h, n, h->s_slot, h->s_x, h->s_u, h->s_J, d.nx, (int64_t)d.nx * d.nu, h->s_G, d.nu, (int64_t)d.nu * d.nu,
+                                ok ? h->s_ok : nullptr, h->stream_ptr()))
+    return 1;
+  return h->sync();
+}
+
+extern "C" int dompc_asmpc_select_device(dompc_asmpc* h, int32_t B, const int32_t* status, int32_t mask, int32_t* idx, int32_t* count,
+                                         void* stream) {
+  if (!h) return 1;
+  if (B <= 0) { h->error = "empty batch"; return 1; }
+  if (B > MAX_BATCH) { h->error = "batch larger than 1048576 loops"; return 1; }
+  if (!status || !idx || !count) { h->error = "null pointer"; return 1; }
+  if (h->set_device()) return 1;
+  const int32_t groups = (B + dompc_asmpck::SELECT_SPAN - 1) / dompc_asmpck::SELECT_SPAN;
+  if (groups > h->sel_cap) {
 #ifndef DOMPC_HOST_EMU
-  // one wavefront per workgroup, four loops per wavefront
-  return h->launch(h->fn_prep, (unsigned)((B + 3) / 4), 64, 0, (hipStream_t)stream, &A, sizeof(A));
+    HIPCHK(h, hipDeviceSynchronize());     // no selection that still uses the old counts is in flight on any stream
+#endif
+    if (h->grow_staging(&h->sel_cap, groups, {{(void**)&h->sel_count, sizeof(int32_t)}})) return 1;
+  }
+  dompc_asmpck::SelectArgs A;
+  memset(&A, 0, sizeof(A));
+  A.status = status; A.idx = idx; A.count = count; A.group_count = h->sel_count;
+  A.batch = B; A.mask = mask;
+#ifndef DOMPC_HOST_EMU
+  if (h->launch(h->fn_sel_count, (unsigned)groups, dompc_asmpck::SELECT_THREADS, 0, (hipStream_t)stream, &A, sizeof(A))) return 1;
+  return h->launch(h->fn_sel_write, (unsigned)groups, dompc_asmpck::SELECT_THREADS, 0, (hipStream_t)stream, &A, sizeof(A));
 #else
   (void)stream;
-  dompc_asmpc_hostemu_prepare(&A);
+  dompc_asmpc_hostemu_select(&A);
   return 0;
 #endif
 }
@@ -150,9 +234,7 @@ extern "C" int dompc_asmpc_set_law(dompc_asmpc* h, int32_t B, const double* x_pr
   const dompc_asmpc_desc& d = h->d;
   if (h->set_device()) return 1;
   const size_t D = sizeof(double);
-  if (h->grow_staging(&h->cap, B, {{(void**)&h->s_x, D * d.nx}, {(void**)&h->s_u, D * d.nu}, {(void**)&h->s_J, D * d.nx * d.nu},
-                                   {(void**)&h->s_G, D * d.nu * d.nu}, {(void**)&h->s_ok, sizeof(int32_t)}, {(void**)&h->s_st, sizeof(int32_t)}}))
-    return 1;
+  if (h->grow_host_staging(B)) return 1;
   if (h->h2d(h->s_x, x_prev, D * B * d.nx) || h->h2d(h->s_u, u0, D * B * d.nu) || h->h2d(h->s_J, J, D * B * d.nx * d.nu) ||
       h->h2d(h->s_G, G, D * B * d.nu * d.nu) || (ok && h->h2d(h->s_ok, ok, sizeof(int32_t) * (size_t)B)))
     return 1;
@@ -216,9 +298,7 @@ extern "C" int dompc_asmpc_step_batch(dompc_asmpc* h, int32_t B, const double* x
   const dompc_asmpc_desc& d = h->d;
   if (h->set_device()) return 1;
   const size_t D = sizeof(double);
-  if (h->grow_staging(&h->cap, B, {{(void**)&h->s_x, D * d.nx}, {(void**)&h->s_u, D * d.nu}, {(void**)&h->s_J, D * d.nx * d.nu},
-                                   {(void**)&h->s_G, D * d.nu * d.nu}, {(void**)&h->s_ok, sizeof(int32_t)}, {(void**)&h->s_st, sizeof(int32_t)}}))
-    return 1;
+  if (h->grow_host_staging(B)) return 1;
   if (h->h2d(h->s_x, x, D * B * d.nx)) return 1;
   if (dompc_asmpc_step_batch_device(h, B, h->s_x, h->s_u, h->s_st, h->stream_ptr())) return 1;
   if (h->d2h(u_out, h->s_u, D * B * d.nu) || (status && h->d2h(status, h->s_st, sizeof(int32_t) * (size_t)B))) return 1;

@@ -432,7 +432,8 @@ int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, cons
  * The law record.  Every pointer is a DEVICE address; arrays are laid out with the loops innermost, so that one thread per loop reads
  * them coalesced over the batch: x_ref [nx][ld], u_ref [nu][ld], M [nu][nx][ld] (entry of loop b at ... * ld + b), flags [ld] (NULL:
  * all zero), lb / ub [nu] in physical units (may be infinite; read only with clip != 0), x_scale [nx].  Status bits of a step: 0 and 1
- * copied from flags, 2 = an input was clipped, 3 = max_k |x_k - x_ref_k| / x_scale_k > max_dx.  The arithmetic is fixed - u_i =
+ * copied from flags, 2 = an input was clipped, 3 = max_k |x_k - x_ref_k| / x_scale_k > max_dx (bit 4 is not written by a step: the
+ * event-triggered loop of do_mpc_amd marks with it, in its records, the loops it re-solved at that step).  The arithmetic is fixed - u_i =
  * fma(M[i][k], x_k - x_ref_k, u_i) for k ascending from u_ref_i, the clip as two comparisons (a NaN stays a NaN) - and the same in
  * dompc_asmpc_step_batch_device and dompc_plant_rollout_affine_device: the two give equal bits.  An LQR gain schedule is such a law
  * (x_ref = xss, u_ref = uss, M = K). */
@@ -490,6 +491,20 @@ int dompc_asmpc_law(dompc_asmpc* h, dompc_affine_law* out);
 int dompc_asmpc_step_batch(dompc_asmpc* h, int32_t B, const double* x, double* u_out, int32_t* status);
 /* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*) */
 int dompc_asmpc_step_batch_device(dompc_asmpc* h, int32_t B, const double* x, double* u, int32_t* status, void* stream);
+/* Event-triggered re-solves of some loops of the law.
+ * dompc_asmpc_select_device: idx[0 .. count[0]) = the loops b with status[b] & mask != 0 in ascending order of b (status [B]: what a
+ * step wrote; idx [B], count [1]; entries of idx beyond count are not written).  An ordered compaction: list and count do not depend
+ * on the launch shape or on timing.  DEVICE buffers, asynchronous on `stream`.
+ * dompc_asmpc_update_device: dompc_asmpc_prepare_device for n compact entries, entry j written into column slot[j] of the EXISTING
+ * law record (slot [n], device; distinct values).  The other columns are not touched, the record keeps its size; a slot outside the
+ * record stores nothing.  0 <= n <= dompc_asmpc_law_batch; n = 0 launches nothing.  Asynchronous on `stream`.
+ * dompc_asmpc_update_law: the same from contiguous HOST arrays (slot included), as dompc_asmpc_set_law; returns when it is done. */
+int dompc_asmpc_select_device(dompc_asmpc* h, int32_t B, const int32_t* status, int32_t mask, int32_t* idx, int32_t* count, void* stream);
+int dompc_asmpc_update_device(dompc_asmpc* h, int32_t n, const int32_t* slot, const double* x_prev, const double* u0, const double* J,
+                              int64_t row_J, int64_t batch_J, const double* G, int64_t row_G, int64_t batch_G, const int32_t* ok,
+                              void* stream);
+int dompc_asmpc_update_law(dompc_asmpc* h, int32_t n, const int32_t* slot, const double* x_prev, const double* u0, const double* J,
+                           const double* G, const int32_t* ok);
 
 /* ---- batched parametric sensitivities of the MPC solution (mode 3 of csrc/dompc_device.hip, sens_newton in csrc/dompc_driver.h):
  * d x*[sel] / d p[cols] at B solutions of one problem class, from Newton directions of the solver's own structured KKT factorisation.

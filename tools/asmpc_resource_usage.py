@@ -1,6 +1,7 @@
-"""Registers, scratch and LDS of the three entries of the sensitivity-based MPC loop, as the compiler reports them
+"""Registers, scratch and LDS of the entries of the sensitivity-based MPC loop, as the compiler reports them
 (-Rpass-analysis=kernel-resource-usage; no GPU needed): the law preparation and the law step of csrc/dompc_asmpc.hip for every prebuilt
-shape - the last one, n_x = 64 and n_u = 16, is the limit - and the plant rollout of csrc/dompc_plant.hip next to the plant step it
+shape - the last one, n_x = 64 and n_u = 16, is the limit -, the two launches of the selection (they read no size: listed once) and the
+plant rollout of csrc/dompc_plant.hip next to the plant step it
 contains, for the plants the loop is tested and measured on.  usage: python tools/asmpc_resource_usage.py > profiles/asmpc_resource_usage.txt"""
 import os
 import re
@@ -28,6 +29,8 @@ for label, hdr, h in ge.lowered_asmpc():
     _, text = build.asmpc_code_object(hdr, h, remarks=True)
     for kernel in ("dompc_asmpc_prepare_kernel", "dompc_asmpc_step_kernel"):
         print(f"| law, {label} | {kernel} | " + " | ".join(row(text, kernel)) + " |")
+for kernel in ("dompc_asmpc_select_count_kernel", "dompc_asmpc_select_write_kernel"):
+    print(f"| law, any shape | {kernel} | " + " | ".join(row(text, kernel)) + " |")
 for name in ("batch_reactor", "CSTR", "industrial_poly"):
     hdr = Simulator(CASES[name].build_model())._lower()
     h = hdr.rsplit('PLANT_MODEL_HASH "', 1)[1].split('"')[0]
