@@ -354,3 +354,67 @@ def check_rollout_with_synthetic_law(hostemu, B=67, K=4):
     lsh = lst.cpu().numpy()
     assert (lsh[:, 3] & 1).all() and (lsh & 4).any() and (lsh & 8).any() and not (pst.cpu().numpy() & 1).any()
     assert np.array_equal(Ut[:, 3].cpu().numpy(), np.tile(np.minimum(np.maximum(r["u0"][3], [5.0, -8500.0]), [60.0, 0.0]), (K, 1)))
+
+
+# ---------------------------------------------------------------------------------------------- pivot orders that are not the identity
+def _lu_order(A):
+    from scipy.linalg import lu
+    return tuple(int(i) for i in np.argmax(lu(A)[0], axis=0))
+
+
+def permuted_record(nx, nu, B, seed):
+    """record() with I - G = (signed permutation with entries in +-[1, 2]) + (0.4 / n_u) uniform(-1, 1): condition number about 2, and
+    the pivot of a column is not the row of the same number.  Even members get a cyclic shift (by 1 + b / 2), odd members a random
+    permutation that is neither the identity nor one of an earlier member"""
+    r = record(nx, nu, B, seed)
+    rng = np.random.default_rng(seed + 1)
+    seen = {tuple(range(nu))}
+    for b in range(B):
+        if b % 2 == 0:
+            perm = np.roll(np.arange(nu), 1 + (b // 2) % (nu - 1))
+        else:
+            perm = rng.permutation(nu)
+            while tuple(perm) in seen:
+                perm = rng.permutation(nu)
+        seen.add(tuple(perm))
+        A = np.zeros((nu, nu))
+        A[np.arange(nu), perm] = rng.uniform(1.0, 2.0, nu) * rng.choice([-1.0, 1.0], nu)
+        r["G"][b] = np.eye(nu) - (A + (0.4 / nu) * rng.uniform(-1.0, 1.0, (nu, nu)))
+    return r
+
+
+def check_pivot_orders(nx, nu, hostemu, B=5):
+    """the Gauss-Jordan routine of csrc/dompc_lanes_la.h with a pivot order that is not the identity in every member, and another one
+    in every member of the wavefront (asserted on the CPU with scipy.linalg.lu): the lane_gather at its end moves every row.  M and U
+    against the reference formula at `close`; flags all 0.  n_u = 16: member 2 with row 5 of I - G zero (rank 15, the zero pivot is met
+    in the last column) gets flag 2 and M = 0, the others are bit-equal to the run without it"""
+    r = permuted_record(nx, nu, B, seed=5000 + 10 * nx + nu)
+    orders = [_lu_order(np.eye(nu) - r["G"][b]) for b in range(B)]
+    conds = [float(np.linalg.cond(np.eye(nu) - r["G"][b])) for b in range(B)]
+    ident = tuple(range(nu))
+    assert all(o != ident for o in orders) and all(orders[b] != orders[b + 1] for b in range(B - 1)) and len(set(orders)) >= 3, orders
+    assert len(set(orders[:4])) >= 3 and max(conds) < 10.0, (orders, conds)
+    a = law_of(r, hostemu)
+    L = a.law
+    U, st = a.make_step_batch(r["X"])
+    assert not L["flags"].any() and not st.any(), (L["flags"], st)
+    worst = 0.0
+    for b in range(B):
+        M, u = reference(r, b, r["X"][b])
+        worst = max(worst, np.max(np.abs(L["M"][b] - M)) / max(1.0, np.max(np.abs(M))), np.max(np.abs(U[b] - u)) / max(1.0, np.max(np.abs(u))))
+        assert close(L["M"][b], M) and close(U[b], u), (b, np.max(np.abs(L["M"][b] - M)), np.max(np.abs(U[b] - u)))
+    print(f"n_x = {nx}, n_u = {nu}: cond(I - G) <= {max(conds):.2f}, {len(set(orders))} pivot orders, max |M - ref|, |U - ref| relative = {worst:.3e}")
+    if nu == 16:
+        s = {k: v.copy() for k, v in r.items()}
+        s["G"][2, 5] = np.eye(nu)[5]
+        assert np.linalg.matrix_rank(np.eye(nu) - s["G"][2]) == nu - 1
+        bad = law_of(s, hostemu)
+        Lb = bad.law
+        Ub, stb = bad.make_step_batch(s["X"])
+        expect = np.array([0, 0, 2, 0, 0], dtype=np.int32)
+        assert np.array_equal(Lb["flags"], expect) and np.array_equal(stb, expect), (Lb["flags"], stb)
+        assert not Lb["M"][2].any() and np.array_equal(Ub[2], s["u0"][2])
+        others = [0, 1, 3, 4]
+        assert np.array_equal(Lb["M"][others], L["M"][others]) and np.array_equal(Ub[others], U[others])
+        bad.close()
+    a.close()

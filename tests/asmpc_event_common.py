@@ -68,6 +68,50 @@ def check_select(B, hostemu):
     a.close()
 
 
+# from workgroup SELECT_THREADS + 1 on (counted from 0), the strided sum over the counts of the workgroups before it takes a second
+# round: 256 workgroups is the largest batch without one, 257 SPAN + 1 loops are 258 workgroups, the last with a single member
+LARGE_SELECT_BATCHES = [256 * SPAN, 257 * SPAN + 1]
+
+
+def check_select_large(B, hostemu):
+    """check_select for batches of more than SELECT_THREADS workgroups, with the statuses drawn by array operations: count, idx[:count]
+    = flatnonzero(status & mask), idx behind count untouched, status unchanged"""
+    a = ac.make_asmpc(ac.stub_mpc(4, 1), hostemu)
+    rng = np.random.default_rng(1000 + B)
+    first_of_last = ((B - 1) // SPAN) * SPAN
+    assert B > 256 * SPAN - 1 and first_of_last // SPAN >= 255
+    for mask in (8, 11):
+        a.settings.event_mask = mask
+        bits = np.array([b for b in (1, 2, 8) if mask & b], dtype=np.int32)
+        for what in ("none", "all", "only the last", "only the first of the last workgroup", "random"):
+            want = np.zeros(B, bool)
+            if what == "all":
+                want[:] = True
+            elif what == "only the last":
+                want[-1] = True
+            elif what == "only the first of the last workgroup":
+                want[first_of_last] = True
+            elif what == "random":
+                want = rng.random(B) < 0.3
+            # a non-empty subset of the mask's bits where wanted; bit 2 and bits outside the mask must not select
+            subset = rng.integers(1, 2 ** bits.size, B)
+            chosen = sum(((subset >> i) & 1).astype(np.int32) * bits[i] for i in range(bits.size))
+            status = np.where(want, chosen, 0).astype(np.int32)
+            status |= np.where(rng.random(B) < 0.5, 4, 0).astype(np.int32)
+            status |= (rng.integers(0, 16, B).astype(np.int32) & np.int32(11 & ~mask))
+            expect = np.flatnonzero(status & mask)
+            assert np.array_equal(expect, np.flatnonzero(want))
+            st, idx, cnt = _tensor(status, hostemu), _tensor(np.full(B, -7, dtype=np.int32), hostemu), _tensor(np.full(1, -7, dtype=np.int32), hostemu)
+            a.select_device(B, st.data_ptr(), idx.data_ptr(), cnt.data_ptr())
+            _sync(hostemu)
+            n, got = int(cnt.cpu().numpy()[0]), idx.cpu().numpy()
+            assert n == expect.size, (B, mask, what, n, expect.size)
+            assert np.array_equal(got[:n], expect), (B, mask, what)
+            assert np.all(got[n:] == -7), (B, mask, what)
+            assert np.array_equal(st.cpu().numpy(), status)
+    a.close()
+
+
 def _same_law(La, Lb, cols=slice(None)):
     return all(np.array_equal(La[k][cols], Lb[k][cols], equal_nan=True) for k in ("x_ref", "u_ref", "M", "flags"))
 

@@ -199,7 +199,8 @@ RES_MARGIN_EXAMPLES = 2.1e-10       # measured 2.04e-11 (cstr_lqr, standard mode
 K_BOUND_16, RES_MARGIN_16 = 3.9e-11, 1.8e-12    # measured 3.90e-12 and 1.72e-13 (both in standard mode) over the designs of size 16
 K_BOUND_A, RES_MARGIN_A = 1.7e-7, 1.7e-8        # measured 1.64e-8 (member 1747: scipy's residual 7.6e-11, the kernel's 9.9e-13) and 1.66e-9
 K_BOUND_B, RES_MARGIN_B, AB_BOUND_B = 4.9e-9, 6.7e-14, 3.6e-12      # measured 4.82e-10, 6.65e-15 and 3.51e-13
-SCIPY_RESIDUAL = 1e-10              # a member is compared only when scipy's own solution is that good
+AB_BOUND_MIXED = 6.0e-12           # measured 5.97e-13 (check_mixed_squarings: 9 .. 13 squarings, |B_d| up to 2.1e3); K 1.30e-10 and residual 5.6e-16 stay under the bounds of family (b)
+SCIPY_RESIDUAL = 1e-10            # a member is compared only when scipy's own solution is that good
 LEFT_OUT = 0.05
 
 
@@ -431,3 +432,94 @@ def kernel_metadata(code_object, tmp_dir, kernel="dompc_lqr_kernel"):
     blk = next(b for b in notes.split("- .agpr_count") if f".name: {kernel}" in " ".join(b.split()))
     field = lambda k: int(next(l for l in blk.splitlines() if l.strip().startswith(k)).split(":")[1])      # noqa: E731
     return field(".private_segment_fixed_size"), field(".vgpr_spill_count")
+
+
+# ---------------------------------------------------------------------------------------------- zero-order hold: unequal designs in one wavefront
+# On the device the squaring loop of expm runs to the largest s of the wavefront (wave_any(q < s)) and a design that is through keeps
+# its T by select.  The host emulation runs one group at a time; "bit for bit against single-member calls" is the point of the GPU twin.
+def mixed_squarings_points(ex):
+    """16 operating points of the CSTR: T_R = 340 .. 440 K, T_J = T_R - 1, F scaled by 0.5 .. 8"""
+    X, U = np.tile(ex.XSS.ravel(), (16, 1)), np.tile(ex.USS.ravel(), (16, 1))
+    X[:, 2] = np.linspace(340.0, 440.0, 16)
+    X[:, 3] = X[:, 2] - 1.0
+    U[:, 0] *= np.linspace(0.5, 8.0, 16)
+    return X, U
+
+
+def squarings(plant, x, u, dt):
+    """s of csrc/dompc_lqr.hip expm for E = [[A, B], [0, 0]] dt, with numpy's 1-norm"""
+    Ac, Bc = twin_jacobians(plant, x, u)
+    n = np.linalg.norm(np.block([[Ac, Bc], [np.zeros((Bc.shape[1], sum(Bc.shape)))]]) * dt, 1)
+    return int(np.floor(np.log2(n))) + 2 if n > 0.5 else 0
+
+
+def _members_equal_single_calls(lqr, plant, X, U, r):
+    for b in range(len(X)):
+        one = lqr.gains_at(plant, X[b:b + 1], U[b:b + 1])
+        for k in ("K", "P", "A", "B", "status", "iters"):
+            assert np.array_equal(one[k][0], r[k][b]), (b, k)
+
+
+def check_mixed_squarings(hostemu, members=None):
+    """gains_at at mixed_squarings_points (members: a sub-batch in that order): the squarings differ inside every group of four
+    (asserted on the CPU), the pair against twin_zoh, K against twin_design by the rule of check_family_b, every member bit for bit
+    against its single-member call"""
+    ex, plant, lqr = example("cstr_lqr", hostemu, n_horizon=None)
+    X, U = mixed_squarings_points(ex)
+    if members is not None:
+        X, U = X[members], U[members]
+    Bn = len(X)
+    s = [squarings(plant, X[b], U[b], ex.T_STEP) for b in range(Bn)]
+    groups = [s[g:g + 4] for g in range(0, Bn, 4)]
+    assert all(len(set(g)) >= 2 for g in groups if len(g) > 1) and len(set(s)) >= 4, s
+    assert s[-1] == max(s)                                 # (the design the idle groups of a partial wavefront repeat is the slowest)
+    r = lqr.gains_at(plant, X, U)
+    assert np.all(r["status"] == 0), r["status"]
+    Q, R, dR = example_weights(ex)
+    Qt = np.block([[Q, np.zeros((4, 2))], [np.zeros((2, 4)), R]])
+    left, worst_k, worst_ab, worst_excess, bmax = 0, 0.0, 0.0, 0.0, 0.0
+    for b in range(Bn):
+        Ac, Bc = twin_jacobians(plant, X[b], U[b])
+        Ad, Bd = twin_zoh(Ac, Bc, ex.T_STEP)
+        worst_ab, bmax = max(worst_ab, relerr(r["A"][b], Ad), relerr(r["B"][b], Bd)), max(bmax, float(np.max(np.abs(Bd))))
+        Kt, Pt = twin_design(Ad, Bd, Q, R, rate=True, delR=dR)
+        At, Bt = design_pair(Ad, Bd, True)
+        rs = riccati_residual(At, Bt, Qt, dR, Pt)
+        if not rs <= SCIPY_RESIDUAL:
+            left += 1
+            continue
+        worst_k = max(worst_k, relerr(r["K"][b], Kt))
+        worst_excess = max(worst_excess, riccati_residual(At, Bt, Qt, dR, r["P"][b]) - rs)
+    print(f"mixed squarings {s}: {Bn} designs, {left} left out, K - twin = {worst_k:.3e} (bound {K_BOUND_B:.1e}), discrete pair - cont2discrete "
+          f"= {worst_ab:.3e} (bound {AB_BOUND_MIXED:.1e}, max |B_d| = {bmax:.1e}), residual kernel - scipy = {worst_excess:.3e} "
+          f"(margin {RES_MARGIN_B:.1e}), doubling steps {r['iters']}")
+    assert left <= LEFT_OUT * Bn
+    assert worst_k < K_BOUND_B and worst_ab < AB_BOUND_MIXED and worst_excess <= RES_MARGIN_B
+    _members_equal_single_calls(lqr, plant, X, U, r)
+
+
+def check_failed_exponential(hostemu):
+    """B = 7 with T_R = NaN (a norm that is not finite), -300 (finite, more than 60 squarings) and -1 (the Arrhenius terms overflow)
+    in slots 1, 3 and 6 among good members.  Pinned as observed: a failed hold reports bits 0 and 1, runs max_iter doubling steps
+    (which its wavefront shares), hands out K = 0, P = Q, A = I, B = 0 and nothing that is not finite; the good members are bit-equal
+    to a call without the failed ones and to their single calls"""
+    ex, plant, lqr = example("cstr_lqr", hostemu, n_horizon=None)
+    X, U = mixed_squarings_points(ex)
+    X, U = X[[0, 3, 5, 7, 9, 12, 15]], U[[0, 3, 5, 7, 9, 12, 15]]
+    bad, good = [1, 3, 6], [0, 2, 4, 5]
+    X[bad, 2] = [np.nan, -300.0, -1.0]
+    r = lqr.gains_at(plant, X, U)
+    print(f"failed exponentials in slots {bad}: status {r['status']}, doubling steps {r['iters']}")
+    for k in ("K", "P", "A", "B"):
+        assert np.all(np.isfinite(r[k])), k
+    Q, R, _ = example_weights(ex)
+    Qt = np.block([[Q, np.zeros((4, 2))], [np.zeros((2, 4)), R]])
+    for b in bad:
+        assert r["status"][b] == 3 and r["iters"][b] == lqr.settings.max_iter == 50, (b, r["status"][b], r["iters"][b])
+        assert not r["K"][b].any() and np.array_equal(r["P"][b], Qt)
+        assert np.array_equal(r["A"][b], np.eye(4)) and not r["B"][b].any()
+    assert np.all(r["status"][good] == 0)
+    alone = lqr.gains_at(plant, X[good], U[good])
+    for k in ("K", "P", "A", "B", "status", "iters"):
+        assert np.array_equal(alone[k], r[k][good]), k
+    _members_equal_single_calls(lqr, plant, X, U, r)

@@ -16,6 +16,12 @@ def test_select_lists_the_flagged_members_in_order(B):
     ec.check_select(B, hostemu=True)
 
 
+@pytest.mark.parametrize("B", ec.LARGE_SELECT_BATCHES)
+def test_select_across_more_than_select_threads_workgroups(B):
+    """(a serial loop on the host emulation: the strided sum over more than SELECT_THREADS workgroups exists on the device only)"""
+    ec.check_select_large(B, hostemu=True)
+
+
 @pytest.mark.parametrize("shape", [(4, 2), (17, 3)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_set_law_members_writes_the_named_columns_only(shape):
     ec.check_scatter(*shape, hostemu=True)

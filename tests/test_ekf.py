@@ -209,6 +209,46 @@ def test_results_of_filter_and_simulator_are_saved_and_loaded(tmp_path):
     assert np.array_equal(res["estimator"]["_time"].ravel(), [1.0, 2.0, 3.0])
 
 
+# ---------------------------------------------------------------------------------------------- unequal problems in one wavefront
+# (the host emulation runs one group at a time: "equals the single call" is trivially true here and is the point of the GPU twins in
+# tests/test_gpu_ekf.py; what the CPU side establishes are the preconditions, the status words and the figures against the twin)
+@pytest.mark.parametrize("B", [8, 7, 5])
+def test_neighbours_with_unequal_step_counts_equal_their_single_calls(B):
+    """eight CSTR filters of 51, 52, 54, 55, 57, 59, 61 and 64 integration steps; B = 7 and 5 with the slowest one last.  Measured on
+    the host emulation: member 3 against the twin 6.9e-14 (twin(1e-12) - twin(1e-13) = 6.1e-15, bound 1e-9)"""
+    ec.check_unequal_steps(ec.make_ekf("CSTR", hostemu=True), B)
+
+
+@pytest.mark.parametrize("last", [None, 1, 2, 3], ids=lambda v: "B8" if v is None else f"B7-member{v}-last")
+def test_failing_filters_leave_their_neighbours_alone(last):
+    """status [0 2 3 2 0 0 0 0] and steps [51 52 1 25 57 59 61 64] on the host emulation; the a-priori estimates handed out with bit 1
+    against the twin's prediction: 6.4e-13 and 4.1e-13 (bound 1e-9)"""
+    ec.check_failures_beside_neighbours(ec.make_ekf("CSTR", hostemu=True), last)
+
+
+def test_step_limit_inside_a_wavefront():
+    """max_steps = 57: status [0 0 0 0 0 1 1 1], steps [51 52 54 55 57 57 57 57] on the host emulation"""
+    ec.check_step_limit_inside_a_wavefront(hostemu=True)
+
+
+@pytest.mark.parametrize("slot", [2, 4])
+def test_singular_s_beside_neighbours(slot):
+    ec.check_status_bit_1_beside_neighbours(hostemu=True, slot=slot)
+
+
+def test_step_limit_of_a_batch():
+    ec.check_step_limit(hostemu=True)
+
+
+@pytest.mark.parametrize("name", ["rotating_masses", "CSTR", "oscillating_masses"])
+def test_elimination_of_s_with_row_swaps(name):
+    """full, non-symmetric R per filter: partial pivoting on S' takes another row order in every filter.  Measured on the host
+    emulation, kernel - twin: rotating_masses (n_y 5, six different orders, cond(S) <= 35.7) 1.3e-12, CSTR (n_y 4, three orders,
+    cond(S) <= 21.7) 5.9e-12, both at the bound 1e-9 of the integration tests; oscillating_masses (discrete, n_y 2, swap and no swap
+    alternate, cond(S) <= 4.4) 8.3e-17 at 1e-10"""
+    ec.check_row_swaps(name, hostemu=True)
+
+
 # ---------------------------------------------------------------------------------------------- compiler evidence
 def _kernel_metadata(code_object, tmp_dir):
     """(private segment bytes, spilled VGPRs) of dompc_ekf_kernel from the code object's amdhsa metadata"""

@@ -22,6 +22,11 @@ def test_zero_leading_entry_is_solved_by_pivoting():
     ac.check_pivoting(hostemu=False)
 
 
+@pytest.mark.parametrize("shape", [(3, 16), (17, 3), (64, 16)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_law_preparation_with_pivot_orders_that_are_not_the_identity(shape):
+    ac.check_pivot_orders(*shape, hostemu=False)
+
+
 def test_singular_failed_and_nan_members_fall_back_and_stay_local():
     ac.check_fallbacks(hostemu=False)
 

@@ -13,6 +13,12 @@ def test_select_lists_the_flagged_members_in_order(B):
     ec.check_select(B, hostemu=False)
 
 
+@pytest.mark.parametrize("B", ec.LARGE_SELECT_BATCHES)
+def test_select_across_more_than_select_threads_workgroups(B):
+    """B = 257 SPAN + 1: workgroup 257 (counted from 0) takes a second round in the strided sum over the counts of the workgroups before it"""
+    ec.check_select_large(B, hostemu=False)
+
+
 @pytest.mark.parametrize("shape", [(4, 2), (17, 3)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_set_law_members_writes_the_named_columns_only(shape):
     ec.check_scatter(*shape, hostemu=False)

@@ -131,3 +131,36 @@ def test_device_resident_closed_loop_with_the_filter_equals_the_per_sample_loops
             x_est = ekf.make_step(y, u0, Q, R).ravel()
             assert ec.relerr(out[k]["u0"][b], u0.ravel()) < 1e-9 and ec.relerr(out[k]["y"][b], y.ravel()) < 1e-9
             assert ec.relerr(out[k]["x_est"][b], x_est) < 1e-9
+
+
+# ---------------------------------------------------------------------------------------------- unequal problems in one wavefront
+# On the device the integration loop runs to the slowest filter of the wavefront and a finished filter keeps its values by select
+# (rule 1): rows of a batch with unequal work against their single calls, bit for bit.
+@pytest.mark.parametrize("B", [8, 7, 5])
+def test_neighbours_with_unequal_step_counts_equal_their_single_calls(B):
+    ec.check_unequal_steps(ec.make_ekf("CSTR", hostemu=False), B)
+
+
+@pytest.mark.parametrize("last", [None, 1, 2, 3], ids=lambda v: "B8" if v is None else f"B7-member{v}-last")
+def test_failing_filters_leave_their_neighbours_alone(last):
+    ec.check_failures_beside_neighbours(ec.make_ekf("CSTR", hostemu=False), last)
+
+
+def test_step_limit_inside_a_wavefront():
+    ec.check_step_limit_inside_a_wavefront(hostemu=False)
+
+
+@pytest.mark.parametrize("slot", [2, 4])
+def test_singular_s_beside_neighbours(slot):
+    """twin of tests/test_ekf.py::test_singular_s_returns_the_a_priori_estimate_with_status_bit_1 with good filters around the bad one"""
+    ec.check_status_bit_1_beside_neighbours(hostemu=False, slot=slot)
+
+
+def test_step_limit_of_a_batch():
+    """twin of tests/test_ekf.py::test_step_limit_sets_status_bit_0"""
+    ec.check_step_limit(hostemu=False)
+
+
+@pytest.mark.parametrize("name", ["rotating_masses", "CSTR", "oscillating_masses"])
+def test_elimination_of_s_with_row_swaps(name):
+    ec.check_row_swaps(name, hostemu=False)

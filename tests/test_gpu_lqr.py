@@ -91,3 +91,13 @@ def test_batch_closed_loop_of_copies_is_the_single_loop(name):
 
 def test_batch_closed_loop_with_a_gain_schedule():
     lc.check_closed_loop_schedule(hostemu=False)
+
+
+@pytest.mark.parametrize("members", [None, [4, 5, 6, 7, 8, 9, 15]], ids=["B16", "B7-slowest-last"])
+def test_zero_order_hold_with_mixed_squarings_in_a_wavefront(members):
+    """the squaring loop of expm runs to the largest s of the wavefront: every member bit for bit against its single-member call"""
+    lc.check_mixed_squarings(hostemu=False, members=members)
+
+
+def test_failed_exponentials_beside_good_designs():
+    lc.check_failed_exponential(hostemu=False)

@@ -354,6 +354,22 @@ def test_per_member_terminal_weight_and_horizon_change():
         assert lc.relerr(r["K"][b], lc.twin_design(A[b], Bm[b], np.eye(3), np.eye(1))[0]) < lc.K_BOUND_A
 
 
+# ---------------------------------------------------------------------------------------------- zero-order hold: unequal designs in one wavefront
+@pytest.mark.parametrize("members", [None, [4, 5, 6, 7, 8, 9, 15]], ids=["B16", "B7-slowest-last"])
+def test_zero_order_hold_with_mixed_squarings_in_a_wavefront(members):
+    """gains_at at 16 operating points of the CSTR (T_R 340 .. 440 K, F x 0.5 .. 8) whose exponentials need 13 13 12 12 | 12 11 11 9 |
+    11 11 12 12 | 12 13 13 13 squarings; B = 7: 12 11 11 9 | 11 11 13.  Measured on the host emulation against scipy: discrete pair -
+    cont2discrete = 5.97e-13 with |B_d| up to 2.1e3 (bound: ten times that, lqr_common.AB_BOUND_MIXED), K - twin = 1.30e-10 and
+    residual excess 5.6e-16 (bounds of family (b)), none left out.  Bit for bit against single-member calls is trivially true here and
+    is the point of the GPU twin."""
+    lc.check_mixed_squarings(hostemu=True, members=members)
+
+
+def test_failed_exponentials_beside_good_designs():
+    """status [0 3 0 3 0 0 3], doubling steps [9 50 10 50 10 11 50] on the host emulation"""
+    lc.check_failed_exponential(hostemu=True)
+
+
 # ---------------------------------------------------------------------------------------------- closed loop
 @pytest.mark.parametrize("name", ["oscillating_masses_lqr", "cstr_lqr"])
 def test_batch_closed_loop_of_copies_is_the_single_loop(name):
