@@ -1,12 +1,30 @@
-"""Batched closed loop with the whole x0 batch resident in HBM.
+"""Batched closed loops with the whole batch resident in device memory.
 
 The reference closes the loop one sample at a time on the host - `u0 = mpc.make_step(x0)`, `y = simulator.make_step(u0)`,
 `x0 = estimator.make_step(y)` (/root/reference/examples/industrial_poly/main.py:105-108) - and fans batches of such loops
 out over processes (`do_mpc.sampling.Sampler`, /root/reference/do_mpc/sampling/_sampler.py:198-228).  Here B loops
-advance together: one `dompc_solve_batch_device` launch (structured IPM, B problems) and one
-`dompc_plant_step_batch_device` launch (plant integrator, B samples) per control step on the same stream; states,
-inputs, parameters and the warm-start solution stay in device memory (torch tensors are only the allocator).
-State feedback (`StateFeedback.make_step` returns y, estimator/_base.py:63-72), measurement = state.
+advance together: one launch per controller, plant and estimator and control step, all on the same stream; states, inputs,
+parameters and the warm-start solution stay in device memory (torch tensors are only the allocator).
+
+The parts, each written once, and the six loops composed of them:
+
+  _Device          the torch device of a loop, host array -> device tensor (always a copy), its stream and its synchronisation
+  _PlantSide       the plant: states, status, its `_p` / `_tvp` at the loop time, the batched step, optionally measurement and noise
+  _ControllerSide  the MPC problem of B loops: `opt_p` rows, warm start, bounds, solution, statistics, its `_tvp` / `_p` at the loop
+                   time, the batched solve and the bookkeeping of the next problem
+  _record_run      n steps of a state-feedback loop collected into records
+
+  BatchClosedLoop       _ControllerSide -> _PlantSide, state feedback
+  BatchClosedLoopMHE    _ControllerSide -> _PlantSide (measuring) -> moving horizon estimator (its chain problem lives in the class)
+  BatchClosedLoopEKF    _ControllerSide -> _PlantSide (measuring, noise) -> extended Kalman filter (its buffers live in the class)
+  BatchClosedLoopLQR    gain (a torch expression) -> _PlantSide; run = _record_run
+  BatchClosedLoopAMPC   network kernel -> _PlantSide; run = _record_run
+  BatchClosedLoopASMPC  _ControllerSide (solved through ASMPC.solve_device, with multipliers) -> affine law -> _PlantSide; events, rollout
+
+The reference's per-sample loop re-evaluates tvp_fun / p_fun at the current time in EVERY make_step of controller, plant and
+estimator (_mpc.py:1009-1019, simulator.py:790-800, _mhe.py:940-950, _ekf.py:268-270) - a set-point staircase over the horizon moves
+along.  Every part therefore keeps the start time and the step of ITS object and refreshes at `t0 + k * dt` from k = 1 on (the
+values at k = 0 are uploaded at construction); the values are the same for every loop of the batch.
 """
 from __future__ import annotations
 
@@ -15,11 +33,96 @@ import numpy as np
 from .solver import STATS_DTYPE
 
 
-class BatchClosedLoop:
-    def __init__(self, mpc, simulator, X0, device: int = 0, U_prev0=None):
+class _Device:
+    """device: index of a HIP device, or "cpu" where the loop serves a controller and a plant on the host emulation"""
+
+    def __init__(self, device, host_ok: bool = False):
         import torch
         self.torch = torch
-        self.mpc, self.sim = mpc, simulator
+        if device == "cpu" and not host_ok:
+            raise NotImplementedError('structured HIP backend: this closed loop has no host flavour (device="cpu")')
+        self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
+
+    def to_dev(self, a):
+        """host array -> float64 tensor; a copy, also on the host (`from_numpy(...).to("cpu")` would alias the array)"""
+        return self.torch.tensor(np.asarray(a, dtype=np.float64), device=self.dev)
+
+    def empty(self, *shape):
+        return self.torch.empty(shape, dtype=self.torch.float64, device=self.dev)
+
+    def zeros(self, *shape, dtype=None):
+        return self.torch.zeros(shape, dtype=dtype or self.torch.float64, device=self.dev)
+
+    def stream(self):
+        return self.torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else 0
+
+    def sync(self):
+        if self.dev.type == "cuda":
+            self.torch.cuda.synchronize(self.dev)
+
+
+def _stats_host(stats):
+    """the solver statistics of a batch (uint8 device buffer) as a numpy record array"""
+    return np.frombuffer(stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
+
+
+class _PlantSide:
+    """The plant of B loops.  X0: [B][nx].  measure: keep the measurements Y [B][max(ny, 1)] of every step; without it the loop is
+    state feedback (`StateFeedback.make_step` returns y, estimator/_base.py:63-72) and the plant's measurement must be its state.
+    noise: keep a buffer V [B][nv] that the loop fills and every step reads as measurement noise."""
+
+    def __init__(self, simulator, dv: _Device, X0, measure: bool = False, noise: bool = False):
+        m = simulator.model
+        assert measure or m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
+        self.sim, self.dv = simulator, dv
+        self.X = dv.to_dev(X0)
+        self.B = int(self.X.shape[0])
+        self.Xn = dv.torch.empty_like(self.X)
+        self.pstat = dv.zeros(self.B, dtype=dv.torch.int32)
+        self.Y = dv.empty(self.B, max(m.n_y, 1)) if measure else None
+        self.V = dv.zeros(self.B, m.n_v) if noise and m.n_v else None
+        self.t0, self.dt = float(simulator._t0[0]), float(simulator.settings.t_step)
+        tv, pp = self.rows(0, 1)
+        self.tvp, self.p = dv.to_dev(tv[0]), dv.to_dev(pp[0])
+
+    def rows(self, k: int, K: int):
+        """the plant's _tvp / _p at the K loop times from step k on: [K][n] each (one zero per row without such parameters)"""
+        m = self.sim.model
+        ts = [self.t0 + (k + j) * self.dt for j in range(K)]
+        # (a copy per row: a tvp_fun / p_fun usually fills and returns one template)
+        tv = np.array([np.array(self.sim.tvp_fun(s).master, dtype=float).reshape(-1) for s in ts]) if m.n_tvp else np.zeros((K, 1))
+        pp = np.array([np.array(self.sim.p_fun(s).master, dtype=float).reshape(-1) for s in ts]) if m.n_p else np.zeros((K, 1))
+        return tv, pp
+
+    def refresh(self, k: int) -> None:
+        """_tvp / _p at the loop time of step k -> device"""
+        m = self.sim.model
+        if k > 0 and (m.n_p or m.n_tvp):
+            tv, pp = self.rows(k, 1)
+            if m.n_p:
+                self.p.copy_(self.dv.to_dev(pp[0]))
+            if m.n_tvp:
+                self.tvp.copy_(self.dv.to_dev(tv[0]))
+
+    def step(self, U, stream, shared_mask: int = 2 | 4 | 8 | 16) -> None:
+        """one plant step of all loops with the inputs U [B][nu]; X is the new state afterwards.  shared_mask: _tvp and _p are one row
+        for the batch (bits 1, 2), and so are the noise inputs (bits 3, 4) unless the loop clears their bits"""
+        self.sim.step_batch_device(self.B, self.X.data_ptr(), U.data_ptr(), self.tvp.data_ptr(), self.p.data_ptr(), self.Xn.data_ptr(),
+                                   self.Y.data_ptr() if self.Y is not None else 0, self.pstat.data_ptr(),
+                                   v=self.V.data_ptr() if self.V is not None else 0, shared_mask=shared_mask, stream=stream)
+        self.X, self.Xn = self.Xn, self.X
+
+    def status(self):
+        """(status, implicit) of the last step per loop: bit 0 and bit 1 of the plant's status word"""
+        s = self.pstat.cpu().numpy()
+        return s & 1, (s >> 1) & 1
+
+
+class _ControllerSide:
+    """The MPC problem of B loops.  x0: [B][nx], the states the first solve starts from; U_prev0: [B][nu] or None (0).  lam_g: keep a
+    buffer for the constraint multipliers (the ASMPC loop, whose solve is `ASMPC.solve_device` on these tensors)."""
+
+    def __init__(self, mpc, dv: _Device, x0, U_prev0=None, lam_g: bool = False):
         ps = self.ps = mpc.structure
         if getattr(ps, "open_loop_stack", False):
             raise NotImplementedError("structured HIP backend: the device-resident closed loop with open_loop and several scenarios "
@@ -27,81 +130,106 @@ class BatchClosedLoop:
         if getattr(mpc.S, "row_mapped", False):
             raise NotImplementedError("structured HIP backend: the device-resident closed loop with rows appended to nlp_cons (internal row "
                                       "layout, solver.RowMappedSolver); use make_step_batch")
-        m = simulator.model
-        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
-        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
-        X0 = np.asarray(X0, dtype=float).reshape(-1, ps.nx)
-        self.B = B = X0.shape[0]
-        dev = self.dev = torch.device("cuda", device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
-        t0 = float(mpc._t0[0])
+        self.mpc, self.dv = mpc, dv
+        self.B = B = x0.shape[0]
+        self.t0, self.dt = float(mpc._t0[0]), float(mpc.settings.t_step)
         P = np.tile(mpc.opt_p_num.master, (B, 1))
-        P[:, :ps.nx] = X0
-        P[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(t0).master
-        P[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(t0).master
+        P[:, :ps.nx] = x0
+        P[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(self.t0).master
+        P[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(self.t0).master
         P[:, ps.p_off_uprev:] = 0.0 if U_prev0 is None else np.asarray(U_prev0, float).reshape(B, ps.nu)
-        Xi = np.zeros((B, ps.n_opt_x))
-        Xi[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (X0 / mpc._x_scaling.master)[:, None, :]
-        Xi[:, ps.off_u:ps.off_eps].reshape(B, -1, ps.nu)[:] = (P[:, ps.p_off_uprev:] / mpc._u_scaling.master)[:, None, :]   # (mpc.u0 = u_prev; set_initial_guess)
-        self.P, self.guess = t(P), t(Xi)                      # opt_p per sample; initial guess = set_initial_guess semantics
-        self.X = t(X0)                                        # plant states
-        self.lbx, self.ubx = t(mpc._lb_opt_x.master), t(mpc._ub_opt_x.master)
-        self.lbg, self.ubg = t(mpc._nlp_cons_lb), t(mpc._nlp_cons_ub)
-        self.sol = torch.empty((B, ps.n_opt_x), dtype=torch.float64, device=dev)
-        self.f = torch.empty(B, dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.U = torch.empty((B, ps.nu), dtype=torch.float64, device=dev)
-        self.Xn = torch.empty_like(self.X)
-        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.xs, self.us = t(mpc._x_scaling.master), t(mpc._u_scaling.master)
-        ts = float(simulator._t0[0])
-        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
-        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
-        self.k = 0
-        # loop time: the reference's per-sample loop re-evaluates tvp_fun / p_fun at the current time in EVERY make_step of
-        # controller and plant (_mpc.py:1009-1019, simulator.py:790-800) - a set-point staircase over the horizon moves along
-        self.t_mpc0, self.t_sim0 = t0, ts
-        self.dt_mpc, self.dt_sim = float(mpc.settings.t_step), float(simulator.settings.t_step)
-        self._p_row = P[0].copy()                             # host image of one opt_p row (its _tvp / _p blocks are re-uploaded)
+        Xi = np.zeros((B, ps.n_opt_x))                         # initial guess = set_initial_guess semantics (mpc.x0 = x0, mpc.u0 = u_prev)
+        Xi[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (x0 / mpc._x_scaling.master)[:, None, :]
+        Xi[:, ps.off_u:ps.off_eps].reshape(B, -1, ps.nu)[:] = (P[:, ps.p_off_uprev:] / mpc._u_scaling.master)[:, None, :]
+        self.P, self.guess = dv.to_dev(P), dv.to_dev(Xi)
+        self.bounds = [dv.to_dev(v) for v in (mpc._lb_opt_x.master, mpc._ub_opt_x.master, mpc._nlp_cons_lb, mpc._nlp_cons_ub)]
+        self.us = dv.to_dev(mpc._u_scaling.master)
+        self.sol, self.f = dv.empty(B, ps.n_opt_x), dv.empty(B)
+        self.lam_g = dv.empty(B, ps.n_g) if lam_g else None
+        self.stats = dv.zeros(B * STATS_DTYPE.itemsize, dtype=dv.torch.uint8)
+        self._p_row = P[0].copy()                              # host image of one opt_p row (its _tvp / _p blocks are re-uploaded)
 
-    def _refresh_time_varying(self):
-        """_tvp / _p of controller and plant at the current loop time -> device (same values for every sample of the batch)"""
-        ps, m, torch = self.ps, self.sim.model, self.torch
-        tm, ts = self.t_mpc0 + self.k * self.dt_mpc, self.t_sim0 + self.k * self.dt_sim
-        if ps.ntvp or ps.np_:
+    def refresh(self, k: int) -> None:
+        """_tvp / _p at the loop time of step k -> their block of every opt_p row"""
+        ps = self.ps
+        if k > 0 and (ps.ntvp or ps.np_):
+            tm = self.t0 + k * self.dt
             row = self._p_row
             row[ps.p_off_tvp:ps.p_off_p] = self.mpc.tvp_fun(tm).master
             row[ps.p_off_p:ps.p_off_uprev] = self.mpc.p_fun(tm).master
-            blk = torch.from_numpy(row[ps.p_off_tvp:ps.p_off_uprev].copy()).to(self.dev)
-            self.P[:, ps.p_off_tvp:ps.p_off_uprev] = blk
-        if m.n_p:
-            self.p_plant.copy_(torch.from_numpy(np.ascontiguousarray(self.sim.p_fun(ts).master, dtype=np.float64)).to(self.dev))
-        if m.n_tvp:
-            self.tvp_plant.copy_(torch.from_numpy(np.ascontiguousarray(self.sim.tvp_fun(ts).master, dtype=np.float64)).to(self.dev))
+            self.P[:, ps.p_off_tvp:ps.p_off_uprev] = self.dv.to_dev(row[ps.p_off_tvp:ps.p_off_uprev])
+
+    def solve(self, stream) -> None:
+        lbx, ubx, lbg, ubg = self.bounds
+        self.mpc.S.solve_batch_device(self.B, self.guess.data_ptr(), lbx.data_ptr(), ubx.data_ptr(), lbg.data_ptr(), ubg.data_ptr(),
+                                      self.P.data_ptr(), self.sol.data_ptr(), 0, 0, 0, self.f.data_ptr(), self.stats.data_ptr(),
+                                      stream=stream)
+
+    def u0(self, out) -> None:
+        """the first input of the solution in physical units -> out [B][nu]"""
+        ps = self.ps
+        iu = ps.iu(0, 0)
+        self.dv.torch.mul(self.sol[:, iu:iu + ps.nu], self.us, out=out)
+
+    def set_x0(self, x, U) -> None:
+        """the parameters of a solve at the states x after the inputs U: x0 <- x, u_prev <- U"""
+        self.P[:, :self.ps.nx] = x
+        self.P[:, self.ps.p_off_uprev:] = U
+
+    def next_problem(self, x, U) -> None:
+        """x0 <- state or estimate, u_prev <- applied input, initial guess <- previous solution (unshifted, optimizer.py:754-768)"""
+        self.set_x0(x, U)
+        self.guess.copy_(self.sol)
+
+    def stats_host(self):
+        return _stats_host(self.stats)
+
+
+def _record_run(loop, n: int) -> dict:
+    """n control steps of a state-feedback loop; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant
+    status of every step"""
+    xs, us, st = [loop.plant.X.cpu().numpy().copy()], [], []
+    for _ in range(int(n)):
+        r = loop.step()
+        xs.append(r["x"].copy())
+        us.append(r["u0"].copy())
+        st.append(r["plant_status"])
+    return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, loop.B, loop.plant.sim.model.n_u)),
+            "plant_status": np.stack(st) if st else np.zeros((0, loop.B), dtype=np.int32)}
+
+
+class BatchClosedLoop:
+    """B closed loops controller -> plant with state feedback: per control step ONE `dompc_solve_batch_device` launch (structured IPM, B
+    problems) and ONE `dompc_plant_step_batch_device` launch (plant integrator, B samples) on the same stream.
+    X0: [B][nx]; U_prev0: [B][nu], the inputs before the first step (default 0)."""
+
+    def __init__(self, mpc, simulator, X0, device: int = 0, U_prev0=None):
+        self.mpc, self.sim = mpc, simulator
+        ps = self.ps = mpc.structure
+        dv = self.dv = _Device(device)
+        X0 = np.asarray(X0, dtype=float).reshape(-1, ps.nx)
+        self.B = B = X0.shape[0]
+        self.ctrl = _ControllerSide(mpc, dv, X0, U_prev0)
+        m = simulator.model
+        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
+        self.plant = _PlantSide(simulator, dv, X0)
+        self.U = dv.empty(B, ps.nu)
+        self.k = 0
 
     def step(self) -> dict:
         """one control step of all B loops; returns the solver statistics (numpy record array) and the plant status"""
-        torch, ps, S = self.torch, self.ps, self.mpc.S
-        stream = torch.cuda.current_stream()
-        if self.k > 0:
-            self._refresh_time_varying()
-        S.solve_batch_device(self.B, self.guess.data_ptr(), self.lbx.data_ptr(), self.ubx.data_ptr(), self.lbg.data_ptr(),
-                             self.ubg.data_ptr(), self.P.data_ptr(), self.sol.data_ptr(), 0, 0, 0, self.f.data_ptr(),
-                             self.stats.data_ptr(), stream=stream.cuda_stream)
-        iu = ps.iu(0, 0)
-        torch.mul(self.sol[:, iu:iu + ps.nu], self.us, out=self.U)                      # u0 in physical units
-        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(),
-                                   self.p_plant.data_ptr(), self.Xn.data_ptr(), 0, self.pstat.data_ptr(),
-                                   shared_mask=2 | 4 | 8 | 16, stream=stream.cuda_stream)
-        # next problem: x0 <- plant state, u_prev <- applied input, initial guess <- previous solution (optimizer.py:754-768)
-        self.X, self.Xn = self.Xn, self.X
-        self.P[:, :ps.nx] = self.X
-        self.P[:, ps.p_off_uprev:] = self.U
-        self.guess.copy_(self.sol)
+        ctrl, plant, stream = self.ctrl, self.plant, self.dv.stream()
+        ctrl.refresh(self.k)
+        plant.refresh(self.k)
+        ctrl.solve(stream)
+        ctrl.u0(out=self.U)
+        plant.step(self.U, stream)
+        ctrl.next_problem(plant.X, self.U)
         self.k += 1
-        torch.cuda.synchronize()
-        st = np.frombuffer(self.stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
-        return {"stats": st, "plant_status": (self.pstat.cpu().numpy() & 1), "plant_implicit": ((self.pstat.cpu().numpy() >> 1) & 1), "u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy()}
+        self.dv.sync()
+        status, implicit = plant.status()
+        return {"stats": ctrl.stats_host(), "plant_status": status, "plant_implicit": implicit, "u0": self.U.cpu().numpy(),
+                "x": plant.X.cpu().numpy()}
 
 
 class BatchClosedLoopMHE:
@@ -114,49 +242,19 @@ class BatchClosedLoopMHE:
     and does the slicing."""
 
     def __init__(self, mpc, simulator, mhe, X0_true, x0_est=None, p_est0=None, device: int = 0):
-        import torch
-        self.torch = torch
         self.mpc, self.sim, self.mhe = mpc, simulator, mhe
         m = simulator.model
-        ps, es = mpc.structure, mhe._ps                     # controller / estimator chain structures
-        if getattr(ps, "open_loop_stack", False):
-            raise NotImplementedError("structured HIP backend: the device-resident closed loop with open_loop and several scenarios")
-        if getattr(mpc.S, "row_mapped", False):
-            raise NotImplementedError("structured HIP backend: the device-resident closed loop with rows appended to nlp_cons")
-        self.ps, self.es = ps, es
+        ps, es = self.ps, self.es = mpc.structure, mhe._ps  # controller / estimator chain structures
+        dv = self.dv = _Device(device)
+        t = dv.to_dev
         X0_true = np.asarray(X0_true, dtype=float).reshape(-1, m.n_x)
         self.B = B = X0_true.shape[0]
-        dev = self.dev = torch.device("cuda", device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
-        nx, nu, ny, npe = m.n_x, m.n_u, m.n_y, mhe.n_p_est
-        self.nx, self.nu, self.ny, self.npe = nx, nu, ny, npe
+        nx, npe = self.nx, self.npe = m.n_x, mhe.n_p_est
         x_est = np.zeros((B, nx)) if x0_est is None else np.broadcast_to(np.asarray(x0_est, float).reshape(-1, nx), (B, nx)).copy()
         p_est = np.zeros((B, npe)) if p_est0 is None else np.broadcast_to(np.asarray(p_est0, float).reshape(-1, npe), (B, npe)).copy()
-        # ---- controller: opt_p rows, initial guess (set_initial_guess semantics), bounds
-        t0 = float(mpc._t0[0])
-        Pc = np.tile(mpc.opt_p_num.master, (B, 1))
-        Pc[:, :nx] = x_est
-        Pc[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(t0).master
-        Pc[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(t0).master
-        Pc[:, ps.p_off_uprev:] = 0.0
-        Gc = np.zeros((B, ps.n_opt_x))
-        Gc[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (x_est / mpc._x_scaling.master)[:, None, :]
-        self.Pc, self.Gc = t(Pc), t(Gc)
-        self.c_lbx, self.c_ubx = t(mpc._lb_opt_x.master), t(mpc._ub_opt_x.master)
-        self.c_lbg, self.c_ubg = t(mpc._nlp_cons_lb), t(mpc._nlp_cons_ub)
-        self.c_sol = torch.empty((B, ps.n_opt_x), dtype=torch.float64, device=dev)
-        self.c_f = torch.empty(B, dtype=torch.float64, device=dev)
-        self.c_stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.xs, self.us = t(mpc._x_scaling.master), t(mpc._u_scaling.master)
-        # ---- plant
-        self.X = t(X0_true)
-        self.Xn = torch.empty_like(self.X)
-        self.U = torch.empty((B, nu), dtype=torch.float64, device=dev)
-        self.Y = torch.empty((B, ny), dtype=torch.float64, device=dev)
-        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        ts = float(simulator._t0[0])
-        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
-        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
+        self.ctrl = _ControllerSide(mpc, dv, x_est)
+        self.plant = _PlantSide(simulator, dv, X0_true, measure=True)
+        self.U = dv.empty(B, m.n_u)
         # ---- estimator: chain opt_p rows (previous estimate | (tvp_k, y_k) per stage | p_set | 0), initial guess, bounds
         N = self.N = mhe.settings.n_horizon
         te = float(mhe._t0[0])
@@ -173,63 +271,43 @@ class BatchClosedLoopMHE:
         em = mhe._mpc
         self.e_lbx, self.e_ubx = t(em._lb_opt_x.master), t(em._ub_opt_x.master)
         self.e_lbg, self.e_ubg = t(em._nlp_cons_lb), t(em._nlp_cons_ub)
-        self.e_sol = torch.empty((B, es.n_opt_x), dtype=torch.float64, device=dev)
-        self.e_f = torch.empty(B, dtype=torch.float64, device=dev)
-        self.e_stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
+        self.e_sol, self.e_f = dv.empty(B, es.n_opt_x), dv.empty(B)
+        self.e_stats = dv.zeros(B * STATS_DTYPE.itemsize, dtype=dv.torch.uint8)
         self.x_est, self.p_est = t(x_est), t(p_est)
         self.exs = t(mhe._x_scaling.master)
         self.eps_ = t(pes if npe else np.zeros(1))              # scaling of the estimated parameters (they ride as scaled states of the chain problem)
-        self.t_mpc0, self.dt = t0, float(mpc.settings.t_step)
-        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
         self.t_mhe0, self.dt_mhe = te, float(mhe.settings.t_step)
-        self._pc_row = Pc[0].copy()
         self.k = 0
 
-    def _refresh_time_varying(self):
-        """_tvp / _p of controller, plant AND estimator at the current loop time -> device (same values for every sample).  The
-        reference's per-sample loop re-evaluates all of them in every make_step (_mpc.py:1009-1019, simulator.py:790-800,
-        _mhe.py:940-950); only the measurement columns of the estimator's window are data of the loop."""
-        torch, ps, es, m, mhe = self.torch, self.ps, self.es, self.sim.model, self.mhe
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
-        tm, ts, te = self.t_mpc0 + self.k * self.dt, self.t_sim0 + self.k * self.dt_sim, self.t_mhe0 + self.k * self.dt_mhe
-        if ps.ntvp or ps.np_:
-            row = self._pc_row
-            row[ps.p_off_tvp:ps.p_off_p] = self.mpc.tvp_fun(tm).master
-            row[ps.p_off_p:ps.p_off_uprev] = self.mpc.p_fun(tm).master
-            self.Pc[:, ps.p_off_tvp:ps.p_off_uprev] = up(row[ps.p_off_tvp:ps.p_off_uprev].copy())
-        if m.n_p:
-            self.p_plant.copy_(up(self.sim.p_fun(ts).master))
-        if m.n_tvp:
-            self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
+    def _refresh_estimator(self):
+        """_tvp / _p of the estimator at the current loop time -> device (same values for every sample); only the measurement columns
+        of the estimator's window are data of the loop"""
+        es, mhe, up = self.es, self.mhe, self.dv.to_dev
+        te = self.t_mhe0 + self.k * self.dt_mhe
         mt = mhe.model.n_tvp
-        if mt or mhe.n_p_set:
+        if self.k > 0 and (mt or mhe.n_p_set):
             op = np.zeros((1, mhe.n_opt_p))
             op[:, mhe._po_pset:mhe._po_tvp] = mhe.p_fun(te).master
             op[:, mhe._po_tvp:mhe._po_y] = mhe.tvp_fun(te).master
             pc = mhe._p_to_chain(op)[0]
             if mt:
                 tv = pc[es.p_off_tvp:es.p_off_p].reshape(self.N + 1, es.ntvp)[:, :mt]
-                self.Pe[:, es.p_off_tvp:es.p_off_p].view(self.B, self.N + 1, es.ntvp)[:, :, :mt] = up(tv.copy())
+                self.Pe[:, es.p_off_tvp:es.p_off_p].view(self.B, self.N + 1, es.ntvp)[:, :, :mt] = up(tv)
             if es.p_off_uprev > es.p_off_p:
-                self.Pe[:, es.p_off_p:es.p_off_uprev] = up(pc[es.p_off_p:es.p_off_uprev].copy())
+                self.Pe[:, es.p_off_p:es.p_off_uprev] = up(pc[es.p_off_p:es.p_off_uprev])
 
     def step(self) -> dict:
-        torch, ps, es, B, nx, nu, ny, npe, N = self.torch, self.ps, self.es, self.B, self.nx, self.nu, self.ny, self.npe, self.N
-        stream = torch.cuda.current_stream()
+        ctrl, plant, es, B, nx, npe, N = self.ctrl, self.plant, self.es, self.B, self.nx, self.npe, self.N
+        stream = self.dv.stream()
         mt = self.mhe.model.n_tvp
-        if self.k > 0:
-            self._refresh_time_varying()
+        ctrl.refresh(self.k)
+        plant.refresh(self.k)
+        self._refresh_estimator()
         # 1. controller
-        self.mpc.S.solve_batch_device(B, self.Gc.data_ptr(), self.c_lbx.data_ptr(), self.c_ubx.data_ptr(), self.c_lbg.data_ptr(),
-                                      self.c_ubg.data_ptr(), self.Pc.data_ptr(), self.c_sol.data_ptr(), 0, 0, 0, self.c_f.data_ptr(),
-                                      self.c_stats.data_ptr(), stream=stream.cuda_stream)
-        iu = ps.iu(0, 0)
-        torch.mul(self.c_sol[:, iu:iu + nu], self.us, out=self.U)
+        ctrl.solve(stream)
+        ctrl.u0(out=self.U)
         # 2. plant: next true state and its measurement
-        self.sim.step_batch_device(B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
-                                   self.Xn.data_ptr(), self.Y.data_ptr(), self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16,
-                                   stream=stream.cuda_stream)
-        self.X, self.Xn = self.Xn, self.X
+        plant.step(self.U, stream)
         # 3. estimator: previous estimates <- `_x[1, -1]`, `_p_est` of ITS previous solution (initial guess before the first solve,
         #    _mhe.py:939-941), measurement window shifted by one stage, the new measurement last
         i1 = es.ix(1, 0, es.M)
@@ -237,10 +315,10 @@ class BatchClosedLoopMHE:
         self.Pe[:, nx:nx + npe] = self.p_est
         TV = self.Pe[:, es.p_off_tvp:es.p_off_p].view(B, N + 1, es.ntvp)
         TV[:, :N - 1, mt:] = TV[:, 1:N, mt:].clone()
-        TV[:, N - 1, mt:] = self.Y
+        TV[:, N - 1, mt:] = plant.Y
         self.mhe.S.solve_batch_device(B, self.Ge.data_ptr(), self.e_lbx.data_ptr(), self.e_ubx.data_ptr(), self.e_lbg.data_ptr(),
                                       self.e_ubg.data_ptr(), self.Pe.data_ptr(), self.e_sol.data_ptr(), 0, 0, 0, self.e_f.data_ptr(),
-                                      self.e_stats.data_ptr(), stream=stream.cuda_stream)
+                                      self.e_stats.data_ptr(), stream=stream)
         iN = es.ix(N, 0, es.M)
         self.x_est = self.e_sol[:, iN:iN + nx] * self.exs
         i0 = es.ix(0, 0, es.M)
@@ -248,16 +326,14 @@ class BatchClosedLoopMHE:
         #  returned estimate are physical, _mhe.py: opt_x_num['_p_est'] * _p_est_scaling - ADVICE r3)
         self.p_est = self.e_sol[:, i0 + nx:i0 + nx + npe] * self.eps_[:npe] if npe else self.e_sol[:, i0 + nx:i0 + nx].clone()
         self.Ge.copy_(self.e_sol)                                  # warm start (unshifted, optimizer.py:754-768)
-        # 4. next controller problem: x0 <- estimate, u_prev <- applied input, initial guess <- previous solution
-        self.Pc[:, :nx] = self.x_est
-        self.Pc[:, ps.p_off_uprev:] = self.U
-        self.Gc.copy_(self.c_sol)
+        # 4. next controller problem, from the estimate
+        ctrl.next_problem(self.x_est, self.U)
         self.k += 1
-        torch.cuda.synchronize()
-        cs = np.frombuffer(self.c_stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
-        est = np.frombuffer(self.e_stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
-        return {"mpc_stats": cs, "mhe_stats": est, "plant_status": (self.pstat.cpu().numpy() & 1), "plant_implicit": ((self.pstat.cpu().numpy() >> 1) & 1), "u0": self.U.cpu().numpy(),
-                "x_true": self.X.cpu().numpy(), "y": self.Y.cpu().numpy(), "x_est": self.x_est.cpu().numpy(), "p_est": self.p_est.cpu().numpy()}
+        self.dv.sync()
+        status, implicit = plant.status()
+        return {"mpc_stats": ctrl.stats_host(), "mhe_stats": _stats_host(self.e_stats), "plant_status": status, "plant_implicit": implicit,
+                "u0": self.U.cpu().numpy(), "x_true": plant.X.cpu().numpy(), "y": plant.Y.cpu().numpy(), "x_est": self.x_est.cpu().numpy(),
+                "p_est": self.p_est.cpu().numpy()}
 
 
 class BatchClosedLoopEKF:
@@ -272,131 +348,75 @@ class BatchClosedLoopEKF:
     the start, then the algebraic states of each step's last Newton solve as the guess of the next; step() returns it as `z_est`."""
 
     def __init__(self, mpc, simulator, ekf, X0_true, x0_est, P0, Q, R, V=None, device: int = 0):
-        import torch
-        self.torch = torch
         self.mpc, self.sim, self.ekf = mpc, simulator, ekf
-        m = simulator.model
+        m, me = simulator.model, ekf.model
         ps = self.ps = mpc.structure
-        if getattr(ps, "open_loop_stack", False):
-            raise NotImplementedError("structured HIP backend: the device-resident closed loop with open_loop and several scenarios")
-        if getattr(mpc.S, "row_mapped", False):
-            raise NotImplementedError("structured HIP backend: the device-resident closed loop with rows appended to nlp_cons")
-        me = ekf.model
-        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
-        assert (me.n_x, me.n_u, me.n_y) == (m.n_x, m.n_u, m.n_y), "plant and filter must share states, inputs and measurements"
+        dv = self.dv = _Device(device)
+        t = dv.to_dev
         X0_true = np.asarray(X0_true, dtype=float).reshape(-1, m.n_x)
         self.B = B = X0_true.shape[0]
-        dev = self.dev = torch.device("cuda", device)
-        t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)      # noqa: E731
-        nx, nu, ny = m.n_x, m.n_u, m.n_y
-        self.nx, self.nu, self.ny = nx, nu, ny
+        nx, ny = m.n_x, m.n_y
         x_est = np.broadcast_to(np.asarray(x0_est, float).reshape(-1, nx), (B, nx)).copy()
+        self.ctrl = _ControllerSide(mpc, dv, x_est)
+        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
+        assert (me.n_x, me.n_u, me.n_y) == (m.n_x, m.n_u, m.n_y), "plant and filter must share states, inputs and measurements"
         P0 = np.asarray(P0, float)
         Pcov = np.broadcast_to(P0.reshape(-1, nx, nx), (B, nx, nx)).copy()
         Q, R = np.asarray(Q, float), np.asarray(R, float)
         assert Q.shape in ((nx, nx), (B, nx, nx)) and R.shape in ((ny, ny), (B, ny, ny)), "Q / R: one matrix or one per loop"
         self.mask = 2 | 4 | (8 if Q.ndim == 2 else 0) | (16 if R.ndim == 2 else 0)
         self.Q, self.R = t(Q), t(R)
-        # ---- controller: opt_p rows, initial guess (set_initial_guess semantics), bounds
-        t0 = float(mpc._t0[0])
-        Pc = np.tile(mpc.opt_p_num.master, (B, 1))
-        Pc[:, :nx] = x_est
-        Pc[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(t0).master
-        Pc[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(t0).master
-        Pc[:, ps.p_off_uprev:] = 0.0
-        Gc = np.zeros((B, ps.n_opt_x))
-        Gc[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (x_est / mpc._x_scaling.master)[:, None, :]
-        self.Pc, self.Gc = t(Pc), t(Gc)
-        self.c_lbx, self.c_ubx = t(mpc._lb_opt_x.master), t(mpc._ub_opt_x.master)
-        self.c_lbg, self.c_ubg = t(mpc._nlp_cons_lb), t(mpc._nlp_cons_ub)
-        self.c_sol = torch.empty((B, ps.n_opt_x), dtype=torch.float64, device=dev)
-        self.c_f = torch.empty(B, dtype=torch.float64, device=dev)
-        self.c_stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.us = t(mpc._u_scaling.master)
-        # ---- plant
-        self.X = t(X0_true)
-        self.Xn = torch.empty_like(self.X)
-        self.U = torch.empty((B, nu), dtype=torch.float64, device=dev)
-        self.Y = torch.empty((B, max(ny, 1)), dtype=torch.float64, device=dev)
-        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        ts = float(simulator._t0[0])
-        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
-        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
         self._V = V
-        self.V = torch.zeros((B, max(m.n_v, 1)), dtype=torch.float64, device=dev)
+        self.plant = _PlantSide(simulator, dv, X0_true, measure=True, noise=V is not None)
+        self.U = dv.empty(B, m.n_u)
         # ---- filter
         te = float(ekf._t0[0])
         self.x_est, self.Pcov = t(x_est), t(Pcov)
         self.p_ekf = t(ekf.p_fun(te).master if me.n_p else np.zeros(1))
         self.tvp_ekf = t(ekf.tvp_fun(te).master if me.n_tvp else np.zeros(1))
-        self.estat = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.estat = dv.zeros(B, dtype=dv.torch.int32)
         self.nz = me.n_z
         if self.nz:
             self.z_est = t(np.tile(ekf.z0.master, (B, 1)))
-            self.enewton = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.t_mpc0, self.dt = t0, float(mpc.settings.t_step)
-        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
+            self.enewton = dv.zeros(B, dtype=dv.torch.int32)
         self.t_ekf0, self.dt_ekf = te, float(ekf.settings.t_step)
-        self._pc_row = Pc[0].copy()
         self.k = 0
 
-    def _refresh_time_varying(self):
-        """_tvp / _p of controller, plant and filter at the current loop time -> device (same values for every loop): the per-sample
-        loop re-evaluates all of them in every make_step (_mpc.py:1009-1019, simulator.py:790-800, _ekf.py:268-270)"""
-        torch, ps, m, me = self.torch, self.ps, self.sim.model, self.ekf.model
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
-        tm, ts, te = self.t_mpc0 + self.k * self.dt, self.t_sim0 + self.k * self.dt_sim, self.t_ekf0 + self.k * self.dt_ekf
-        if ps.ntvp or ps.np_:
-            row = self._pc_row
-            row[ps.p_off_tvp:ps.p_off_p] = self.mpc.tvp_fun(tm).master
-            row[ps.p_off_p:ps.p_off_uprev] = self.mpc.p_fun(tm).master
-            self.Pc[:, ps.p_off_tvp:ps.p_off_uprev] = up(row[ps.p_off_tvp:ps.p_off_uprev].copy())
-        if m.n_p:
-            self.p_plant.copy_(up(self.sim.p_fun(ts).master))
-        if m.n_tvp:
-            self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
-        if me.n_p:
-            self.p_ekf.copy_(up(self.ekf.p_fun(te).master))
-        if me.n_tvp:
-            self.tvp_ekf.copy_(up(self.ekf.tvp_fun(te).master))
+    def _refresh_filter(self):
+        """_tvp / _p of the filter at the current loop time -> device (same values for every loop)"""
+        me = self.ekf.model
+        te = self.t_ekf0 + self.k * self.dt_ekf
+        if self.k > 0 and me.n_p:
+            self.p_ekf.copy_(self.dv.to_dev(self.ekf.p_fun(te).master))
+        if self.k > 0 and me.n_tvp:
+            self.tvp_ekf.copy_(self.dv.to_dev(self.ekf.tvp_fun(te).master))
 
     def step(self) -> dict:
-        torch, ps, B, nx, nu = self.torch, self.ps, self.B, self.nx, self.nu
-        stream = torch.cuda.current_stream()
-        if self.k > 0:
-            self._refresh_time_varying()
-        nv = self.sim.model.n_v
-        if self._V is not None and nv:
+        ctrl, plant, B = self.ctrl, self.plant, self.B
+        stream = self.dv.stream()
+        ctrl.refresh(self.k)
+        plant.refresh(self.k)
+        self._refresh_filter()
+        if plant.V is not None:
             v = self._V(self.k) if callable(self._V) else self._V
-            self.V.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(v, float).reshape(B, nv))).to(self.dev))
+            plant.V.copy_(self.dv.to_dev(np.asarray(v, float).reshape(plant.V.shape)))
         # 1. controller
-        self.mpc.S.solve_batch_device(B, self.Gc.data_ptr(), self.c_lbx.data_ptr(), self.c_ubx.data_ptr(), self.c_lbg.data_ptr(),
-                                      self.c_ubg.data_ptr(), self.Pc.data_ptr(), self.c_sol.data_ptr(), 0, 0, 0, self.c_f.data_ptr(),
-                                      self.c_stats.data_ptr(), stream=stream.cuda_stream)
-        iu = ps.iu(0, 0)
-        torch.mul(self.c_sol[:, iu:iu + nu], self.us, out=self.U)
-        # 2. plant: next true state and its measurement
-        self.sim.step_batch_device(B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
-                                   self.Xn.data_ptr(), self.Y.data_ptr(), self.pstat.data_ptr(),
-                                   v=(self.V.data_ptr() if (self._V is not None and nv) else 0), shared_mask=2 | 4 | 8,
-                                   stream=stream.cuda_stream)
-        self.X, self.Xn = self.Xn, self.X
+        ctrl.solve(stream)
+        ctrl.u0(out=self.U)
+        # 2. plant: next true state and its measurement (noise per loop)
+        plant.step(self.U, stream, shared_mask=2 | 4 | 8)
         # 3. filter: estimate and covariance in place
-        self.ekf.step_batch_device(B, self.x_est.data_ptr(), self.Pcov.data_ptr(), self.Y.data_ptr(), self.U.data_ptr(),
+        self.ekf.step_batch_device(B, self.x_est.data_ptr(), self.Pcov.data_ptr(), plant.Y.data_ptr(), self.U.data_ptr(),
                                    self.tvp_ekf.data_ptr(), self.p_ekf.data_ptr(), self.Q.data_ptr(), self.R.data_ptr(),
-                                   status=self.estat.data_ptr(), shared_mask=self.mask, stream=stream.cuda_stream,
+                                   status=self.estat.data_ptr(), shared_mask=self.mask, stream=stream,
                                    **({"z": self.z_est.data_ptr(), "newton": self.enewton.data_ptr()} if self.nz else {}))
-        # 4. next controller problem: x0 <- estimate, u_prev <- applied input, initial guess <- previous solution
-        self.Pc[:, :nx] = self.x_est
-        self.Pc[:, ps.p_off_uprev:] = self.U
-        self.Gc.copy_(self.c_sol)
+        # 4. next controller problem, from the estimate
+        ctrl.next_problem(self.x_est, self.U)
         self.k += 1
-        torch.cuda.synchronize()
-        cs = np.frombuffer(self.c_stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
-        est = self.estat.cpu().numpy()
-        out = {"mpc_stats": cs, "plant_status": (self.pstat.cpu().numpy() & 1), "ekf_status": est & 0xFF, "u0": self.U.cpu().numpy(),
-               "x_true": self.X.cpu().numpy(), "y": self.Y[:, :self.ny].cpu().numpy(), "x_est": self.x_est.cpu().numpy(),
-               "P": self.Pcov.cpu().numpy()}
+        self.dv.sync()
+        out = {"mpc_stats": ctrl.stats_host(), "plant_status": plant.status()[0], "ekf_status": self.estat.cpu().numpy() & 0xFF,
+               "u0": self.U.cpu().numpy(), "x_true": plant.X.cpu().numpy(), "y": plant.Y[:, :self.sim.model.n_y].cpu().numpy(),
+               "x_est": self.x_est.cpu().numpy(), "P": self.Pcov.cpu().numpy()}
         if self.nz:
             out["z_est"], out["ekf_newton"] = self.z_est.cpu().numpy(), self.enewton.cpu().numpy()
         return out
@@ -412,18 +432,16 @@ class BatchClosedLoopLQR:
     device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests)."""
 
     def __init__(self, lqr, simulator, X0, K=None, XSS=None, USS=None, device=0, U_prev0=None):
-        import torch
-        self.torch = torch
         self.lqr, self.sim = lqr, simulator
         assert lqr.flags["setup"] is True, "LQR is not setup. run setup() function."
         m = simulator.model
         ml = lqr.model
         assert (m.n_x, m.n_u) == (ml.n_x, ml.n_u), "controller and plant must share states and inputs"
-        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
         X0 = np.asarray(X0, dtype=float).reshape(-1, m.n_x)
         self.B = B = X0.shape[0]
-        dev = self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
-        t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)      # noqa: E731  (a copy, also on the host)
+        dv = self.dv = _Device(device, host_ok=True)
+        t = dv.to_dev
+        self.plant = _PlantSide(simulator, dv, X0)
         rate = lqr.mode == "inputRatePenalization"
         if XSS is None and USS is None and hasattr(lqr, "xss"):
             xs = np.asarray(lqr.xss, float).ravel()
@@ -432,47 +450,22 @@ class BatchClosedLoopLQR:
         self.uss = t(np.zeros((1, m.n_u)) if USS is None else np.asarray(USS, float).reshape(-1, m.n_u))
         self.K = t(np.asarray(lqr.K if K is None else K, float).reshape(-1, m.n_u, lqr.n_design))
         assert self.K.shape[0] in (1, B) and self.xss.shape[0] in (1, B) and self.uss.shape[0] in (1, B), "one gain / set-point or one per loop"
-        self.X = t(X0)
-        self.Xn = torch.empty_like(self.X)
         self.U = t(np.zeros((B, m.n_u)) if U_prev0 is None else np.asarray(U_prev0, float).reshape(B, m.n_u))
-        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        ts = float(simulator._t0[0])
-        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
-        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
-        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
         self.k = 0
 
     def step(self) -> dict:
         """one control step of all B loops; returns the inputs applied, the new states and the plant status"""
-        torch, m = self.torch, self.sim.model
-        cuda = self.dev.type == "cuda"
-        if self.k > 0 and (m.n_p or m.n_tvp):      # the plant's parameters at the current loop time (simulator.py:790-800)
-            ts = self.t_sim0 + self.k * self.dt_sim
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
-            if m.n_p:
-                self.p_plant.copy_(up(self.sim.p_fun(ts).master))
-            if m.n_tvp:
-                self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
-        self.U = self.lqr.make_step_batch(self.X, K=self.K, XSS=self.xss, USS=self.uss, U_prev=self.U).contiguous()
-        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
-                                   self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16,
-                                   stream=(torch.cuda.current_stream().cuda_stream if cuda else 0))
-        self.X, self.Xn = self.Xn, self.X
+        plant = self.plant
+        plant.refresh(self.k)
+        self.U = self.lqr.make_step_batch(plant.X, K=self.K, XSS=self.xss, USS=self.uss, U_prev=self.U).contiguous()
+        plant.step(self.U, self.dv.stream())
         self.k += 1
-        if cuda:
-            torch.cuda.synchronize()
-        return {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1)}
+        self.dv.sync()
+        return {"u0": self.U.cpu().numpy(), "x": plant.X.cpu().numpy(), "plant_status": plant.status()[0]}
 
     def run(self, n: int) -> dict:
         """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step"""
-        xs, us, st = [self.X.cpu().numpy().copy()], [], []
-        for _ in range(int(n)):
-            r = self.step()
-            xs.append(r["x"].copy())
-            us.append(r["u0"].copy())
-            st.append(r["plant_status"])
-        return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, self.B, self.sim.model.n_u)),
-                "plant_status": np.stack(st) if st else np.zeros((0, self.B), dtype=np.int32)}
+        return _record_run(self, n)
 
 
 class BatchClosedLoopAMPC:
@@ -484,74 +477,47 @@ class BatchClosedLoopAMPC:
     has an rterm).  device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests)."""
 
     def __init__(self, ampc, simulator, X0, U_prev0=None, device=0, clip_to_bounds=True):
-        import torch
-        self.torch = torch
         self.ampc, self.sim, self.clip = ampc, simulator, bool(clip_to_bounds)
         assert ampc.flags["setup"] == True, "MPC was not setup yet. Please call ApproxMPC.setup()."      # noqa: E712
         m = simulator.model
         mc = ampc.mpc.model
         assert (m.n_x, m.n_u) == (mc.n_x, mc.n_u), "controller and plant must share states and inputs"
-        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
         X0 = np.asarray(X0, dtype=float).reshape(-1, m.n_x)
         self.B = B = X0.shape[0]
-        dev = self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
-        t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)      # noqa: E731  (a copy, also on the host)
-        self.X = t(X0)
-        self.Xn = torch.empty_like(self.X)
+        dv = self.dv = _Device(device, host_ok=True)
+        self.plant = _PlantSide(simulator, dv, X0)
         if U_prev0 is None:
             u0 = ampc.u0
             U_prev0 = np.tile(np.asarray(u0.master if hasattr(u0, "master") else u0, dtype=float).reshape(1, m.n_u), (B, 1))
-        self.U = t(np.asarray(U_prev0, float).reshape(B, m.n_u))
-        self.Un = torch.empty_like(self.U)
-        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        ts = float(simulator._t0[0])
-        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
-        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
-        self.t_sim0, self.dt_sim = ts, float(simulator.settings.t_step)
+        self.U = dv.to_dev(np.asarray(U_prev0, float).reshape(B, m.n_u))
+        self.Un = dv.torch.empty_like(self.U)
         self.k = 0
 
     def step(self) -> dict:
         """one control step of all B loops; returns the inputs applied, the new states and the plant status"""
-        torch, m = self.torch, self.sim.model
-        cuda = self.dev.type == "cuda"
-        if self.k > 0 and (m.n_p or m.n_tvp):      # the plant's parameters at the current loop time
-            ts = self.t_sim0 + self.k * self.dt_sim
-            up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
-            if m.n_p:
-                self.p_plant.copy_(up(self.sim.p_fun(ts).master))
-            if m.n_tvp:
-                self.tvp_plant.copy_(up(self.sim.tvp_fun(ts).master))
-        stream = torch.cuda.current_stream().cuda_stream if cuda else 0
-        self.ampc.make_step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr() if self.ampc.rterm else 0, self.Un.data_ptr(),
+        plant, stream = self.plant, self.dv.stream()
+        plant.refresh(self.k)
+        self.ampc.make_step_batch_device(self.B, plant.X.data_ptr(), self.U.data_ptr() if self.ampc.rterm else 0, self.Un.data_ptr(),
                                          stream=stream, clip_to_bounds=self.clip)
         self.U, self.Un = self.Un, self.U
-        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
-                                   self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16, stream=stream)
-        self.X, self.Xn = self.Xn, self.X
+        plant.step(self.U, stream)
         self.k += 1
-        if cuda:
-            torch.cuda.synchronize()
-        return {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1)}
+        self.dv.sync()
+        return {"u0": self.U.cpu().numpy(), "x": plant.X.cpu().numpy(), "plant_status": plant.status()[0]}
 
     def run(self, n: int) -> dict:
         """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step"""
-        xs, us, st = [self.X.cpu().numpy().copy()], [], []
-        for _ in range(int(n)):
-            r = self.step()
-            xs.append(r["x"].copy())
-            us.append(r["u0"].copy())
-            st.append(r["plant_status"])
-        return {"x": np.stack(xs), "u": np.stack(us) if us else np.zeros((0, self.B, self.sim.model.n_u)),
-                "plant_status": np.stack(st) if st else np.zeros((0, self.B), dtype=np.int32)}
+        return _record_run(self, n)
 
 
 class BatchClosedLoopASMPC:
     """B closed loops sensitivity-based MPC -> plant advancing together, everything resident in device memory (do_mpc_amd/asmpc.py).  On
-    every `asmpc.settings.resolve_every`-th control step the controller is solved at the current states - warm start, u_prev and the
-    _tvp / _p refresh exactly those of BatchClosedLoop.step -, differentiated and the law prepared (`ASMPC.solve_device`: three device
-    calls on one stream, no host copy); every step then applies the law u = sat(u_ref + M (x - x_ref)) and the plant step.  With
-    resolve_every = 1 this is the MPC loop (the law at x = x_ref adds an exact zero).  Between two solves the law needs nothing from the
-    host: `run(n, fused=True)` covers those steps with ONE launch each (`Simulator.rollout_affine_device`).
+    every `asmpc.settings.resolve_every`-th control step the controller is solved at the current states - the problem, its warm start,
+    u_prev and _tvp / _p refresh are the _ControllerSide of BatchClosedLoop -, differentiated and the law prepared
+    (`ASMPC.solve_device`: three device calls on one stream, no host copy); every step then applies the law
+    u = sat(u_ref + M (x - x_ref)) and the plant step.  With resolve_every = 1 this is the MPC loop (the law at x = x_ref adds an exact
+    zero).  Between two solves the law needs nothing from the host: `run(n, fused=True)` covers those steps with ONE launch each
+    (`Simulator.rollout_affine_device`).
     With `asmpc.settings.event_triggered` a step whose law status carries a bit of `settings.event_mask` for some members (far from the
     expansion point, or a fallback law) solves THOSE members again at once, as a sub-batch with their own previous solutions as warm
     start, writes their columns of the law and applies the law again; the period counter goes on.  The step's record names them in
@@ -561,173 +527,117 @@ class BatchClosedLoopASMPC:
     controller, a law and a plant on the host emulation (tests).  State feedback: the plant's measurement must be its state."""
 
     def __init__(self, asmpc, simulator, X0, U_prev0=None, device=0):
-        import torch
-        self.torch = torch
         self.asmpc, self.sim = asmpc, simulator
         mpc = self.mpc = asmpc.mpc
         ps = self.ps = mpc.structure
-        if getattr(ps, "open_loop_stack", False):
-            raise NotImplementedError("structured HIP backend: the device-resident closed loop with open_loop and several scenarios")
-        if getattr(mpc.S, "row_mapped", False):
-            raise NotImplementedError("structured HIP backend: the device-resident closed loop with rows appended to nlp_cons")
-        m = simulator.model
-        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
-        assert m.n_y == m.n_x, "state feedback: the plant's measurement must be its state"
+        dv = self.dv = _Device(device, host_ok=True)
+        self.dev = dv.dev
         X0 = np.asarray(X0, dtype=float).reshape(-1, ps.nx)
         self.B = B = X0.shape[0]
-        dev = self.dev = torch.device("cpu") if device == "cpu" else torch.device("cuda", device)
-        t = lambda a: torch.tensor(np.asarray(a, dtype=np.float64), device=dev)      # noqa: E731  (a copy, also on the host)
-        t0 = float(mpc._t0[0])
-        P = np.tile(mpc.opt_p_num.master, (B, 1))
-        P[:, :ps.nx] = X0
-        P[:, ps.p_off_tvp:ps.p_off_p] = mpc.tvp_fun(t0).master
-        P[:, ps.p_off_p:ps.p_off_uprev] = mpc.p_fun(t0).master
-        P[:, ps.p_off_uprev:] = 0.0 if U_prev0 is None else np.asarray(U_prev0, float).reshape(B, ps.nu)
-        Xi = np.zeros((B, ps.n_opt_x))
-        Xi[:, :ps.off_z].reshape(B, -1, ps.nx)[:] = (X0 / mpc._x_scaling.master)[:, None, :]
-        Xi[:, ps.off_u:ps.off_eps].reshape(B, -1, ps.nu)[:] = (P[:, ps.p_off_uprev:] / mpc._u_scaling.master)[:, None, :]
-        self.P, self.guess = t(P), t(Xi)
-        self.X = t(X0)
-        self.Xn = torch.empty_like(self.X)
-        self.U = t(P[:, ps.p_off_uprev:])                     # the inputs applied last (u_prev of the next solve)
-        self.Un = torch.empty_like(self.U)
-        self.sol = torch.empty((B, ps.n_opt_x), dtype=torch.float64, device=dev)
-        self.lam_g = torch.empty((B, ps.n_g), dtype=torch.float64, device=dev)
-        self.f = torch.empty(B, dtype=torch.float64, device=dev)
-        self.stats = torch.zeros(B * STATS_DTYPE.itemsize, dtype=torch.uint8, device=dev)
-        self.pstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        self.lstat = torch.zeros(B, dtype=torch.int32, device=dev)
-        ts = float(simulator._t0[0])
-        self.p_plant = t(simulator.p_fun(ts).master if m.n_p else np.zeros(1))
-        self.tvp_plant = t(simulator.tvp_fun(ts).master if m.n_tvp else np.zeros(1))
-        self.t_mpc0, self.t_sim0 = t0, ts
-        self.dt_mpc, self.dt_sim = float(mpc.settings.t_step), float(simulator.settings.t_step)
-        self._p_row = P[0].copy()
+        self.ctrl = _ControllerSide(mpc, dv, X0, U_prev0, lam_g=True)
+        m = simulator.model
+        assert m.n_x == ps.nx and m.n_u == ps.nu, "controller and plant must share states and inputs"
+        self.plant = _PlantSide(simulator, dv, X0)
+        self.U = dv.empty(B, ps.nu).copy_(self.ctrl.P[:, ps.p_off_uprev:])      # the inputs applied last (u_prev of the next solve)
+        self.Un = dv.torch.empty_like(self.U)
+        self.lstat = dv.zeros(B, dtype=dv.torch.int32)
         self.k = 0
         self._since = None                                    # control steps since the last solve (None: never solved)
-        self.ev_idx = torch.zeros(B, dtype=torch.int32, device=dev)       # event-triggered re-solves: the members selected at a step
-        self.ev_count = torch.zeros(1, dtype=torch.int32, device=dev)
+        self.ev_idx = dv.zeros(B, dtype=dv.torch.int32)       # event-triggered re-solves: the members selected at a step
+        self.ev_count = dv.zeros(1, dtype=dv.torch.int32)
+
+    # the tensors and times of the two sides under the names they had on the loop (tests rebuild a solve's parameters from them)
+    X = property(lambda self: self.plant.X)
+    P = property(lambda self: self.ctrl.P)
+    guess = property(lambda self: self.ctrl.guess)
+    _p_row = property(lambda self: self.ctrl._p_row)
+    t_mpc0 = property(lambda self: self.ctrl.t0)
+    dt_mpc = property(lambda self: self.ctrl.dt)
 
     def resolve(self) -> None:
         """forces a solve at the next step"""
         self._since = None
 
-    def _stream(self):
-        return self.torch.cuda.current_stream(self.dev).cuda_stream if self.dev.type == "cuda" else 0
-
-    def _sync(self):
-        if self.dev.type == "cuda":
-            self.torch.cuda.synchronize(self.dev)
-
     def _due(self) -> bool:
         return self._since is None or self._since >= int(self.asmpc.settings.resolve_every)
 
     def _solve(self):
-        """the solve of BatchClosedLoop.step at the current states, then sensitivities and law: x0 <- plant state, u_prev <- applied
-        input, initial guess <- previous solution, the controller's _tvp / _p at the current loop time"""
+        """the solve of BatchClosedLoop.step at the current states, then sensitivities and law"""
+        c = self.ctrl
         self._refresh_P()
-        self.asmpc.solve_device(self.guess, self.P, self.sol, self.lam_g, self.f, self.stats)
-        self.guess.copy_(self.sol)
+        self.asmpc.solve_device(c.guess, c.P, c.sol, c.lam_g, c.f, c.stats)
+        c.guess.copy_(c.sol)
         self._since = 0
 
     def _refresh_P(self):
-        """the parameters of a solve at the current states: x0 <- plant state, u_prev <- applied input, _tvp / _p at the loop time"""
-        torch, ps = self.torch, self.ps
-        if self.k > 0 and (ps.ntvp or ps.np_):
-            tm = self.t_mpc0 + self.k * self.dt_mpc
-            row = self._p_row
-            row[ps.p_off_tvp:ps.p_off_p] = self.mpc.tvp_fun(tm).master
-            row[ps.p_off_p:ps.p_off_uprev] = self.mpc.p_fun(tm).master
-            self.P[:, ps.p_off_tvp:ps.p_off_uprev] = torch.from_numpy(row[ps.p_off_tvp:ps.p_off_uprev].copy()).to(self.dev)
-        self.P[:, :ps.nx] = self.X
-        self.P[:, ps.p_off_uprev:] = self.U
+        """the parameters of a solve at the current states: _tvp / _p at the loop time, x0 <- plant state, u_prev <- applied input"""
+        self.ctrl.refresh(self.k)
+        self.ctrl.set_x0(self.plant.X, self.U)
 
     def _resolve_events(self, stream):
         """after the law step: the members whose status carries a bit of settings.event_mask are solved again at their states (a
         sub-batch solve from their own previous solutions), their law columns written, and the law applied again for the whole batch -
         the other members see an untouched law and get the same bits, the selected ones their new u0 (the law at x = x_ref adds an
         exact zero).  Returns the members (host array, empty if none)."""
-        torch, a = self.torch, self.asmpc
+        torch, a, c = self.dv.torch, self.asmpc, self.ctrl
         a.select_device(self.B, self.lstat.data_ptr(), self.ev_idx.data_ptr(), self.ev_count.data_ptr(), stream=stream)
         n = int(self.ev_count.item())                         # (4 bytes; the step synchronises anyway)
         if n == 0:
             return np.zeros(0, dtype=np.int64)
         self._refresh_P()                                     # (self.U still holds the inputs applied last: the law step wrote self.Un)
-        a.solve_members_device(self.ev_idx, n, self.guess, self.P, self.sol, self.lam_g, self.f, self.stats)
+        a.solve_members_device(self.ev_idx, n, c.guess, c.P, c.sol, c.lam_g, c.f, c.stats)
         ix = self.ev_idx[:n].to(torch.int64)
-        self.guess.index_copy_(0, ix, self.sol.index_select(0, ix))
-        a.make_step_batch_device(self.B, self.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
+        c.guess.index_copy_(0, ix, c.sol.index_select(0, ix))
+        a.make_step_batch_device(self.B, self.plant.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
         return self.ev_idx[:n].cpu().numpy().astype(np.int64)
-
-    def _plant_rows(self, K):
-        """the plant's _tvp / _p at the K loop times ahead: [K][n] each (one zero per row without such parameters)"""
-        m = self.sim.model
-        ts = [self.t_sim0 + (self.k + j) * self.dt_sim for j in range(K)]
-        # (a copy per row: a tvp_fun / p_fun usually fills and returns one template)
-        tv = np.array([np.array(self.sim.tvp_fun(s).master, dtype=float).reshape(-1) for s in ts]) if m.n_tvp else np.zeros((K, 1))
-        pp = np.array([np.array(self.sim.p_fun(s).master, dtype=float).reshape(-1) for s in ts]) if m.n_p else np.zeros((K, 1))
-        return tv, pp
-
-    def _stats_host(self):
-        return np.frombuffer(self.stats.cpu().numpy().tobytes(), dtype=STATS_DTYPE).copy()
 
     def step(self) -> dict:
         """one control step of all B loops; returns the inputs applied, the new states, the plant status, the law status, whether the
         step solved and - then - the solver statistics.  With settings.event_triggered also 'resolved': the members (int array, empty
         if none) that an event solved again at this step; they carry bit 4 in 'law_status', and 'stats' is there when there are any."""
-        torch, m = self.torch, self.sim.model
+        plant = self.plant
         solved = self._due()
         if solved:
             self._solve()
-        if self.k > 0 and (m.n_p or m.n_tvp):      # the plant's parameters at the current loop time (simulator.py:790-800)
-            tv, pp = self._plant_rows(1)
-            if m.n_p:
-                self.p_plant.copy_(torch.from_numpy(np.ascontiguousarray(pp[0])).to(self.dev))
-            if m.n_tvp:
-                self.tvp_plant.copy_(torch.from_numpy(np.ascontiguousarray(tv[0])).to(self.dev))
-        stream = self._stream()
-        self.asmpc.make_step_batch_device(self.B, self.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
+        plant.refresh(self.k)
+        stream = self.dv.stream()
+        self.asmpc.make_step_batch_device(self.B, plant.X.data_ptr(), self.Un.data_ptr(), self.lstat.data_ptr(), stream=stream)
         event = bool(self.asmpc.settings.event_triggered)
         # (on a step that has just solved the whole batch dx = 0: only a member whose solve failed there can be selected, and gets a
         #  second solve from the iterate the first one ended at)
         resolved = self._resolve_events(stream) if event else None
         self.U, self.Un = self.Un, self.U
-        self.sim.step_batch_device(self.B, self.X.data_ptr(), self.U.data_ptr(), self.tvp_plant.data_ptr(), self.p_plant.data_ptr(),
-                                   self.Xn.data_ptr(), 0, self.pstat.data_ptr(), shared_mask=2 | 4 | 8 | 16, stream=stream)
-        self.X, self.Xn = self.Xn, self.X
+        plant.step(self.U, stream)
         self.k += 1
         self._since += 1
-        self._sync()
-        out = {"u0": self.U.cpu().numpy(), "x": self.X.cpu().numpy(), "plant_status": (self.pstat.cpu().numpy() & 1),
+        self.dv.sync()
+        out = {"u0": self.U.cpu().numpy(), "x": plant.X.cpu().numpy(), "plant_status": plant.status()[0],
                "law_status": self.lstat.cpu().numpy().copy(), "solved": solved}
         if event:
             out["law_status"][resolved] |= 16                 # bit 4: re-solved by an event at this step
             out["resolved"] = resolved
         if solved or (event and resolved.size):
-            out["stats"] = self._stats_host()
+            out["stats"] = self.ctrl.stats_host()
         return out
 
     def _rollout(self, K):
         """K control steps between two solves in one launch; returns (x [K][B][nx], u [K][B][nu], plant status, law status)"""
-        torch, m, B = self.torch, self.sim.model, self.B
+        dv, plant, m, B = self.dv, self.plant, self.sim.model, self.B
         if m.n_z:
             raise NotImplementedError("BatchClosedLoopASMPC.run(fused=True): plants with algebraic states are not served by the rollout "
                                       "(run(n, fused=False) steps them)")
-        tv, pp = self._plant_rows(K)
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(self.dev)      # noqa: E731
-        tv, pp = up(tv), up(pp)
-        Xt = torch.empty((K + 1, B, m.n_x), dtype=torch.float64, device=self.dev)
-        Ut = torch.empty((K, B, m.n_u), dtype=torch.float64, device=self.dev)
-        ps_, ls_ = (torch.zeros((K, B), dtype=torch.int32, device=self.dev) for _ in range(2))
-        Xt[0].copy_(self.X)
+        tv, pp = (dv.to_dev(a) for a in plant.rows(self.k, K))
+        Xt, Ut = dv.empty(K + 1, B, m.n_x), dv.empty(K, B, m.n_u)
+        ps_, ls_ = (dv.zeros(K, B, dtype=dv.torch.int32) for _ in range(2))
+        Xt[0].copy_(plant.X)
         law = self.asmpc.law_record()
         self.sim.rollout_affine_device(B, K, law, Xt.data_ptr(), Ut.data_ptr(), tv.data_ptr(), pp.data_ptr(), ps_.data_ptr(), ls_.data_ptr(),
-                                       stream=self._stream())
-        self.X.copy_(Xt[K])
+                                       stream=dv.stream())
+        plant.X.copy_(Xt[K])
         self.U.copy_(Ut[K - 1])
         self.k += K
         self._since += K
-        self._sync()
+        dv.sync()
         return Xt[1:].cpu().numpy(), Ut.cpu().numpy(), ps_.cpu().numpy() & 1, ls_.cpu().numpy()
 
     def run(self, n: int, fused: bool = True) -> dict:
@@ -742,7 +652,7 @@ class BatchClosedLoopASMPC:
             raise NotImplementedError("BatchClosedLoopASMPC.run(fused=True): event-triggered re-solves are not served by the rollout, which "
                                       "would have to be rewound to the first event (run(n, fused=False) steps them)")
         events = []
-        xs, us, pst, lst, solve_steps, stats = [self.X.cpu().numpy().copy()[None]], [], [], [], [], []
+        xs, us, pst, lst, solve_steps, stats = [self.plant.X.cpu().numpy().copy()[None]], [], [], [], [], []
         i = 0
         while i < n:
             if not fused:
@@ -757,8 +667,8 @@ class BatchClosedLoopASMPC:
                 continue
             if self._due():
                 self._solve()
-                self._sync()
-                solve_steps.append(i); stats.append(self._stats_host())
+                self.dv.sync()
+                solve_steps.append(i); stats.append(self.ctrl.stats_host())
             K = min(int(self.asmpc.settings.resolve_every) - self._since, n - i)
             x, u, p_, l_ = self._rollout(K)
             xs.append(x); us.append(u); pst.append(p_); lst.append(l_)
