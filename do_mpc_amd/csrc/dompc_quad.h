@@ -21,8 +21,8 @@
 //   * no dense image: the entries of the compact model-output record are read where they are needed, addressed at COMPILE time (the
 //     structure tables of the generated header are constant expressions): the point Hessians enter the condensing as the sparse matrices
 //     they are (industrial_poly: 25 of 91 packed entries per point).
-//   * condensing in the same layout: lane c owns column c of [W | w0 | -], T = (H_p + Sigma_p) Z_p is lane-local, Z_p' T takes the rows of
-//     Z_p from a staged copy in LDS (group-uniform reads, no vector-ALU slots).
+//   * condensing in the same layout: lane c owns column c of [W | w0 | -], T = (H_p + Sigma_p) Z_p is lane-local, Z_p' T takes entry
+//     [k][i] of Z_p from lane i as the DPP operand of its multiply-add (no LDS round trip; -DDOMPC_QUAD_LDS=1 keeps the staged copy).
 // Measured effect: DESIGN.md section 4 / profiles/r06_*.  The cross-lane primitives and their rules: dompc_lanes.h, DESIGN.md section 4k.
 #if !defined(DOMPC_HOST_EMU) && DOMPC_DEG >= 1 && DOMPC_M >= 1 && DOMPC_NI == 1 && DOMPC_NX + DOMPC_NU + 2 <= 16 && DOMPC_DEG * DOMPC_DEG * DOMPC_NX <= 64      // (array sizes and lane numbers below; the rest of the conditions: QUAD_EDGE, dompc_edge.h)
 
@@ -31,6 +31,7 @@
 using dompc_lanes::rbc;
 using dompc_lanes::pin;
 using dompc_lanes::fmac_rbc;
+using dompc_lanes::dpp_ready;
 using dompc_lanes::sfor;
 
 // where a dense entry of the model-output record lives: kind 0 structural zero, 1 model constant (index into the constant table),
@@ -84,6 +85,12 @@ __device__ inline void stage_quad(const Prob& Q, int e0, int lane, ldsd* Ld, int
 
 #ifndef DOMPC_QUAD_PROFILE
 #define DOMPC_QUAD_PROFILE DOMPC_PROFILE
+#endif
+// -DDOMPC_QUAD_LDS=1: the comparison build - the rows of Z_p of the condensing (step 8 below) go through a staged copy in LDS behind
+// wave barriers, as they did before they became DPP operands.  Same operands in the same order: the two builds give the same bits
+// (tests/test_gpu_quad_dpp.py).  The forward pass below keeps its LDS hand-overs in both builds (measured, no gain).
+#ifndef DOMPC_QUAD_LDS
+#define DOMPC_QUAD_LDS 0
 #endif
 // scheduling barriers between the pieces of a quad and between the pivots of its elimination: without them the machine scheduler stretches
 // live ranges over the whole 9 000-instruction body and spills hundreds of registers
@@ -411,10 +418,13 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
   for (int i = 0; i < NA; ++i) acc[i] = 0.0;
   {
     const double ind = (j >= NA) ? 1.0 : 0.0;                 // the two vector columns (lanes NA, NA + 1)
+#if DOMPC_QUAD_LDS
     ldsd* Wb = Ld + QL_WB + g * QL_WBG;
+#endif
     const ldsd* Lvec = Ld + QL_RW + g * QL_VG + (j == NA + 1 ? NW : 0);
     sfor<M>([&](auto P_) {
       constexpr int p = P_;
+#if DOMPC_QUAD_LDS
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
       if (j <= NA) {
@@ -423,6 +433,7 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
       }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       __builtin_amdgcn_wave_barrier();
+#endif
       double Zc[NX], Tv[NA];
 #pragma unroll
       for (int k = 0; k < NX; ++k) Zc[k] = (j <= NA) ? Wc[p * NX + k] : 0.0;
@@ -458,8 +469,17 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
         Tv[k] = fma(sg, Zc[k], Tv[k]);
         Tv[k] = fma(ind, Lvec[p * NX + k], Tv[k]);
       });
-      // acc[i] += sum_k Z_p[k][i] T[k]: the rows of Z_p from their staged copy, two rows per batch of LDS reads (the scheduler would
-      // otherwise issue all 130 reads of the slot up front and spill what they displace)
+      // acc[i] += sum_k Z_p[k][i] T[k].  Entry [k][i] of Z_p is Zc[k] of lane i of this row of 16 lanes: the DPP operand of the
+      // multiply-add, as in the elimination (k ascending for every acc[i]: the order of the sums of the staged copy it replaces)
+#if !DOMPC_QUAD_LDS
+      dpp_ready(Zc);
+      sfor<NX>([&](auto K_) {
+        constexpr int k = K_;
+        sfor<NA>([&](auto I_) { constexpr int i = I_; fmac_rbc<i>(acc[i], Zc[k], Tv[k]); });
+      });
+#else
+      // (comparison build: the rows of Z_p from their staged copy, two rows per batch of LDS reads - the scheduler would otherwise issue
+      //  all 130 reads of the slot up front and spill what they displace)
       sfor<(NX + 1) / 2>([&](auto K2_) {
         constexpr int k0 = 2 * K2_;
         QD_SB();
@@ -475,6 +495,7 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
             for (int i = 0; i < NA; ++i) acc[i] = fma(wr[kk][i], Tv[k0 + kk], acc[i]);
           }
       });
+#endif
       if constexpr (p < DEG) {
 #pragma unroll
         for (int ku = 0; ku < NU; ++ku) acc[NX + ku] += Tv[NX + ku];
@@ -821,6 +842,12 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     const int lane0 = (int)(threadIdx.x & 63u);
     stage_quad(Q, 4 * qd, lane0, Ld, 0);
   }
+#if DOMPC_QUAD_PROFILE
+  long long pc0 = prof_clock();
+#define QF_PH(i) if (T.prof && T.tid == 0) { const long long pc1 = prof_clock(); T.prof[i] += pc1 - pc0; pc0 = pc1; }
+#else
+#define QF_PH(i)
+#endif
   while (qd < nq) {
     int lane = (int)(threadIdx.x & 63u);
     asm volatile("" : "+v"(lane));
@@ -856,6 +883,7 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the staged records (and everything above) have landed
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    QF_PH(15)
     const ldsd* rec = Ld + bank * QL_MOSZ + (e - e0) * MO_REC;      // (a row beyond the last edge: the last edge's record, as in eval_edge_quad - the same verdict as the sweep's)
     ldsd* Lv = Ld + QL_WB + g * QF_VG;                        // dw | dy | rhs | rr of this lane's edge
     constexpr int V_DW = 0, V_DY = NW, V_RHS = NW + NA, V_RR = 2 * NW + NA;
@@ -881,9 +909,11 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     QD_SB();
     double bc[DEG][R];
     qd_fw_columns(rec, j, gv, bc);
+    QF_PH(28)
     QD_SB();
     const int bad = qd_fw_eliminate(j, bc);
     const bool fb = __ballot(bad) != 0ull;                   // (the sweep took its fallback for this quad and stored the inverses: used below)
+    QF_PH(29)
     // the compact records of the quad this wavefront handles next
     const int qn = qd + ng;
     if (qn < nq) stage_quad(Q, 4 * qn, lane, Ld, bank ^ 1);
@@ -928,6 +958,7 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    QF_PH(30)
     QD_SB();
     // ---- rhs = -(r_w + (Sigma_w + delta) dw + H_ww dw + H_wu du + [end-point slot] d nu), row (s, b) on lane b
     double rhs[M];
@@ -959,6 +990,7 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
       rhs[s] = -t;
       pin(rhs[s]);
     });
+    QF_PH(31)
     QD_SB();
     // ---- d lambda = G_w^-T rhs,  G_w^-T = [[Gi', -Gi'E'], [0, I]]: rr = rhs_c + D rhs_e handed round, column (s, b) of Gi times rr
     if (isx) {
@@ -1007,9 +1039,11 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    QF_PH(20)
     bank ^= 1;
     qd = qn;
   }
+#undef QF_PH
 }
 #elif !defined(DOMPC_HOST_EMU)
 __device__ inline void phase_forward_quads(const void*, int, int, int, double, double, int) {}      // (never called: QUAD_FWD is false)

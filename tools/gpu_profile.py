@@ -57,9 +57,19 @@ def main():
              12: "node:staged tiles", 13: "node:own terms", 14: "node:own matrix", 8: "node:column to tile", 9: "node:coupling", 10: "node:cholesky+K", 11: "node:own part of the value function", 16: "fwd:node steps (chain walk)", 17: "fwd:edge loads issued",
              18: "fwd:edge wait + dw", 19: "fwd:edge rhs", 20: "fwd:edge dlam + stores", 21: "sweep:model evaluation", 22: "sweep:edge loop", 23: "sweep:node assembly",
              24: "node:closed loop (children, pass 2)", 25: "node:wait for the next node's operands", 26: "node:stores", 27: "chain:request of the next node's operands"}
-    for i in (0, 4, 5, 6, 1, 2, 7, 3, 12, 13, 14, 8, 9, 10, 11, 24, 25, 26, 27, 16, 17, 18, 19, 20, 21, 22, 23):
-        print(f"    {names[i]:30s} {sub[i] / 1e6:9.2f} Mcycles")
-
+    order = (0, 4, 5, 6, 1, 2, 7, 3, 12, 13, 14, 8, 9, 10, 11, 24, 25, 26, 27, 16, 17, 18, 19, 20, 21, 22, 23)
+    if mpc.S.edges_per_wavefront == 4:
+        # four edges per wavefront (csrc/dompc_quad.h): where the QD_PH(i) / QF_PH(i) calls of eval_edge_quad and phase_forward_quads
+        # sit, in the order of the code.  Rows 17 - 19 stay with the two-edge forward pass (the adjoint variant still takes it), row 20
+        # is shared with it; row 0 is the model evaluation of the wavefront-per-edge fallback.
+        names.update({0: "edge:model-eval (fallback path)", 4: "quad:operand loads + wait", 5: "quad:residuals, barrier terms, columns",
+                      6: "quad:dual pieces", 2: "quad:gauss-jordan", 7: "quad:fwd record, W, [A B] stores", 1: "quad:condensing",
+                      3: "quad:record stores", 15: "fwdq:operand request + wait", 28: "fwdq:dy, g, column build", 29: "fwdq:elimination",
+                      30: "fwdq:dw", 31: "fwdq:rhs", 20: "fwdq:dlam + stores (+ two-edge path)",
+                      17: "fwd2:edge loads issued", 18: "fwd2:edge wait + dw", 19: "fwd2:edge rhs"})
+        order = (0, 4, 5, 6, 2, 7, 1, 3, 12, 13, 14, 8, 9, 10, 11, 24, 25, 26, 27, 16, 15, 28, 29, 30, 31, 20, 17, 18, 19, 21, 22, 23)
+    for i in order:
+        print(f"    {names[i]:38s} {sub[i] / 1e6:9.2f} Mcycles")
 
 if __name__ == "__main__":
     main()
