@@ -15,6 +15,11 @@ csrc/dompc_ampc.hip behind the C ABI `dompc_ampc_*` (include/dompc_ipm.h) for a 
 weights are packed and uploaded before a step whenever a parameter changed (an optimiser step, `load_from_state_dict`).
 Training is PyTorch (Adam, mse_loss, ReduceLROnPlateau) and `predict` is the plain torch forward of `self.net`.
 
+Additions to the reference's surface: `jacobian_batch` / `jacobian_batch_device` - u and the network's own Jacobian du/dx, du/du_prev
+for a batch in one launch of the second kernel of the same code object (`dompc_ampc_jacobian_batch*`) - and Sobolev training:
+`TrainerSettings.sobolev_weight` > 0 also fits that Jacobian to the MPC sensitivities the sampler stored (`du0dx0`, `du0du_prev`),
+`Trainer.sensitivity_error()` measures it against them.
+
 Two behaviours of the reference are deliberately NOT copied:
   * `setup()` does not call `torch.set_default_device`: a process-wide side effect that would change every other torch user in
     the process.  The trainer moves the network and its data to `cuda:<gpu_index>` itself when a device is there.
@@ -76,6 +81,7 @@ class TrainerSettings:
     save_history: bool = False
     print_frequency: int = 10
     gpu_index: int = 0
+    sobolev_weight: float = 0.0            # (addition) > 0: the loss also fits the network's Jacobian to du0dx0 / du0du_prev of the data file
 
     def check_for_mandatory_settings(self):
         if self.dataset_name is None:
@@ -136,6 +142,31 @@ class FeedforwardNN(torch.nn.Module):
         return x
 
 
+def network_jacobian(net: FeedforwardNN, xs):
+    """(net(xs), d net / d xs [B][n_out][n_in]) by the tangent recursion over `net.layers`, T <- diag(act'(a)) W T with the activation's
+    derivative formed from its output a - the arithmetic of csrc/dompc_ampc.hip:jac32 -, in torch operations, so that autograd reaches
+    the weights through both results"""
+    h, T = xs, None
+    for module in net.layers:
+        if isinstance(module, torch.nn.Linear):
+            h = module(h)
+            T = module.weight if T is None else module.weight @ T
+            continue
+        h = module(h)
+        if isinstance(module, torch.nn.Tanh):
+            d = 1.0 - h * h
+        elif isinstance(module, torch.nn.Sigmoid):
+            d = h * (1.0 - h)
+        elif isinstance(module, torch.nn.ReLU):
+            d = (h > 0).to(h.dtype)
+        elif isinstance(module, torch.nn.LeakyReLU):
+            d = torch.where(h > 0, 1.0, module.negative_slope).to(h.dtype)
+        else:
+            raise ValueError("Activation function not implemented.")
+        T = d.unsqueeze(-1) * T
+    return h, (T if T.dim() == 3 else T.expand(xs.shape[0], *T.shape))
+
+
 # ---------------------------------------------------------------------------------------------------------------------- native side
 class AMPCDesc(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("n_in", "n_out", "n_hidden_layers", "n_neurons", "act", "out_act", "scaling", "nx")] + \
@@ -158,6 +189,10 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_ampc_step_batch.restype = C.c_int
     lib.dompc_ampc_step_batch_device.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp]
     lib.dompc_ampc_step_batch_device.restype = C.c_int
+    lib.dompc_ampc_jacobian_batch.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.c_int32]
+    lib.dompc_ampc_jacobian_batch.restype = C.c_int
+    lib.dompc_ampc_jacobian_batch_device.argtypes = [vp, C.c_int32, vp, vp, vp, vp, vp, C.c_int32, vp]
+    lib.dompc_ampc_jacobian_batch_device.restype = C.c_int
     return lib
 
 
@@ -338,18 +373,23 @@ class ApproxMPC(torch.nn.Module):
         except Exception:
             pass
 
-    def make_step_batch(self, X, U_prev=None, clip_to_bounds=True) -> np.ndarray:
-        """one step for B samples in one launch: X [B][nx] (and U_prev [B][nu] when the controller has an rterm) -> U [B][nu], float64"""
-        h = self._handle()
+    def _host_inputs(self, X, U_prev, who):
+        """(X [B][nx], U_prev [B][nu] or None) as contiguous float64 arrays"""
         m = self.mpc.model
         X = np.ascontiguousarray(np.asarray(X, dtype=np.float64)).reshape(-1, m.n_x)
-        B = X.shape[0]
         up = None
         if self.rterm:
             if U_prev is None:
-                raise ValueError("make_step_batch: the controller has an rterm, the network input is [x; u_prev]: U_prev is required")
-            up = np.ascontiguousarray(np.asarray(U_prev, dtype=np.float64)).reshape(B, m.n_u)
-        U = np.empty((B, m.n_u))
+                raise ValueError(f"{who}: the controller has an rterm, the network input is [x; u_prev]: U_prev is required")
+            up = np.ascontiguousarray(np.asarray(U_prev, dtype=np.float64)).reshape(X.shape[0], m.n_u)
+        return X, up
+
+    def make_step_batch(self, X, U_prev=None, clip_to_bounds=True) -> np.ndarray:
+        """one step for B samples in one launch: X [B][nx] (and U_prev [B][nu] when the controller has an rterm) -> U [B][nu], float64"""
+        h = self._handle()
+        X, up = self._host_inputs(X, U_prev, "make_step_batch")
+        B = X.shape[0]
+        U = np.empty((B, self.mpc.model.n_u))
         ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None      # noqa: E731
         self._check(self._lib.dompc_ampc_step_batch(h, B, ptr(X), ptr(up), ptr(U), 1 if clip_to_bounds else 0))
         return U
@@ -361,6 +401,28 @@ class ApproxMPC(torch.nn.Module):
         self._check(self._lib.dompc_ampc_step_batch_device(
             h, int(B), C.c_void_p(int(X_ptr)), C.c_void_p(int(U_prev_ptr) if U_prev_ptr else None), C.c_void_p(int(U_out_ptr)),
             1 if clip_to_bounds else 0, C.c_void_p(int(stream) if stream else None)))
+
+    def jacobian_batch(self, X, U_prev=None, clip_to_bounds=False) -> dict:
+        """the network's own Jacobian for B samples in one launch (dompc_ampc_jac_kernel: forward mode in float32): {"u": [B][nu] as
+        make_step_batch gives it, "du_dx": [B][nu][nx], "du_du_prev": [B][nu][nu] or None without an rterm}, float64, in physical
+        units like the sampler's du0dx0 / du0du_prev.  With clip_to_bounds the row of an output that lay beyond a bound is zero."""
+        h = self._handle()
+        m = self.mpc.model
+        X, up = self._host_inputs(X, U_prev, "jacobian_batch")
+        B = X.shape[0]
+        out = {"u": np.empty((B, m.n_u)), "du_dx": np.empty((B, m.n_u, m.n_x)), "du_du_prev": np.empty((B, m.n_u, m.n_u)) if self.rterm else None}
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None      # noqa: E731
+        self._check(self._lib.dompc_ampc_jacobian_batch(h, B, ptr(X), ptr(up), ptr(out["u"]), ptr(out["du_dx"]), ptr(out["du_du_prev"]),
+                                                        1 if clip_to_bounds else 0))
+        return out
+
+    def jacobian_batch_device(self, B, X_ptr, U_prev_ptr, U_out_ptr, dUdX_ptr, dUdUprev_ptr, stream=0, clip_to_bounds=False) -> None:
+        """jacobian_batch on raw device addresses of float64 arrays [B][nx], [B][nu], [B][nu], [B][nu][nx] and [B][nu][nu] (U_prev_ptr and
+        dUdUprev_ptr 0 without an rterm); asynchronous on `stream`"""
+        h = self._handle()
+        vp = lambda a: C.c_void_p(int(a) if a else None)      # noqa: E731
+        self._check(self._lib.dompc_ampc_jacobian_batch_device(h, int(B), vp(X_ptr), vp(U_prev_ptr), vp(U_out_ptr), vp(dUdX_ptr),
+                                                               vp(dUdUprev_ptr), 1 if clip_to_bounds else 0, vp(stream)))
 
     def make_step(self, x0, u_prev=None, clip_to_bounds=True):
         assert self.flags["setup"] == True, "MPC was not setup yet. Please call ApproxMPC.setup()."      # noqa: E712
@@ -386,7 +448,13 @@ def _pyplot():
 
 class Trainer:
     """_trainer.py: Adam on mse_loss over the (scaled) samples of `data_<name>_opt.pkl`, a random validation split, optionally
-    ReduceLROnPlateau.  Runs on cuda:<gpu_index> when a device is there, otherwise on the CPU; the network stays there afterwards."""
+    ReduceLROnPlateau.  Runs on cuda:<gpu_index> when a device is there, otherwise on the CPU; the network stays there afterwards.
+
+    Addition (Sobolev training): with `settings.sobolev_weight` = w > 0 the data file's MPC sensitivities du0dx0 (and du0du_prev with an
+    rterm; AMPCSampler.settings.store_sensitivities) become labels of the network's Jacobian, in the network's coordinates
+    Js[i][k] = J[i][k] x_range[k] / y_range[i], and the loss is mse(net(xs), us) + w mse(J_net(xs), Js), the second term over the rows
+    whose labels are all finite (the sampler writes NaN where the differentiation failed).  The history then also carries the two terms
+    as train_loss_u / train_loss_j / val_loss_u / val_loss_j.  With the default 0.0 nothing of this is read or computed."""
 
     def __init__(self, approx_mpc):
         self.approx_mpc = approx_mpc
@@ -402,6 +470,7 @@ class Trainer:
         self.approx_mpc.net.to(self.device)
         self.generator = torch.Generator()          # (the trainer's own: the split and the shuffling do not touch the global one)
         self.history = {"epoch": []}
+        self._terms = []                            # (loss_u, loss_j) of the mini-batches of a Sobolev epoch
 
     @property
     def settings(self):
@@ -431,6 +500,31 @@ class Trainer:
         u0_scaled = (u0 - a.y_shift.to(u0.device)) / a.y_range.to(u0.device)
         return x_scaled.type(a.torch_data_type), u0_scaled.type(a.torch_data_type)
 
+    def _scaled_columns(self, dataset, sensitivities, source="the data"):
+        """(xs, us) of a data table in the network's coordinates and data type and, on request, the Jacobian labels Js [N][n_u][n_in]"""
+        a = self.approx_mpc
+        m, rterm = a.mpc.model, a.mpc.flags["set_rterm"]
+        col = lambda key, *n: torch.tensor(np.stack([np.asarray(v, dtype=float).reshape(-1) for v in dataset[key]]),      # noqa: E731
+                                           dtype=a.torch_data_type).reshape(-1, *n)
+        x0, u0 = col("x0", m.n_x), col("u0", m.n_u)
+        x = torch.cat((x0, col("u_prev", m.n_u)), dim=1) if rterm else x0
+        if a.settings.scaling:
+            x_scaled, u0_scaled = self.scale_dataset(x, u0)
+        else:
+            x_scaled, u0_scaled = x, u0
+        if not sensitivities:
+            return x_scaled, u0_scaled
+        for key in ["du0dx0"] + (["du0du_prev"] if rterm else []):
+            if key not in dataset:
+                raise ValueError(f"TrainerSettings.sobolev_weight > 0 needs the column {key} in {source}: sample with "
+                                 "AMPCSampler.settings.store_sensitivities = True")
+        J = col("du0dx0", m.n_u, m.n_x)
+        if rterm:
+            J = torch.cat((J, col("du0du_prev", m.n_u, m.n_u)), dim=2)
+        if a.settings.scaling:
+            J = (J * a.x_range.reshape(1, 1, -1) / a.y_range.reshape(1, -1, 1)).type(a.torch_data_type)
+        return x_scaled, u0_scaled, J
+
     def load_data(self):
         assert self.flags["setup"] == True, "MPC was not setup yet. Please call Trainer.setup()."      # noqa: E712
         st, sc, a = self.settings, self.scheduler_settings, self.approx_mpc
@@ -444,17 +538,9 @@ class Trainer:
         print(f"Path from trainer to sampled files\n {data_dir}")
         with open(data_dir, "rb") as f:
             dataset = pkl.load(f)
-        m = a.mpc.model
-        col = lambda key, n: torch.tensor(np.stack([np.asarray(v, dtype=float).reshape(-1) for v in dataset[key]]),      # noqa: E731
-                                          dtype=a.torch_data_type).reshape(-1, n)
-        x0, u0 = col("x0", m.n_x), col("u0", m.n_u)
-        x = torch.cat((x0, col("u_prev", m.n_u)), dim=1) if a.mpc.flags["set_rterm"] else x0
-        if a.settings.scaling:
-            x_scaled, u0_scaled = self.scale_dataset(x, u0)
-        else:
-            x_scaled, u0_scaled = x, u0
+        tensors = [t.to(self.device) for t in self._scaled_columns(dataset, st.sobolev_weight > 0, data_dir)]
         from torch.utils.data import DataLoader, TensorDataset, random_split
-        data = TensorDataset(x_scaled.to(self.device), u0_scaled.to(self.device))
+        data = TensorDataset(*tensors)
         training_data, val_data = random_split(data, [1 - st.val, st.val], generator=self.generator)
         train_dataloader = DataLoader(training_data, batch_size=st.batch_size, shuffle=st.shuffle, generator=self.generator)
         test_dataloader = DataLoader(val_data, batch_size=st.batch_size, shuffle=st.shuffle, generator=self.generator)
@@ -498,12 +584,21 @@ class Trainer:
                 plt.show()
             plt.close(fig)
 
-    def _loss(self, x, y):
-        return torch.nn.functional.mse_loss(self.approx_mpc(x), y)
+    def _loss(self, x, y, js=None):
+        """mse(net(x), y), plus sobolev_weight mse(J_net(x), js) over the rows of js that are all finite when the weight is positive"""
+        w = self.settings.sobolev_weight
+        if not w > 0:
+            return torch.nn.functional.mse_loss(self.approx_mpc(x), y)
+        out, J = network_jacobian(self.approx_mpc.net, x)
+        loss_u = torch.nn.functional.mse_loss(out, y)
+        labelled = torch.isfinite(js).all(dim=2).all(dim=1)
+        loss_j = torch.nn.functional.mse_loss(J[labelled], js[labelled]) if bool(labelled.any()) else torch.zeros((), dtype=loss_u.dtype, device=loss_u.device)
+        self._terms.append((loss_u.item(), loss_j.item()))
+        return loss_u + w * loss_j
 
-    def train_step(self, optim, x, y):
+    def train_step(self, optim, x, y, js=None):
         """one optimiser step on one mini-batch -> its loss"""
-        loss = self._loss(x, y)
+        loss = self._loss(x, y, js)
         optim.zero_grad()
         loss.backward()
         optim.step()
@@ -511,22 +606,60 @@ class Trainer:
 
     def train_epoch(self, optim, train_loader):
         """mean loss over the mini-batches of one pass"""
-        return fmean(self.train_step(optim, x, y) for x, y in train_loader)
+        return fmean(self.train_step(optim, *batch) for batch in train_loader)
 
-    def validation_step(self, x, y):
+    def validation_step(self, x, y, js=None):
         with torch.no_grad():
-            return self._loss(x, y).item()
+            return self._loss(x, y, js).item()
 
     def validation_epoch(self, val_loader):
-        return fmean(self.validation_step(x, y) for x, y in val_loader)
+        return fmean(self.validation_step(*batch) for batch in val_loader)
+
+    def _mean_terms(self, prefix):
+        """the two terms of the loss, averaged over the mini-batches since the last call (Sobolev training only)"""
+        terms, self._terms = self._terms, []
+        return {prefix + "_u": fmean(t[0] for t in terms), prefix + "_j": fmean(t[1] for t in terms)} if terms else {}
+
+    def sensitivity_error(self, data=None) -> dict:
+        """The network's Jacobian against the stored MPC sensitivities, in the network's coordinates, over the rows of the `_opt` file
+        (or of `data`, a table with the same columns) whose labels are all finite -> {"mse", "max_abs", "n_rows", "n_labelled"}.  The
+        Jacobian comes from ApproxMPC.jacobian_batch when a device is there, otherwise from the torch recursion."""
+        assert self.flags["setup"] == True, "MPC was not setup yet. Please call Trainer.setup()."      # noqa: E712
+        st, a = self.settings, self.approx_mpc
+        source = Path(st.data_dir).joinpath(st.dataset_name).joinpath("data_" + st.dataset_name + "_opt.pkl")
+        if data is None:
+            with open(source, "rb") as f:
+                data = pkl.load(f)
+        xs, _, Js = self._scaled_columns(data, True, source)
+        labelled = torch.isfinite(Js).all(dim=2).all(dim=1)
+        out = {"n_rows": int(Js.shape[0]), "n_labelled": int(labelled.sum())}
+        if not out["n_labelled"]:
+            return {**out, "mse": float("nan"), "max_abs": float("nan")}
+        Js = Js[labelled].double()
+        if torch.cuda.is_available():
+            m = a.mpc.model
+            rows = labelled.numpy()
+            stack = lambda key, n: np.stack([np.asarray(v, dtype=float).reshape(-1) for v in data[key]]).reshape(-1, n)[rows]      # noqa: E731
+            r = a.jacobian_batch(stack("x0", m.n_x), stack("u_prev", m.n_u) if a.rterm else None, clip_to_bounds=False)
+            J = torch.from_numpy(np.concatenate((r["du_dx"], r["du_du_prev"]), axis=2) if a.rterm else r["du_dx"])
+            if a.settings.scaling:
+                J = J * a.x_range.reshape(1, 1, -1) / a.y_range.reshape(1, -1, 1)
+        else:
+            with torch.no_grad():
+                J = network_jacobian(a.net, xs[labelled].to(self.device))[1].double().cpu()
+        err = J - Js
+        return {**out, "mse": float(err.square().mean()), "max_abs": float(err.abs().max())}
 
     def default_training(self):
         assert self.flags["setup"] == True, "MPC was not setup yet. Please call Trainer.setup()."      # noqa: E712
         st = self.settings
         train_loader, val_loader, optimizer = self.load_data()
         for epoch in range(st.n_epochs):
-            row = {"epoch": epoch, "train_loss": self.train_epoch(optimizer, train_loader), "lr": optimizer.param_groups[0]["lr"],
-                   "val_loss": self.validation_epoch(val_loader)}
+            self._terms = []
+            row = {"epoch": epoch, "train_loss": self.train_epoch(optimizer, train_loader), "lr": optimizer.param_groups[0]["lr"]}
+            row.update(self._mean_terms("train_loss"))
+            row["val_loss"] = self.validation_epoch(val_loader)
+            row.update(self._mean_terms("val_loss"))
             for key, val in row.items():
                 self.log_value(val, key)
             if (epoch + 1) % st.print_frequency == 0:

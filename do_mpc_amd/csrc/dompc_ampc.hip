@@ -14,6 +14,21 @@
 // Arithmetic (the reference's promotions): xs = f32((f64(f32(x)) - shift) / range); the network in f32, per neuron an fmaf chain
 // from the bias; y = f64(ys) * (ubu - lbu) + lbu; max(., lbu), min(., ubu) in f64.
 //
+// The Jacobian kernel (dompc_ampc_jac_kernel, the same code object): u as above, bit for bit, and du/dx, du/du_prev of the network
+// for the same 32 samples per wavefront - forward mode, one input direction k after the other (the outermost loop, not unrolled).
+// Per direction the primal and ONE tangent go through the layers together, a layer's primal pass first and its tangent pass behind it:
+// the primal's input is dead when the tangent pass begins, so at most three sets of tiles are live (widest shape: 3 x 64 accumulator
+// registers) where one pass over shared weight operands would hold four - and spill, as the compiler reported for 128 neurons.  The
+// price is that a weight operand is read twice, from the cache.  The cost is about 2 n_in forward passes.
+//
+// Arithmetic of a tangent, f32 in the network's scaled coordinates: the first layer sees the unit vector e_k; a layer maps
+// t_out[i] = d_i * chain, chain = the fmaf chain fmaf(W[i][j], t_in[j], acc) over j in the order of the primal pass from acc = 0 (no
+// bias), d_i = the activation's derivative formed from its OUTPUT a_i as torch's backward forms it, the value at the kink included:
+// relu a > 0 ? 1 : 0, tanh 1 - a a, leaky_relu a > 0 ? 1 : 0.01, sigmoid a (1 - a), linear 1 (products and differences rounded one
+// by one).  A padded neuron's d_i may be non-zero (sigmoid: 0.25); its chain is zero and its column in the next layer is zero.
+// J[i][k] = (f64(t_i) * (ubu - lbu)[i]) / range[k] in f64, product and quotient rounded separately (without scaling J = f64(t));
+// with clip != 0 the row of an output with u < lbu or u > ubu before clipping is zero.  The f32 rounding of the input has no derivative.
+//
 // Build flavours as dompc_lqr.hip: hipcc --genco (product) or g++ -DDOMPC_HOST_EMU (tests).
 #ifndef DOMPC_AMPC_HEADER
 #error "DOMPC_AMPC_HEADER must name the generated network header"
@@ -66,10 +81,43 @@ AMPC_DEV void layer(const float* __restrict__ W, const Tile (&in)[TK], Tile (&ou
   }
 }
 
-// the 32 samples from `first` on
-AMPC_DEV void step32(const Args& A, int64_t first) {
-  const double *shift = A.par, *range = A.par + NI, *lbu = A.par + 2 * NI, *ubu = lbu + NO, *yrange = ubu + NO;
-  Tile x[TI];
+// d act / d(pre-activation) from the activation's OUTPUT a (torch's backward formulas)
+template <int ACT>
+AMPC_DEV float activation_slope(float a) {
+#pragma clang fp contract(off)
+  if (ACT == 0) return a > 0.0f ? 1.0f : 0.0f;
+  if (ACT == 1) return 1.0f - a * a;
+  if (ACT == 2) return a > 0.0f ? 1.0f : 0.01f;
+  if (ACT == 3) return a * (1.0f - a);
+  return 1.0f;
+}
+
+// the tangent of layer(): tout <- diag(act'(out)) W tin, `out` being what layer() left (the activations)
+template <int TK, int TO, int KIN, int ACT>
+AMPC_DEV void layer_tangent(const float* __restrict__ W, const Tile (&tin)[TK], const Tile (&out)[TO], Tile (&tout)[TO]) {
+#pragma unroll
+  for (int to = 0; to < TO; ++to) {
+#pragma unroll
+    for (int g = 0; g < 16; ++g) lanes([&](int l) { tset(tout[to], g, l, 0.0f); });
+#pragma unroll
+    for (int tk = 0; tk < TK; ++tk) {
+#pragma unroll
+      for (int g = 0; g < 16; ++g) {
+        if (32 * tk + AMPC_ROW(g, 0) < KIN) {
+          wf a;
+          lanes([&](int l) { wset(a, l, W[((to * TK + tk) * 16 + g) * 64 + l]); });
+          mfma_32x32x2(a, tcol(tin[tk], g), tout[to]);
+        }
+      }
+    }
+#pragma unroll
+    for (int g = 0; g < 16; ++g) lanes([&](int l) { tset(tout[to], g, l, activation_slope<ACT>(tget(out[to], g, l)) * tget(tout[to], g, l)); });
+  }
+}
+
+// the scaled network input of the 32 samples from `first` on
+AMPC_DEV void scaled_input(const Args& A, int64_t first, Tile (&x)[TI]) {
+  const double *shift = A.par, *range = A.par + NI;
 #pragma unroll
   for (int t = 0; t < TI; ++t) {
 #pragma unroll
@@ -86,6 +134,30 @@ AMPC_DEV void step32(const Args& A, int64_t first) {
         tset(x[t], g, l, xs);
       });
   }
+}
+
+// output i of the network -> the input u_i, rescaled and (A.clip) clipped; *outside: u_i lay beyond a bound before clipping
+AMPC_DEV double rescaled_output(const Args& A, int i, float ys, bool* outside) {
+  const double *lbu = A.par + 2 * NI, *ubu = lbu + NO, *yrange = ubu + NO;
+  double u = (double)ys;
+  if (AMPC_SCALING) {
+    // product and sum rounded separately, like the reference's two operations: no contraction into one fma here
+#pragma clang fp contract(off)
+    const double m = u * yrange[i];
+    u = m + lbu[i];
+  }
+  *outside = u < lbu[i] || u > ubu[i];
+  if (A.clip) {
+    u = u > lbu[i] ? u : lbu[i];
+    u = u < ubu[i] ? u : ubu[i];
+  }
+  return u;
+}
+
+// the 32 samples from `first` on
+AMPC_DEV void step32(const Args& A, int64_t first) {
+  Tile x[TI];
+  scaled_input(A, first, x);
   Tile y[1];
   if constexpr (NH == 0) {
     layer<TI, 1, NI, AMPC_ACT>(A.w, x, y);
@@ -108,20 +180,73 @@ AMPC_DEV void step32(const Args& A, int64_t first) {
       const int i = AMPC_ROW(g, l >> 5);
       const int64_t s = first + (l & 31);
       if (i < NO && s < A.batch) {
-        double u = (double)tget(y[0], g, l);
-        if (AMPC_SCALING) {
-          // product and sum rounded separately, like the reference's two operations: no contraction into one fma here
-#pragma clang fp contract(off)
-          const double m = u * yrange[i];
-          u = m + lbu[i];
-        }
-        if (A.clip) {
-          u = u > lbu[i] ? u : lbu[i];
-          u = u < ubu[i] ? u : ubu[i];
-        }
-        A.u[s * NO + i] = u;
+        bool outside;
+        A.u[s * NO + i] = rescaled_output(A, i, tget(y[0], g, l), &outside);
       }
     });
+}
+
+// u and the Jacobian of the 32 samples from `first` on
+AMPC_DEV void jac32(const JacArgs& J, int64_t first) {
+  Args A = J.step;
+  const int nup = NI - A.nx;
+  Tile x[TI];
+  scaled_input(A, first, x);
+#pragma unroll 1
+  for (int k = 0; k < NI; ++k) {
+    // weights, biases and bounds are the same in every direction: read again per direction they cost a cache hit, hoisted out of this
+    // loop they would sit in more than a hundred registers through all of it
+    A.w = reloaded(A.w);
+    A.par = reloaded(A.par);
+    const double *range = A.par + NI, *yrange = A.par + 2 * NI + 2 * NO;
+    Tile e[TI];                                                // the unit vector e_k, for every sample
+#pragma unroll
+    for (int t = 0; t < TI; ++t) {
+#pragma unroll
+      for (int g = 0; g < 16; ++g) lanes([&](int l) { tset(e[t], g, l, 32 * t + AMPC_ROW(g, l >> 5) == k ? 1.0f : 0.0f); });
+    }
+    Tile y[1], ty[1];
+    if constexpr (NH == 0) {
+      layer<TI, 1, NI, AMPC_ACT>(A.w, x, y);
+      layer_tangent<TI, 1, NI, AMPC_ACT>(A.w, e, y, ty);
+    } else {
+      Tile h[TN], th[TN], n[TN], tn[TN];
+      layer<TI, TN, NI, AMPC_ACT>(A.w, x, h);
+      layer_tangent<TI, TN, NI, AMPC_ACT>(A.w, e, h, th);
+      const float* W = A.w + layer_floats(TI, TN);
+#pragma unroll 1
+      for (int q = 1; q < NH; ++q) {
+        layer<TN, TN, NN, AMPC_ACT>(W, h, n);
+        layer_tangent<TN, TN, NN, AMPC_ACT>(W, th, n, tn);
+#pragma unroll
+        for (int t = 0; t < TN; ++t) { h[t] = n[t]; th[t] = tn[t]; }
+        W += layer_floats(TN, TN);
+      }
+      layer<TN, 1, NN, AMPC_OUT_ACT>(W, h, y);
+      layer_tangent<TN, 1, NN, AMPC_OUT_ACT>(W, th, y, ty);
+    }
+#pragma unroll
+    for (int g = 0; g < 16; ++g)
+      lanes([&](int l) {
+        const int i = AMPC_ROW(g, l >> 5);
+        const int64_t s = first + (l & 31);
+        if (i < NO && s < A.batch) {
+          bool outside;
+          const double u = rescaled_output(A, i, tget(y[0], g, l), &outside);
+          if (k == 0) A.u[s * NO + i] = u;
+          double d = (double)tget(ty[0], g, l);
+          if (AMPC_SCALING) {
+            // product and quotient rounded separately
+#pragma clang fp contract(off)
+            const double m = d * yrange[i];
+            d = m / range[k];
+          }
+          if (A.clip && outside) d = 0.0;
+          if (k < A.nx) J.du_dx[(s * NO + i) * A.nx + k] = d;
+          else J.du_du_prev[(s * NO + i) * nup + (k - A.nx)] = d;
+        }
+      });
+  }
 }
 
 }  // namespace dompc_ampck
@@ -130,7 +255,7 @@ AMPC_DEV void step32(const Args& A, int64_t first) {
   do {                                                                                                                        \
     using namespace dompc_ampck;                                                                                              \
     out[0] = NI; out[1] = NO; out[2] = NH; out[3] = NN; out[4] = AMPC_ACT; out[5] = AMPC_OUT_ACT; out[6] = AMPC_SCALING;      \
-    out[7] = (int64_t)sizeof(Args); out[8] = PACKED;                                                                          \
+    out[7] = (int64_t)sizeof(Args); out[8] = PACKED; out[9] = (int64_t)sizeof(JacArgs);                                   \
     const char h_[] = AMPC_MODEL_HASH;                                                                                        \
     for (int i = 0; i < (int)sizeof(h_); ++i) hash[i] = h_[i];                                                                \
   } while (0)
@@ -139,6 +264,9 @@ AMPC_DEV void step32(const Args& A, int64_t first) {
 extern "C" __global__ void __launch_bounds__(64) dompc_ampc_kernel(dompc_ampck::Args A) {
   dompc_ampck::step32(A, (int64_t)blockIdx.x * 32);
 }
+extern "C" __global__ void __launch_bounds__(64) dompc_ampc_jac_kernel(dompc_ampck::JacArgs J) {
+  dompc_ampck::jac32(J, (int64_t)blockIdx.x * 32);
+}
 extern "C" __global__ void dompc_ampc_info_kernel(int64_t* out, char* hash) {
   if (threadIdx.x == 0 && blockIdx.x == 0) AMPC_INFO(out, hash);
 }
@@ -146,5 +274,8 @@ extern "C" __global__ void dompc_ampc_info_kernel(int64_t* out, char* hash) {
 extern "C" void dompc_ampc_hostemu_info(int64_t* out, char* hash) { AMPC_INFO(out, hash); }
 extern "C" void dompc_ampc_hostemu_run(const dompc_ampck::Args* A) {
   for (int64_t first = 0; first < A->batch; first += 32) dompc_ampck::step32(*A, first);
+}
+extern "C" void dompc_ampc_hostemu_jac(const dompc_ampck::JacArgs* J) {
+  for (int64_t first = 0; first < J->step.batch; first += 32) dompc_ampck::jac32(*J, first);
 }
 #endif

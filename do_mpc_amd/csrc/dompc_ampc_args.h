@@ -1,4 +1,4 @@
-// dompc_ampc_args.h - kernel argument block of the batched approximate-MPC network step, shared by the generic host runtime
+// dompc_ampc_args.h - kernel argument blocks of the batched approximate-MPC network step and of its Jacobian, shared by the generic host runtime
 // (dompc_ampc_runtime.cpp) and the per-network device code (dompc_ampc.hip).  Plain data, no size that depends on the network.
 #pragma once
 #include <stdint.h>
@@ -12,5 +12,10 @@ struct Args {
   int32_t batch, nx;
   int32_t clip;                              // != 0: max(., lbu) then min(., ubu)
   int32_t pad_;
+};
+// the Jacobian kernel: the step and, beside u, the network's Jacobian (a clipped output's row is zero)
+struct JacArgs {
+  Args step;
+  double *du_dx, *du_du_prev;                // out: [B][n_out][nx], [B][n_out][n_in - nx] (null when the network input is x alone)
 };
 }  // namespace dompc_ampck

@@ -9,6 +9,7 @@
 #ifdef DOMPC_HOST_EMU
 extern "C" void dompc_ampc_hostemu_info(int64_t* out, char* hash);
 extern "C" void dompc_ampc_hostemu_run(const dompc_ampck::Args* A);
+extern "C" void dompc_ampc_hostemu_jac(const dompc_ampck::JacArgs* J);
 #endif
 
 static thread_local std::string g_ampc_create_error;
@@ -21,9 +22,11 @@ struct dompc_ampc : dompc_host::Context {
   double* par = nullptr;
   int32_t cap = 0;
   double *s_x = nullptr, *s_up = nullptr, *s_u = nullptr;
+  int32_t cap_jac = 0;                   // staging of the Jacobian's two outputs (its x, u_prev and u are the step's)
+  double *s_dx = nullptr, *s_dup = nullptr;
 #ifndef DOMPC_HOST_EMU
   hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr, fn_info = nullptr;
+  hipFunction_t fn = nullptr, fn_jac = nullptr, fn_info = nullptr;
 #endif
 };
 
@@ -47,7 +50,8 @@ extern "C" int dompc_ampc_create(const dompc_ampc_desc* desc, dompc_ampc** out) 
   char hash[64] = {0};
 #ifndef DOMPC_HOST_EMU
   if (h->open_device("approximate MPC") ||
-      h->load_module(desc->code_object_path, &h->module, {{"dompc_ampc_kernel", &h->fn}, {"dompc_ampc_info_kernel", &h->fn_info}},
+      h->load_module(desc->code_object_path, &h->module,
+                     {{"dompc_ampc_kernel", &h->fn}, {"dompc_ampc_jac_kernel", &h->fn_jac}, {"dompc_ampc_info_kernel", &h->fn_info}},
                      "code object lacks the network kernels") ||
       h->query_info(h->fn_info, "dompc_ampc_info_kernel", info, hash))
     return fail();
@@ -56,6 +60,7 @@ extern "C" int dompc_ampc_create(const dompc_ampc_desc* desc, dompc_ampc** out) 
 #endif
   const int64_t want[7] = {desc->n_in, desc->n_out, desc->n_hidden_layers, desc->n_neurons, desc->act, desc->out_act, desc->scaling ? 1 : 0};
   if (h->check_info("network ", info, want, 7, 7, sizeof(dompc_ampck::Args), hash, desc->model_hash)) return fail();
+  if (info[9] != (int64_t)sizeof(dompc_ampck::JacArgs)) { h->error = "network argument layout mismatch between runtime and code object (Jacobian kernel)"; return fail(); }
   h->packed = info[8];
   if (h->packed <= 0) { h->error = "network code object reports no weights"; return fail(); }
   if (h->alloc((void**)&h->w, sizeof(float) * (size_t)h->packed) ||
@@ -125,5 +130,49 @@ extern "C" int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, 
   if (h->h2d(h->s_x, x, D * B * d.nx) || (nup > 0 && h->h2d(h->s_up, u_prev, D * B * nup))) return 1;
   if (dompc_ampc_step_batch_device(h, B, h->s_x, nup > 0 ? h->s_up : nullptr, h->s_u, clip, h->stream_ptr())) return 1;
   if (h->d2h(u_out, h->s_u, D * B * d.n_out)) return 1;
+  return h->sync();
+}
+
+extern "C" int dompc_ampc_jacobian_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, double* du_dx,
+                                                double* du_du_prev, int32_t clip, void* stream) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  const dompc_ampc_desc& d = h->d;
+  if (!h->have_weights) { h->error = "no weights: call dompc_ampc_set_weights first"; return 1; }
+  if (!x || !u || !du_dx || (d.n_in > d.nx && (!u_prev || !du_du_prev))) { h->error = "null pointer"; return 1; }
+  dompc_ampck::JacArgs G;
+  memset(&G, 0, sizeof(G));
+  G.step.x = x; G.step.u_prev = u_prev; G.step.u = u; G.step.w = h->w; G.step.par = h->par;
+  G.step.batch = B; G.step.nx = d.nx; G.step.clip = clip ? 1 : 0;
+  G.du_dx = du_dx; G.du_du_prev = d.n_in > d.nx ? du_du_prev : nullptr;
+  if (h->set_device()) return 1;
+#ifndef DOMPC_HOST_EMU
+  return h->launch(h->fn_jac, (unsigned)(((int64_t)B + 31) / 32), 64, 0, (hipStream_t)stream, &G, sizeof(G));
+#else
+  (void)stream;
+  dompc_ampc_hostemu_jac(&G);
+  return 0;
+#endif
+}
+
+extern "C" int dompc_ampc_jacobian_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, double* du_dx,
+                                         double* du_du_prev, int32_t clip) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  const dompc_ampc_desc& d = h->d;
+  const int nup = d.n_in - d.nx;
+  if (!x || !u_out || !du_dx || (nup > 0 && (!u_prev || !du_du_prev))) { h->error = "null pointer"; return 1; }
+  if (h->set_device()) return 1;
+  const size_t D = sizeof(double);
+  if (h->grow_staging(&h->cap, B, {{(void**)&h->s_x, D * d.nx}, {(void**)&h->s_up, D * nup}, {(void**)&h->s_u, D * d.n_out}}) ||
+      h->grow_staging(&h->cap_jac, B, {{(void**)&h->s_dx, D * d.n_out * d.nx}, {(void**)&h->s_dup, D * d.n_out * nup}}))
+    return 1;
+  if (h->h2d(h->s_x, x, D * B * d.nx) || (nup > 0 && h->h2d(h->s_up, u_prev, D * B * nup))) return 1;
+  if (dompc_ampc_jacobian_batch_device(h, B, h->s_x, nup > 0 ? h->s_up : nullptr, h->s_u, h->s_dx, nup > 0 ? h->s_dup : nullptr, clip,
+                                       h->stream_ptr()))
+    return 1;
+  if (h->d2h(u_out, h->s_u, D * B * d.n_out) || h->d2h(du_dx, h->s_dx, D * B * d.n_out * d.nx) ||
+      (nup > 0 && h->d2h(du_du_prev, h->s_dup, D * B * d.n_out * nup)))
+    return 1;
   return h->sync();
 }

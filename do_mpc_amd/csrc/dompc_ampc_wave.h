@@ -34,6 +34,8 @@ AMPC_DEV float tget(const Tile& t, int g, int) { return t.v[g]; }
 AMPC_DEV void tset(Tile& t, int g, int, float x) { t.v[g] = x; }
 AMPC_DEV wf tcol(const Tile& t, int g) { return t.v[g]; }
 AMPC_DEV void mfma_32x32x2(const wf& a, const wf& b, Tile& c) { c.v = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, c.v, 0, 0, 0); }
+// p, as a value the compiler knows nothing about: loads through it are not hoisted out of the loop this is called in
+template <class T> AMPC_DEV const T* reloaded(const T* p) { asm volatile("" : "+s"(p)); return p; }
 AMPC_DEV float ampc_tanh(float x) { return tanhf(x); }
 AMPC_DEV float ampc_exp(float x) { return expf(x); }
 #else
@@ -61,6 +63,7 @@ AMPC_DEV void mfma_32x32x2(const wf& a, const wf& b, Tile& c) {
       c.v[g][l] = acc;
     }
 }
+template <class T> AMPC_DEV const T* reloaded(const T* p) { return p; }
 AMPC_DEV float ampc_tanh(float x) { return std::tanh(x); }
 AMPC_DEV float ampc_exp(float x) { return std::exp(x); }
 #endif

@@ -64,21 +64,26 @@ def build_ampc(mpc, setup: bool = True, n_hidden_layers=N_HIDDEN_LAYERS, n_neuro
     return ampc
 
 
-def build_sampler(mpc, dataset_name: str, n_samples: int, data_dir: str, simulator=None, closed_loop: bool = False) -> AMPCSampler:
+def build_sampler(mpc, dataset_name: str, n_samples: int, data_dir: str, simulator=None, closed_loop: bool = False,
+                  sensitivities: bool = False) -> AMPCSampler:
+    """sensitivities=True: the data file also carries du0dx0 and du0du_prev of every row (the labels of Sobolev training)"""
     sampler = AMPCSampler(mpc, simulator)
     st = sampler.settings
     st.dataset_name, st.n_samples, st.data_dir = dataset_name, n_samples, data_dir
     st.closed_loop_flag, st.trajectory_length = closed_loop, 1
+    st.store_sensitivities = sensitivities
     box(st)
     sampler.setup()
     return sampler
 
 
-def build_trainer(ampc, dataset_name: str, n_epochs: int, data_dir: str, results_dir: str):
+def build_trainer(ampc, dataset_name: str, n_epochs: int, data_dir: str, results_dir: str, sobolev_weight: float = 0.0):
+    """sobolev_weight > 0: the loss also fits the network's Jacobian to the stored sensitivities (build_sampler(sensitivities=True))"""
     from ..ampc import Trainer
     trainer = Trainer(ampc)
     st = trainer.settings
     st.dataset_name, st.n_epochs, st.data_dir, st.results_dir = dataset_name, n_epochs, data_dir, results_dir
+    st.sobolev_weight = sobolev_weight
     st.save_history = True
     st.scheduler_flag = True
     trainer.scheduler_settings.cooldown = 0

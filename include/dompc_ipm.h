@@ -427,6 +427,15 @@ int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const doubl
 /* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*) */
 int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, int32_t clip_to_bounds,
                                  void* stream);
+/* The network's own Jacobian beside the step, ONE launch (dompc_ampc_jac_kernel of the same code object, forward mode in float32):
+ * u [B][n_out] exactly as the step writes it; du_dx [B][n_out][nx] and du_du_prev [B][n_out][n_in - nx] (NULL when n_in == nx), the
+ * derivative of the unclipped u with respect to x and u_prev in physical units; with clip_to_bounds the row of an output that lay
+ * beyond a bound is zero.  The weights are those of the last dompc_ampc_set_weights. */
+int dompc_ampc_jacobian_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, double* du_dx,
+                              double* du_du_prev, int32_t clip_to_bounds);
+/* DEVICE buffers, asynchronous on `stream`; nothing behind row B of any output is written */
+int dompc_ampc_jacobian_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, double* du_dx,
+                                     double* du_du_prev, int32_t clip_to_bounds, void* stream);
 
 /* ---- affine state feedback  u = sat(u_ref + M (x - x_ref))  for B loops (csrc/dompc_affine.h) --------------------------------
  * The law record.  Every pointer is a DEVICE address; arrays are laid out with the loops innermost, so that one thread per loop reads
