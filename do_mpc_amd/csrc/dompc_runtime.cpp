@@ -15,6 +15,10 @@
 
 #include "dompc_host.h"
 #include "dompc_kargs.h"
+#include "dompc_shape.h"
+
+using dompc_launch::BATCH_ONE_WAVE;
+using dompc_launch::fit_block;
 
 #ifdef DOMPC_HOST_EMU
 extern "C" void dompc_hostemu_model_info(const int32_t* in, int64_t* out, char* hash);
@@ -22,7 +26,6 @@ extern "C" void dompc_hostemu_run(const dompc::KArgs* A);
 #endif
 
 static thread_local std::string g_create_error;
-static const int BATCH_ONE_WAVE = 4096;     // batch size from which a problem gets one wavefront instead of four (see dompc_create)
 
 struct dompc_handle : dompc_host::Context {
   dompc_problem_desc d;
@@ -198,13 +201,33 @@ static void* own_stream(dompc_handle* h) {
 #endif
 }
 
-// largest workgroup size <= `block` whose LDS pool (one edge working set per wavefront) fits the 160 KiB of a CU - models with
-// a large dense edge working set (DAE path: 45 kB per wavefront for the double inverted pendulum) run with fewer wavefronts
-// per workgroup
-static int fit_block(const dompc_handle* h, int block) {
-  const int64_t lds_max = 160 * 1024 - 4096;                     // (static LDS of the kernel: filter, flags, counters)
-  while (block > 64 && (int64_t)(block / 64) * h->el_size * (int64_t)sizeof(double) > lds_max) block /= 2;
-  return block;
+// what the launch shape is decided from (dompc_shape.h)
+static dompc_shape_facts shape_facts(const dompc_handle* h) {
+  return dompc_shape_facts{h->d.n_edges, h->n_leaves, (int32_t)h->edges_per_wave, h->el_size, h->slots64, h->slots256, h->n_slots, h->block,
+                           h->block_auto ? 1 : 0, h->sharded ? 1 : 0};
+}
+#ifndef DOMPC_HOST_EMU
+// DOMPC_WIDE / DOMPC_WIDE_SPREAD / DOMPC_WIDE_BLOCK, read at every solve.  Values that the decision never told apart are folded: a
+// DOMPC_WIDE below 1 is one workgroup per problem like 0, and a DOMPC_WIDE_BLOCK other than 64/128/256/512 ran 256 threads like 256.
+static dompc_shape_overrides shape_overrides() {
+  dompc_shape_overrides o = {-1, -1, 0};
+  if (const char* we = getenv("DOMPC_WIDE")) { const int v = atoi(we); o.wide = v > 0 ? v : 0; }
+  if (const char* se = getenv("DOMPC_WIDE_SPREAD")) o.wide_spread = atoi(se) != 0 ? 1 : 0;
+  if (const char* wb = getenv("DOMPC_WIDE_BLOCK")) { const int v = atoi(wb); o.wide_block = (v == 64 || v == 128 || v == 256 || v == 512) ? v : 256; }
+  return o;
+}
+#endif
+
+extern "C" int dompc_launch_shape(const dompc_shape_facts* facts, const dompc_shape_overrides* overrides, int32_t B, dompc_shape* out) {
+  if (!facts || !overrides || !out || B < 1) return 1;
+  *out = dompc_launch::solve_shape(*facts, *overrides, B);
+  return 0;
+}
+
+// doubles of the LDS pool of a workgroup of `block` threads: one edge working set per wavefront, or the reduction rows if they are larger
+static int64_t pool_doubles(const dompc_handle* h, int block) {
+  const int64_t per_wave = (int64_t)(block / 64) * h->el_size, red = h->xlayout[0] * (int64_t)block;
+  return per_wave > red ? per_wave : red;
 }
 
 // `block` threads per workgroup (a multiple of 64): the LDS pool is sized for block/64 wavefronts
@@ -212,8 +235,7 @@ static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* s
 #ifndef DOMPC_HOST_EMU
   hipStream_t st = (hipStream_t)stream_v;          // nullptr = HIP default stream
   if (dev_zero(h, A.work_counter, sizeof(int32_t), st)) return 1;
-  const int64_t per_wave = (int64_t)(block / 64) * h->el_size, red = h->xlayout[0] * (int64_t)block;
-  A.pool_doubles = (int32_t)(per_wave > red ? per_wave : red);
+  A.pool_doubles = (int32_t)pool_doubles(h, block);
   // (batch launches of the solver with one 64-thread workgroup per problem, not sharded, run the build of the kernels that is compiled for
   //  exactly that shape when it was loaded: build.py batch_only)
   hipFunction_t fn = (h->fn_solve_batch && (A.mode == 0 || A.mode == 2) && A.wide <= 1 && block == 64 && !h->sharded) ? h->fn_solve_batch : h->fn_solve;
@@ -326,8 +348,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   auto resident_at = [&](int block) -> int {
     int resident = 512 * (256 / block);
 #ifndef DOMPC_HOST_EMU
-    const int64_t per_wave = (int64_t)(block / 64) * h->el_size, red = h->xlayout[0] * (int64_t)block;
-    const size_t lds = sizeof(double) * (size_t)(per_wave > red ? per_wave : red);
+    const size_t lds = sizeof(double) * (size_t)pool_doubles(h, block);
     int occ = 0, cus = 0;
     if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->fn_solve, block, lds) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device) == hipSuccess && occ > 0 && cus > 0)
@@ -337,7 +358,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
     return resident;
   };
   h->slots64 = resident_at(64);
-  h->slots256 = resident_at(fit_block(h, 256));
+  h->slots256 = resident_at(fit_block(h->el_size, 256));
   {
     // batches of >= BATCH_ONE_WAVE problems run one wavefront per problem and need that many more slots
     const int resident = h->block_auto ? (max_batch >= BATCH_ONE_WAVE ? h->slots64 : h->slots256) : resident_at(h->block);
@@ -661,11 +682,6 @@ extern "C" int dompc_solve_batch_device(dompc_handle* h, int32_t B, const double
   A.x0 = x0; A.lbx = lbx; A.ubx = ubx; A.lbg = lbg; A.ubg = ubg; A.p = p;
   A.x_out = x; A.g_out = g; A.lam_x_out = lam_x; A.lam_g_out = lam_g; A.f_out = f; A.stats = stats;
   A.batch = B; A.mode = 0;
-  const int block = fit_block(h, h->block_auto ? (B >= BATCH_ONE_WAVE ? 64 : 256) : h->block);
-  const int cap = (h->block_auto && block != 64 && h->slots256 < h->n_slots) ? h->slots256 : h->n_slots;   // resident workgroups at this block size
-  int grid = B < cap ? B : cap;
-  A.wide = 1;
-  A.wide_spread = 0;
   if (h->sharded) {
     if (B != 1) { h->error = "a sharded handle solves one problem per call"; return 1; }
 #ifndef DOMPC_HOST_EMU
@@ -674,72 +690,18 @@ extern "C" int dompc_solve_batch_device(dompc_handle* h, int32_t B, const double
 #endif
   }
 #ifndef DOMPC_HOST_EMU
-  // small batches: several workgroups per problem so that one make_step can use many CUs
-  const char* wenv = getenv("DOMPC_WIDE");
-  // enough workgroups that every wavefront owns about two edges, fewer when the batch itself fills the chip
-  // (measured on MI355X, single cold industrial_poly step, round-2 kernels: K = 4 / 8 / 16 / 32 -> 27.1 / 23.4 / 22.6 / 26.0 ms;
-  //  CSTR 9.1 / - / 8.3 / 10.2 ms - the device-scope barriers grow with K faster than the phases shrink)
-  int K = wenv ? atoi(wenv) : (B <= 8 ? 16 : (B <= 32 ? 8 : (B <= 64 ? 4 : 1)));
-  if (!wenv && K > h->d.n_edges / 8) K = h->d.n_edges / 8 > 1 ? h->d.n_edges / 8 : 1;
-  // Whole-chip placement (KArgs::wide_spread): the K workgroups of a problem are consecutive blocks, which the dispatcher spreads over
-  // all XCDs, instead of K blocks of ONE XCD (<= 32 CUs); the device-scope barrier then keeps its L2 write-back (xcd_census sees the
-  // placement).  One problem alone always runs this way: measured on MI355X (tools/gpu_wide_spread.py, profiles/r05_wide_spread.txt) the
-  // 243-leaf tree of BASELINE configs[4] (4 008 edges) takes 72.3 ms with K = 32 on one XCD, 67.4 ms with the same K spread and
-  // 49.7 / 48.9 / 49.3 / 55.6 / 63.8 ms with K = 64 / 96 / 128 / 192 / 256; the shipped 9-scenario problem (180 edges) 19.1 ms with 16
-  // workgroups of one XCD and 18.2 / 18.0 / 18.8 ms with 16 / 24 / 32 spread - the barriers grow with K, the phases shrink with
-  // sqrt-like returns: K ~ 12 sqrt(edges / 45).  DOMPC_WIDE_SPREAD=0/1 and DOMPC_WIDE override.
-  const char* senv = getenv("DOMPC_WIDE_SPREAD");
-  int auto_block = 256;
-  bool spread = senv ? atoi(senv) != 0 : (!h->sharded && (B == 1 || (B <= 4 && h->d.n_edges >= 2048)));
-  if (spread && !wenv) {
-    // Round 6 (tools/gpu_b1_k_sweep.sh, tools/gpu_tree_k_sweep.sh; the phases got faster, the barriers did not): the 180-edge problem
-    // 24.7 / 22.8 / 22.9 / 23.1 / 23.5 / 24.0 / 25.7 ms (84 iterations) with K = 8 / 12 / 16 / 20 / 24 / 32 / 48, the 243-leaf tree 53.8 /
-    // 49.5 / 38.9 / 39.5 / 39.6 / 39.8 / 40.1 ms with K = 32 / 48 / 64 / 80 / 96 / 112 / 128 - K ~ 6.4 sqrt(edges / 45) in steps of four,
-    // and at least one wavefront per scenario chain (four wavefronts per workgroup): below that some wavefronts walk two chains of the
-    // Riccati passes one after the other - the step between K = 48 and 64 on the tree.
-    int Ks = 4 * (int)lround(1.6 * sqrt((double)h->d.n_edges / 45.0));
-    if (4 * Ks < h->n_leaves) Ks = 4 * ((h->n_leaves + 15) / 16);
-    // ... and for the small problems on the four-edge sweep two wavefronts per workgroup instead of four, twice the workgroups
-    // (tools/gpu_b1_block_sweep.sh: the 180-edge problem 22.6 ms with 12 x 256 threads, 21.3 ms with 24 x 128 - 48 wavefronts either way,
-    // one quad of edges each; 20 x 128: 22.6, 28 x 128: 21.7, 32 x 128: 21.7, 32 x 64: 23.2; the tree prefers 64 x 256: 38.9 against 42.6 ms
-    // with 128 x 128 - there the barrier grows with the workgroups)
-    if (h->edges_per_wave == 4 && Ks <= 16 && !getenv("DOMPC_WIDE_BLOCK")) { auto_block = 128; Ks *= 2; }
-    if (Ks > h->d.n_edges / 7) Ks = h->d.n_edges / 7;
-    if (Ks > 256 / B) Ks = 256 / B;
-    // (fewer than eight workgroups: the problem is too small for the whole chip - its few workgroups stay on one XCD with the light
-    //  barrier; measured: CSTR nominal, 20 edges, 4.9 ms on one XCD against 5.6 ms with its two workgroups on two XCDs)
-    if (Ks >= 8 || senv) K = Ks < 1 ? 1 : Ks; else spread = false;
-  }
-  if (K > (spread ? 256 : 32)) K = spread ? 256 : 32;
-  if (spread && (int64_t)B * K > 2048) spread = false;       // (reduction partials: 64 x 32 workgroup rows)
-  if (!spread && K > 32) K = 32;
-  {
-    // Co-residency: the device-scope barrier of the wide mode needs EVERY workgroup of the launch on the chip at the same time - a
-    // workgroup that waits for a free CU never arrives and its peers spin until the watchdog.  The grid is therefore capped by what this
-    // device keeps resident at the wide mode's workgroup size (occupancy of the kernel x compute units: a partitioned or smaller part,
-    // a DOMPC_WIDE / DOMPC_WIDE_SPREAD override); K shrinks until it fits, down to one workgroup per problem.  (What this cannot see:
-    // other kernels on the device - INTEGRATION.md section 4.)
-    const int wb_ = fit_block(h, 256);
-    const int64_t resident = (wb_ == 256 || h->slots64 <= 0) ? h->slots256 : (int64_t)h->slots64 * 64 / wb_;
-    auto grid_of = [&](int k, bool sp) -> int64_t { return sp ? (int64_t)B * k : (int64_t)((B + 7) / 8) * 8 * k; };
-    while (K > 1 && resident > 0 && grid_of(K, spread) > resident) --K;
-  }
-  if (K > 1 && B <= 64 && B <= h->n_slots) {
-    A.wide = K;
-    A.wide_spread = spread ? 1 : 0;
-    grid = spread ? B * K : ((B + 7) / 8) * 8 * K;
+  const dompc_shape s = dompc_launch::solve_shape(shape_facts(h), shape_overrides(), B);
+  if (s.wide > 1) {
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(h, hipMemsetAsync(A.wide_bar, 0, sizeof(uint32_t) * dompc::WIDE_BAR_STRIDE * 64, st));
     HIPCHK(h, hipMemsetAsync(A.wide_flags, 0, sizeof(int32_t) * 8 * 64, st));
   }
-#endif
-#ifndef DOMPC_HOST_EMU
-  int wide_block = (A.wide > 1 && A.wide_spread) ? auto_block : 256;
 #else
-  int wide_block = 256;
+  const dompc_shape s = dompc_launch::batch_shape(shape_facts(h), B);      // (a workgroup is the calling thread: grid and block are ignored)
 #endif
-  if (const char* wb = getenv("DOMPC_WIDE_BLOCK")) { const int v = atoi(wb); if (v == 64 || v == 128 || v == 256 || v == 512) wide_block = v; }   // (512 needs a code object built with -DDOMPC_MAXBLOCK=512)
-  if (launch(h, A, grid, (A.wide > 1 || h->sharded) ? fit_block(h, wide_block) : block, stream)) return 1;
+  A.wide = s.wide;
+  A.wide_spread = s.wide_spread;
+  if (launch(h, A, s.grid, s.block, stream)) return 1;
 #ifndef DOMPC_HOST_EMU
   if (h->sharded) return serve_exchanges(h, (hipStream_t)stream);
 #endif
@@ -814,10 +776,8 @@ extern "C" int dompc_sweep_batch_device(dompc_handle* h, int32_t B, const double
   A.p = p; A.sw_x = x; A.sw_lam = lam; A.sw_g = g; A.sw_blocks = blocks;
   A.batch = B; A.mode = 2;
   // (same launch shape as a solve of that many problems: one 64-thread workgroup per iterate from BATCH_ONE_WAVE on)
-  const int block = fit_block(h, h->block_auto ? (B >= BATCH_ONE_WAVE ? 64 : 256) : h->block);
-  const int cap = (h->block_auto && block != 64 && h->slots256 < h->n_slots) ? h->slots256 : h->n_slots;
-  const int grid = B < cap ? B : cap;
-  return launch(h, A, grid, block, stream);
+  const dompc_shape s = dompc_launch::batch_shape(shape_facts(h), B);
+  return launch(h, A, s.grid, s.block, stream);
 }
 
 static int newton_step_impl(dompc_handle* h, const double* x, const double* lam_g, const double* zl,
@@ -846,7 +806,7 @@ static int newton_step_impl(dompc_handle* h, const double* x, const double* lam_
   A.dbg_dx = h->s_dbg[3]; A.dbg_dlam = h->s_dbg[4]; A.dbg_rd = h->s_dbg[5]; A.dbg_c = h->s_dbg[6];
   A.dbg_mu = mu; A.dbg_delta = delta_w;
   A.batch = 1; A.mode = 1; A.dbg_at_solution = at_solution;
-  if (launch(h, A, 1, fit_block(h, 256), h->stream_ptr())) return 1;
+  if (launch(h, A, 1, fit_block(h->el_size, 256), h->stream_ptr())) return 1;
   if (dx) rc |= h->d2h(dx, h->s_dbg[3], sizeof(double) * d.n_opt_x);
   if (dlam) rc |= h->d2h(dlam, h->s_dbg[4], sizeof(double) * d.n_g);
   if (rd) rc |= h->d2h(rd, h->s_dbg[5], sizeof(double) * d.n_opt_x);
@@ -900,7 +860,7 @@ extern "C" int dompc_newton_steps_at_solution(dompc_handle* h, int32_t B, const 
     A.dbg_dx = h->s_x; A.dbg_dlam = h->s_lamg; A.dbg_rd = h->s_lamx; A.dbg_c = h->s_g;        // (batch staging buffers: nb rows each)
     A.dbg_mu = mu; A.dbg_delta = 0.0;
     A.batch = nb; A.mode = 1; A.dbg_at_solution = 1;
-    if (launch(h, A, nb, fit_block(h, 256), h->stream_ptr())) return 1;
+    if (launch(h, A, nb, fit_block(h->el_size, 256), h->stream_ptr())) return 1;
     rc |= h->d2h(dx + (size_t)b0 * d.n_opt_x, h->s_x, sizeof(double) * (size_t)nb * d.n_opt_x);
     rc |= h->d2h(dlam + (size_t)b0 * d.n_g, h->s_lamg, sizeof(double) * (size_t)nb * d.n_g);
     if (rc || h->sync()) return 1;
@@ -962,17 +922,15 @@ extern "C" int dompc_sens_batch_device(dompc_handle* h, int32_t B, const double*
     A.p = A.sn_prow;
     A.sn_S = S + q0 * n_sel * n_cols; A.sn_res = residual_step + q0; A.sn_ok = ok + q0;
     A.batch = nq * n_rows; A.mode = 3; A.wide = 1; A.wide_spread = 0;
-    const int block = fit_block(h, h->block_auto ? (A.batch >= BATCH_ONE_WAVE ? 64 : 256) : h->block);
-    const int cap = (h->block_auto && block != 64 && h->slots256 < h->n_slots) ? h->slots256 : h->n_slots;
-    const int grid = A.batch < cap ? A.batch : cap;
+    const dompc_shape s = dompc_launch::batch_shape(shape_facts(h), A.batch);
 #ifndef DOMPC_HOST_EMU
     hipStream_t st = (hipStream_t)stream;
     auto blocks_for = [](int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g)); };
     if (h->launch(h->fn_sens_prep, blocks_for((int64_t)A.batch * d.n_opt_p), 256, 0, st, &A, sizeof(A))) return 1;
-    if (launch(h, A, grid, block, stream, (void*)((block == 64 && h->fn_sens_batch) ? h->fn_sens_batch : h->fn_sens))) return 1;
+    if (launch(h, A, s.grid, s.block, stream, (void*)((s.block == 64 && h->fn_sens_batch) ? h->fn_sens_batch : h->fn_sens))) return 1;
     if (h->launch(h->fn_sens_finish, blocks_for((int64_t)nq * n_sel * n_cols), 256, 0, st, &A, sizeof(A))) return 1;
 #else
-    if (launch(h, A, grid, block, stream)) return 1;
+    if (launch(h, A, s.grid, s.block, stream)) return 1;
 #endif
   }
   return 0;

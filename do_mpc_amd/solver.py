@@ -119,6 +119,8 @@ def _load(lib_path: str) -> C.CDLL:
     lib.dompc_sens_batch.restype = C.c_int
     lib.dompc_debug_get_trace.argtypes = [vp, vp, C.c_int32]
     lib.dompc_debug_get_trace.restype = C.c_int
+    lib.dompc_launch_shape.argtypes = [vp, vp, C.c_int32, vp]      # (dompc_shape_facts*, dompc_shape_overrides*, B, dompc_shape*)
+    lib.dompc_launch_shape.restype = C.c_int
     lib.dompc_abort.argtypes = [vp, C.c_int32]
     lib.dompc_abort.restype = C.c_int
     lib.dompc_workspace_bytes.argtypes = [vp]

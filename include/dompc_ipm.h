@@ -194,6 +194,30 @@ int dompc_newton_steps_at_solution(dompc_handle* h, int32_t B,
  * +-alpha (negative: line search failed), delta_w, obj). */
 int dompc_debug_get_trace(dompc_handle* h, double* out, int32_t max_rows);
 
+/* The launch shape of a solve as a function of plain values: the decision dompc_solve_batch_device makes for a batch of B problems
+ * (do_mpc_amd/csrc/dompc_shape.h), without a handle and without a device - what tests/test_launch_shape.py pins.
+ * facts: what a handle knows after dompc_create; overrides: what DOMPC_WIDE / DOMPC_WIDE_SPREAD / DOMPC_WIDE_BLOCK ask for.
+ * Returns 1 on a null pointer or B < 1. */
+typedef struct dompc_shape_facts {
+  int32_t n_edges, n_leaves;     /* edges of the scenario tree, nodes of its last stage                                  */
+  int32_t edges_per_wave;        /* dompc_edges_per_wavefront                                                            */
+  int64_t el_size;               /* doubles of LDS per wavefront (one edge working set)                                  */
+  int32_t slots64, slots256;     /* resident workgroups of the solver kernel at 64 / at (up to) 256 threads              */
+  int32_t n_slots;               /* workspace slots of the handle                                                        */
+  int32_t block, block_auto;     /* threads per problem of a batch; 1 = chosen per call from the batch size instead      */
+  int32_t sharded;               /* 1 = tree sharding is on (dompc_set_sharding)                                         */
+} dompc_shape_facts;
+typedef struct dompc_shape_overrides {
+  int32_t wide;                  /* workgroups per problem, -1 = not set                                                 */
+  int32_t wide_spread;           /* 0 / 1, -1 = not set                                                                  */
+  int32_t wide_block;            /* threads per workgroup of the wide mode (64/128/256/512), 0 = not set                 */
+} dompc_shape_overrides;
+typedef struct dompc_shape {
+  int32_t block, grid;           /* threads per workgroup, workgroups                                                    */
+  int32_t wide, wide_spread;     /* workgroups per problem (1 = one each) and whether they are spread over the XCDs      */
+} dompc_shape;
+int dompc_launch_shape(const dompc_shape_facts* facts, const dompc_shape_overrides* overrides, int32_t B, dompc_shape* out);
+
 /* Stop request: running and queued solves of this handle leave their IPM loop at the next iteration and report
  * status 6 (User_Requested_Stop, success = 0); may be called from another thread while a solve is in flight.
  * stop = 0 re-arms the handle.  The blocking entry points (dompc_solve, dompc_solve_batch, the service loop of a
