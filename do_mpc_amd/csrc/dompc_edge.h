@@ -311,6 +311,21 @@ constexpr int FW4_NEED = (NA <= 16 && NV <= 16) ? 4 * FW4_CH : 0;
 constexpr int FW4_NEED = 0;
 #endif
 constexpr int EL_SIZE = ((el_max(el_max(el_max(el_max(el_max(EL_MOC + MOC_STAGE, RB_NEED), el_max(RF_IMG + MO_IMG, R16_NEED)), DAE_NEED), QL_NEED), FW4_NEED) + 7) / 8) * 8;
+// Forward pass with four edges per wavefront: the per-edge operands of the wavefront's NEXT quad are copied in by LDS-DMA while the
+// current quad is computed (phase_forward_quads, dompc_quad.h), into the part of the region that the forward pass leaves unused behind
+// QF_NEED (the sweep's layout decides EL_SIZE; the staging area never makes it grow - a model whose region has no room keeps the loop
+// with the loads at the top of the quad).  An LDS-DMA instruction writes base + lane x size, so every piece is padded to whole
+// instructions; the lanes of the padding copy the last word of their piece again:
+//   QF_SG_EW + 64 g   Sigma_w | r_w of edge g: 2 NW doubles in 16-byte pieces, two edges per instruction (32 lanes each)
+//   QF_SG_C  + 32 g   residuals of its collocation and continuity rows: NW doubles in 4-byte pieces, one instruction
+//   QF_SG_V  + 32 g   dx_n (NX) | d nu (NX) | du (NU) in 4-byte pieces, one instruction
+// -DDOMPC_FWD_STAGE=0: the comparison build (tests/test_gpu_forward_stage.py) - the loop with the loads at the top of the quad.
+#ifndef DOMPC_FWD_STAGE
+#define DOMPC_FWD_STAGE 1
+#endif
+constexpr int QF_SG = QF_NEED;
+constexpr int QF_SG_EW = 0, QF_SG_C = QF_SG_EW + 4 * 64, QF_SG_V = QF_SG_C + 4 * 32, QF_SG_SIZE = QF_SG_V + 4 * 32;
+constexpr bool QF_STAGE = QUAD_FWD && (DOMPC_FWD_STAGE != 0) && NW <= 32 && 2 * NX + NU <= 32 && QF_SG % 2 == 0 && QF_SG + QF_SG_SIZE <= EL_SIZE;
 
 // ---- dense image of a compact model-output record
 // dense index (MO_PT / MO_LT / MO_MT / MO_NL layout) of compact entry k

@@ -820,6 +820,56 @@ __device__ inline QfPack qf_pack(const KArgs& A, int e) {
   return k;
 }
 
+// ---- the staged variant of the forward quad loop (QF_STAGE, dompc_edge.h; Sigma_w | r_w of a forward record has to take 16-byte pieces)
+constexpr bool QF_STAGED = QF_STAGE && EW_SIGW % 2 == 0;
+// The index records of the edges e0 .. e0 + 3, one entry per lane: lane 16 g + f asks for field f of edge e0 + g (rows beyond the last
+// edge: of the last edge, as they take its record everywhere else).
+static_assert(EP_N == 16, "one index record per row of 16 lanes");
+__device__ inline int qf_index_request(const KArgs& A, int e0, int lane) {
+  const int e = min(e0 + (lane >> 4), A.n_edges - 1);
+  return A.edge_pack[(int64_t)e * EP_N + (lane & 15)];
+}
+// field F of the record of this lane's row (v_mov_b32_dpp row_newbcast; executed by every lane)
+template <int F>
+__device__ inline int qf_row_field(int ipk) { return __builtin_amdgcn_update_dpp(0, ipk, 0x150 + F, 0xf, 0xf, true); }
+__device__ inline void qf_glds4(const double* src, int word, ldsd* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((const unsigned*)src + word),
+                                   (__attribute__((address_space(3))) void*)dst, 4, 0, 0);
+}
+// Request the per-edge operands of the edges e0 .. e0 + 3 into the staging area of the wavefront's LDS region (layout: dompc_edge.h);
+// `ipk`: their index records (qf_index_request), landed.  Ten LDS-DMA instructions; every source address lies inside the run it copies
+// (the lanes of the padding repeat the last word / piece of the run), so no address outside the arrays is formed.
+__device__ inline void stage_quad_operands(const Prob& Q, int e0, int ipk, int lane, ldsd* Ld) {
+  const KArgs& A = *Q.A;
+  ldsd* dst = Ld + QF_SG;
+  // Sigma_w | r_w: contiguous in the forward record and 16-byte aligned in memory (records start on 64-byte boundaries)
+  static_assert(EW_RW == EW_SIGW + NW, "Sigma_w | r_w is one run of 2 NW doubles");
+  static_assert(!QF_STAGED || (EW_SIGW % 2 == 0 && EW_SIZE % 8 == 0 && QF_SG % 2 == 0), "16-byte pieces of Sigma_w | r_w, in memory and in LDS");
+#pragma unroll
+  for (int p = 0; p < 2; ++p) {
+    const int e = min(e0 + 2 * p + (lane >> 5), A.n_edges - 1);
+    const double* src = Q.ew + (int64_t)e * EW_SIZE + EW_SIGW + 2 * min(lane & 31, NW - 1);
+    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                     (__attribute__((address_space(3))) void*)(dst + QF_SG_EW + 128 * p), 16, 0, 0);
+  }
+  // the runs that are only 8-byte aligned, in 4-byte pieces: lane 2 k takes the low word and lane 2 k + 1 the high word of double k
+  const int k = min(lane >> 1, 2 * NX + NU - 1), h = lane & 1;
+  sfor<4>([&](auto G_) {
+    constexpr int gg = G_;
+    const int row0 = __builtin_amdgcn_readlane(ipk, 16 * gg + EP_ROW0), n = __builtin_amdgcn_readlane(ipk, 16 * gg + EP_PARENT);
+    qf_glds4(Q.c + row0, min(lane, 2 * NW - 1), dst + QF_SG_C + 32 * gg);
+    const double* xs = Q.nd + (int64_t)n * ND_SIZE + ND_DXT + k;
+    const double* ns = Q.dlam + row0 + NW + (k - NX);
+    const double* vs = k < NX ? xs : ns;
+    if constexpr (NU > 0) {
+      const int uoffp = __builtin_amdgcn_readlane(ipk, 16 * gg + EP_UOFF_PARENT);
+      const double* us = Q.dx + uoffp + (k - 2 * NX);
+      vs = k < 2 * NX ? vs : us;
+    }
+    qf_glds4(vs, h, dst + QF_SG_V + 32 * gg);
+  });
+}
+
 __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, int b_, int slot, int soc, double sf, double delta_, int cl_) {
   const KArgs A = kernel_args(kp);
   Thr T = make_thr(A);
@@ -842,6 +892,13 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     const int lane0 = (int)(threadIdx.x & 63u);
     stage_quad(Q, 4 * qd, lane0, Ld, 0);
   }
+  // QF_STAGED: index records (one entry per lane) of this quad's edges and of the next quad's
+  int ipk = 0, ipkn = 0;
+  if constexpr (QF_STAGED) {
+    const int lane0 = (int)(threadIdx.x & 63u);
+    ipk = qf_index_request(A, 4 * qd, lane0);
+    stage_quad_operands(Q, 4 * qd, ipk, lane0, Ld);
+  }
 #if DOMPC_QUAD_PROFILE
   long long pc0 = prof_clock();
 #define QF_PH(i) if (T.prof && T.tid == 0) { const long long pc1 = prof_clock(); T.prof[i] += pc1 - pc0; pc0 = pc1; }
@@ -857,22 +914,34 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     const int e = act ? e0 + g : A.n_edges - 1;
     const bool isx = j < NX, st_x = act && isx;
     const int b = isx ? j : 0;
-    const QfPack pk = qf_pack(A, e);
+    QfPack pk;
+    if constexpr (QF_STAGED) {
+      // (requested a quad ahead: no load, and nothing but the branching levels below in front of the wait)
+      pk.woff = qf_row_field<EP_WOFF>(ipk); pk.row0 = qf_row_field<EP_ROW0>(ipk); pk.level = qf_row_field<EP_LEVEL>(ipk);
+      pk.n = 0; pk.cn = qf_row_field<EP_CHILD>(ipk); pk.uoffp = 0; pk.epsoff = qf_row_field<EP_EPSOFF_PARENT>(ipk);
+    } else {
+      pk = qf_pack(A, e);
+    }
     const bool chain = pk.level >= cl;
     // ---- operands: steps of the parent node's variables, the residuals of the edge's rows, r_w and Sigma_w of its unknowns, d nu of its
     //      end-point rows (chain levels: from the chain walk; branching levels: P dx + p of the child node, stored here)
-    const double dxn = Q.nd[(int64_t)pk.n * ND_SIZE + ND_DXT + b];
+    double dxn, ccont, dnu;
     double du[NU > 0 ? NU : 1];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) du[u] = Q.dx[pk.uoffp + u];
     double cres[DEG], rwv[M], sgv[M];
-#pragma unroll
-    for (int jj = 0; jj < DEG; ++jj) cres[jj] = Q.c[pk.row0 + jj * NX + b];
-    const double ccont = Q.c[pk.row0 + R + b];
     const double* ew = Q.ew + (int64_t)e * EW_SIZE;
+    if constexpr (!QF_STAGED) {
+      dxn = Q.nd[(int64_t)pk.n * ND_SIZE + ND_DXT + b];
 #pragma unroll
-    for (int s = 0; s < M; ++s) { rwv[s] = ew[EW_RW + s * NX + b]; sgv[s] = ew[EW_SIGW + s * NX + b]; }
-    double dnu = Q.dlam[pk.row0 + NW + b];
+      for (int u = 0; u < NU; ++u) du[u] = Q.dx[pk.uoffp + u];
+#pragma unroll
+      for (int jj = 0; jj < DEG; ++jj) cres[jj] = Q.c[pk.row0 + jj * NX + b];
+      ccont = Q.c[pk.row0 + R + b];
+#pragma unroll
+      for (int s = 0; s < M; ++s) { rwv[s] = ew[EW_RW + s * NX + b]; sgv[s] = ew[EW_SIGW + s * NX + b]; }
+      dnu = Q.dlam[pk.row0 + NW + b];
+    } else {
+      dnu = 0.0;
+    }
     if (__ballot(!chain) != 0ull) {
       const double* Nc = Q.nd + (int64_t)pk.cn * ND_SIZE;
       double t = Nc[ND_PV + b];
@@ -880,10 +949,27 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
       for (int bb = 0; bb < NA; ++bb) t = fma(Nc[ND_P + b * NA + bb], Nc[ND_DXT + bb], t);
       dnu = chain ? dnu : t;
     }
+    if constexpr (!QF_STAGED) { QF_PH(17) }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // the staged records (and everything above) have landed
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
     QF_PH(15)
+    if constexpr (QF_STAGED) {
+      // the index records of the next quad: retired long before their use behind the elimination
+      if (qd + ng < nq) ipkn = qf_index_request(A, 4 * (qd + ng), lane);
+      // this quad's operands, requested while the previous quad was computed (prologue: the first one's) and landed behind the wait above
+      const ldsd* So = Ld + QF_SG;
+      dxn = So[QF_SG_V + 32 * g + b];
+      const double dnus = So[QF_SG_V + 32 * g + NX + b];
+      dnu = chain ? dnus : dnu;
+#pragma unroll
+      for (int u = 0; u < NU; ++u) du[u] = So[QF_SG_V + 32 * g + 2 * NX + u];
+#pragma unroll
+      for (int jj = 0; jj < DEG; ++jj) cres[jj] = So[QF_SG_C + 32 * g + jj * NX + b];
+      ccont = So[QF_SG_C + 32 * g + R + b];
+#pragma unroll
+      for (int s = 0; s < M; ++s) { rwv[s] = So[QF_SG_EW + 64 * g + NW + s * NX + b]; sgv[s] = So[QF_SG_EW + 64 * g + s * NX + b]; }
+    }
     const ldsd* rec = Ld + bank * QL_MOSZ + (e - e0) * MO_REC;      // (a row beyond the last edge: the last edge's record, as in eval_edge_quad - the same verdict as the sweep's)
     ldsd* Lv = Ld + QL_WB + g * QF_VG;                        // dw | dy | rhs | rr of this lane's edge
     constexpr int V_DW = 0, V_DY = NW, V_RHS = NW + NA, V_RR = 2 * NW + NA;
@@ -917,6 +1003,18 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     // the compact records of the quad this wavefront handles next
     const int qn = qd + ng;
     if (qn < nq) stage_quad(Q, 4 * qn, lane, Ld, bank ^ 1);
+    if constexpr (QF_STAGED) {
+      // ... and its per-edge operands.  No quad reads what another quad of this phase stores (a quad stores dx[woff ..], dlam[row0 ..
+      // row0 + NW), on branching edges dlam[row0 + NW ..] of its OWN edges, and the nl_cons rows; it reads dx_n / du of the parent node,
+      // c, Sigma_w | r_w and, on chain edges, dlam[row0 + NW ..] - all written before this phase by the chain walk, the branching
+      // levels and the sweep), so the operands of the next quad may be read from memory while this one computes.  One staging area:
+      // this quad took its operands into registers at the top, and the wait below retires those LDS reads before a DMA overwrites them.
+      if (qn < nq) {
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        stage_quad_operands(Q, 4 * qn, ipkn, lane, Ld);
+      }
+      QF_PH(17)
+    }
     // ---- dw: collocation slots from lane NA's column -G_cc^-1 g, end-point slot from the continuity rows
     double dwv[M];
     if (!fb) {
@@ -1042,6 +1140,7 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
     QF_PH(20)
     bank ^= 1;
     qd = qn;
+    ipk = ipkn;
   }
 #undef QF_PH
 }

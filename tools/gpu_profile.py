@@ -64,10 +64,15 @@ def main():
         # is shared with it; row 0 is the model evaluation of the wavefront-per-edge fallback.
         names.update({0: "edge:model-eval (fallback path)", 4: "quad:operand loads + wait", 5: "quad:residuals, barrier terms, columns",
                       6: "quad:dual pieces", 2: "quad:gauss-jordan", 7: "quad:fwd record, W, [A B] stores", 1: "quad:condensing",
-                      3: "quad:record stores", 15: "fwdq:operand request + wait", 28: "fwdq:dy, g, column build", 29: "fwdq:elimination",
-                      30: "fwdq:dw", 31: "fwdq:rhs", 20: "fwdq:dlam + stores (+ two-edge path)",
-                      17: "fwd2:edge loads issued", 18: "fwd2:edge wait + dw", 19: "fwd2:edge rhs"})
-        order = (0, 4, 5, 6, 2, 7, 1, 3, 12, 13, 14, 8, 9, 10, 11, 24, 25, 26, 27, 16, 15, 28, 29, 30, 31, 20, 17, 18, 19, 21, 22, 23)
+                      3: "quad:record stores", 28: "fwdq:dy, g, column build", 29: "fwdq:elimination",
+                      30: "fwdq:dw", 31: "fwdq:rhs", 20: "fwdq:dlam + stores (+ two-edge path)", 18: "fwd2:edge wait + dw",
+                      19: "fwd2:edge rhs"})
+        # The operands of the forward quad loop.  The default build requests them one quad ahead (behind the elimination);
+        # -DDOMPC_FWD_STAGE=0 (and every model whose LDS region has no room for the staging area) issues the loads at the top of the
+        # quad and waits there.  Row 17 is shared with the two-edge forward pass, which a four-edge build takes in the adjoint
+        # variant only (last barrier levels).
+        names.update({17: "fwdq:operand request issued (+ fwd2:loads issued)", 15: "fwdq:operand wait"})
+        order = (0, 4, 5, 6, 2, 7, 1, 3, 12, 13, 14, 8, 9, 10, 11, 24, 25, 26, 27, 16, 17, 15, 18, 28, 29, 30, 31, 20, 19, 21, 22, 23)
     for i in order:
         print(f"    {names[i]:38s} {sub[i] / 1e6:9.2f} Mcycles")
 
