@@ -40,11 +40,12 @@ def _run(cmd, what):
 
 
 @contextlib.contextmanager
-def _locked(directory: str):
+def _locked(directory: str, name: str = ".lock"):
     """Exclusive lock on a build directory: several rank processes lower the same MPC at the same time
-    (MPC.shard_tree, torchrun) and must not compile into the same paths concurrently."""
+    (MPC.shard_tree, torchrun) and must not compile into the same paths concurrently.  `name`: a lock of one output file of the
+    directory instead - the code objects of one model (its variants and sets of switches) are compiled side by side."""
     os.makedirs(directory, exist_ok=True)
-    fd = os.open(os.path.join(directory, ".lock"), os.O_CREAT | os.O_RDWR, 0o644)
+    fd = os.open(os.path.join(directory, name), os.O_CREAT | os.O_RDWR, 0o644)
     try:
         fcntl.flock(fd, fcntl.LOCK_EX)
         yield
@@ -118,13 +119,16 @@ def model_dir(model_hash: str) -> str:
     return d
 
 
-def model_code_object(header_text: str, model_hash: str, force: bool = False, opt: str = "-O3", shard: bool = False, batch_only: bool = False) -> str:
+def model_code_object(header_text: str, model_hash: str, force: bool = False, opt: str = "-O3", shard: bool = False, batch_only: bool = False,
+                      defs: Optional[str] = None) -> str:
     """Per-model gfx950 code object (hsaco) from the generated header + the kernel sources.
     shard=True: the variant with tree-sharding support (ownership masks, cross-rank exchanges).
     batch_only=True: the sibling `..._batch.hsaco` compiled with -DDOMPC_NO_WIDE=1 -DDOMPC_BLOCK_CONST=64 - "one workgroup of ONE wavefront
     per problem" (the launch shape of batches >= 4096) is a compile-time fact there: no device-scope barrier / atomic flag code in the phases
     (+1.6 % on the headline batch in a same-box A/B), thread counts and strides constants, workgroup barriers folded (+1.0 % more); the
-    runtime loads it next to the general object when it exists and launches it whenever the workgroups have 64 threads."""
+    runtime loads it next to the general object when it exists and launches it whenever the workgroups have 64 threads.
+    defs: the extra switches of the build, in place of the environment's DOMPC_DEFS (build() compiles the objects of several sets of
+    switches side by side: the environment is one per process)."""
     forced = os.environ.get("DOMPC_CODE_OBJECT")     # measurement aid: use this code object as it is (A/B against an older kernel)
     if forced and not shard:
         return forced
@@ -135,7 +139,7 @@ def model_code_object(header_text: str, model_hash: str, force: bool = False, op
     stamp = out + ".stamp"
     lb = os.environ.get("DOMPC_LB", "2")          # tuning aid: wavefronts per SIMD the kernel is compiled for
     prof = os.environ.get("DOMPC_PROFILE", "0")    # measurement aid: sub-phase cycle counters compiled in (tools/gpu_profile.py)
-    defs = os.environ.get("DOMPC_DEFS", "").split()  # measurement aid: extra -D switches / compiler flags (entries starting with '-') for A/B builds (own file per set)
+    defs = (os.environ.get("DOMPC_DEFS", "") if defs is None else defs).split()  # measurement aid: extra -D switches / compiler flags (entries starting with '-') for A/B builds (own file per set)
     if defs or prof != "0" or lb != "2":          # (measurement builds live next to the product build, under their own names)
         tag = ("prof" if prof != "0" else "") + (("lb" + lb) if lb != "2" else "") + (hashlib.sha256(" ".join(defs).encode()).hexdigest()[:8] if defs else "")
         out = out[:-len(".hsaco")] + "_" + tag + ".hsaco"
@@ -156,7 +160,7 @@ def model_code_object(header_text: str, model_hash: str, force: bool = False, op
     dig = _sources_digest() + hashlib.sha256(header_text.encode()).hexdigest()[:12] + opt + ("S" if shard else "") + "lb" + lb + "p" + prof + " ".join(defs) + " ".join(sched)
     if not force and _fresh(out, stamp, dig):
         return out
-    with _locked(d):
+    with _locked(d, os.path.basename(out) + ".lock"):
         if not force and _fresh(out, stamp, dig):       # another rank built it while we waited for the lock
             return out
         if not (os.path.exists(hdr) and open(hdr).read() == header_text):

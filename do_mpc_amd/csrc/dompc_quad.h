@@ -46,15 +46,35 @@ constexpr MoRef moref_dyn(int p, int d) { return moref_in(d, DOMPC_DYN_VIDX, DOM
 constexpr MoRef moref_lt(int d) { return moref_in(d, DOMPC_LT_VIDX, DOMPC_LT_NV, DOMPC_LT_CIDX, DOMPC_LT_NC, MOC_LT); }
 constexpr MoRef moref_nl(int d) { return moref_in(d, DOMPC_NL_VIDX, DOMPC_NL_NV, DOMPC_NL_CIDX, DOMPC_NL_NC, MOC_NL); }
 constexpr MoRef moref_mt(int d) { return moref_in(d, DOMPC_MT_VIDX, DOMPC_MT_NV, DOMPC_MT_CIDX, DOMPC_MT_NC, MOC_MT); }
-// its value: `rec` = the compact record of this lane's edge in LDS (a constant index into a table with a constant initialiser folds to the literal)
-template <int KIND, int OFF>
-__device__ inline double mo_dyn_val(const ldsd* rec) { if constexpr (KIND == 2) return rec[OFF]; else if constexpr (KIND == 1) return DOMPC_DYN_CVAL[OFF]; else return 0.0; }
-template <int KIND, int OFF>
-__device__ inline double mo_lt_val(const ldsd* rec) { if constexpr (KIND == 2) return rec[OFF]; else if constexpr (KIND == 1) return DOMPC_LT_CVAL[OFF]; else return 0.0; }
-template <int KIND, int OFF>
-__device__ inline double mo_nl_val(const ldsd* rec) { if constexpr (KIND == 2) return rec[OFF]; else if constexpr (KIND == 1) return DOMPC_NL_CVAL[OFF]; else return 0.0; }
-template <int KIND, int OFF>
-__device__ inline double mo_mt_val(const ldsd* rec) { if constexpr (KIND == 2) return rec[OFF]; else if constexpr (KIND == 1) return DOMPC_MT_CVAL[OFF]; else return 0.0; }
+// its value: `rec` = the compact record of this lane's edge in LDS (a constant index into a table with a constant initialiser folds to the literal).
+// A variable entry is read through a volatile pointer (MoRec::at): most of these reads feed a select `(j == bb) ? t_ : v`, and the compiler
+// sinks a plain read into an exec-mask branch of its own for the lanes that keep it - one branch, one single ds_read_b64 and one
+// s_waitcnt lgkmcnt(0) per entry, 80 dependent LDS round trips per quad in each of the two quad loops.  A volatile read stays where
+// the source has it: executed by all lanes (an LDS broadcast, the address is uniform per row of 16 lanes), issued back to back with
+// its neighbours, waited for with a count.  Same values from the same addresses, the selects of the source: the same bits.
+// -DDOMPC_MO_BRANCHED=1: the comparison build - plain reads, the former instruction stream (tests/test_gpu_mo_reads.py); = 2 / = 3: plain
+// reads in the sweep's quad loop only / in the forward pass's only (the two loops measured apart).
+#ifndef DOMPC_MO_BRANCHED
+#define DOMPC_MO_BRANCHED 0
+#endif
+#define MO_BR_SWEEP (DOMPC_MO_BRANCHED == 1 || DOMPC_MO_BRANCHED == 2)
+#define MO_BR_FWD (DOMPC_MO_BRANCHED == 1 || DOMPC_MO_BRANCHED == 3)
+template <bool BRANCHED>
+struct MoRec {
+  const ldsd* p;
+  __device__ inline double at(int off) const {
+    if constexpr (BRANCHED) return p[off];
+    else return ((const volatile ldsd*)p)[off];
+  }
+};
+template <int KIND, int OFF, class REC>
+__device__ inline double mo_dyn_val(REC rec) { if constexpr (KIND == 2) return rec.at(OFF); else if constexpr (KIND == 1) return DOMPC_DYN_CVAL[OFF]; else return 0.0; }
+template <int KIND, int OFF, class REC>
+__device__ inline double mo_lt_val(REC rec) { if constexpr (KIND == 2) return rec.at(OFF); else if constexpr (KIND == 1) return DOMPC_LT_CVAL[OFF]; else return 0.0; }
+template <int KIND, int OFF, class REC>
+__device__ inline double mo_nl_val(REC rec) { if constexpr (KIND == 2) return rec.at(OFF); else if constexpr (KIND == 1) return DOMPC_NL_CVAL[OFF]; else return 0.0; }
+template <int KIND, int OFF, class REC>
+__device__ inline double mo_mt_val(REC rec) { if constexpr (KIND == 2) return rec.at(OFF); else if constexpr (KIND == 1) return DOMPC_MT_CVAL[OFF]; else return 0.0; }
 // the function values f of a point are the first NX entries of its compact record (lowering.py writes the variable entries in the order
 // of the dense layout, and f comes first): lane b reads f_b at a lane-dependent address
 constexpr bool qd_f_linear() {
@@ -161,14 +181,14 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
   QD_SB();
   // compact record of this lane's edge.  A row beyond the last edge repeats that edge with ITS record, row e - e0 of the bank: row g holds
   // what stage_quad() copied from behind the last record, and the lanes of the row vote in the pivot test below
-  const ldsd* rec = Ld + bank * QL_MOSZ + (e - e0) * MO_REC;
+  const MoRec<MO_BR_SWEEP> rec{Ld + bank * QL_MOSZ + (e - e0) * MO_REC};
   // ---- 2. residual rows of state b: collocation rows (one per point), continuity row, end-point row (optimizer.py:951-983, _mpc.py:1224)
   double res[DEG], rc, ce;
   {
     double fv[DEG];
     if constexpr (qd_f_linear()) {
 #pragma unroll
-      for (int jj = 0; jj < DEG; ++jj) fv[jj] = rec[jj * DOMPC_DYN_NV + (int)b];
+      for (int jj = 0; jj < DEG; ++jj) fv[jj] = rec.p[jj * DOMPC_DYN_NV + (int)b];
     } else {
       sfor<DEG>([&](auto JJ) {
         constexpr int jj = JJ;
@@ -571,15 +591,27 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
         rnl = fma(jds, ydv[i], rnl);
         if (act && j < NA) Q.ew[(int64_t)e * EW_SIZE + EW_JD + i * NA + j] = jds;
       });
+#if !MO_BR_SWEEP
+      double dnl[NE1];                                 // (row i of d(x_n, u_n): its entry of the record, read by every lane in front of the lane branch)
+      sfor<NE>([&](auto I_) {
+        constexpr int i2 = I_;
+        constexpr MoRef rf = moref_nl(i2);
+        dnl[i2] = mo_nl_val<rf.kind, rf.off>(rec);
+      });
+#endif
       if (act && j == 0) {
 #pragma unroll
         for (int i = 0; i < NE; ++i) {
+#if MO_BR_SWEEP
           double d = 0.0;
           sfor<NE>([&](auto I_) {                      // (row i of d(x_n, u_n): its entry of the record)
             constexpr int i2 = I_;
             constexpr MoRef rf = moref_nl(i2);
             if constexpr (rf.kind != 0) { const double t_ = mo_nl_val<rf.kind, rf.off>(rec); d = (i == i2) ? t_ : d; }
           });
+#else
+          double d = dnl[i];
+#endif
           const int sq = nl_slack(i);
           if (NSE > 0 && sq >= 0) {
 #pragma unroll
@@ -602,7 +634,13 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
       S_[ES_QVB + j] = Lq[16 + j];
     }
     const bool last = pk.level == A.N - 1;
+#if !MO_BR_SWEEP
+    double mt0 = 0.0;
+#endif
     if (__ballot(last) != 0ull) {
+#if !MO_BR_SWEEP
+      mt0 = mo_mt_val<moref_mt(0).kind, moref_mt(0).off>(rec);
+#endif
       double mg = 0.0;
       sfor<NX>([&](auto A_) {
         constexpr int a = A_;
@@ -621,10 +659,18 @@ __device__ inline int eval_edge_quad(const Thr& T, const Prob& Q, int e0, int e0
         if (st_x && last) S_[ES_MH + a * NX + (int)b] = omh * v;
       });
     }
+    constexpr MoRef r0 = moref_lt(0), m0 = moref_mt(0);
+#if !MO_BR_SWEEP
+    const double lt0 = mo_lt_val<r0.kind, r0.off>(rec);          // (read by every lane: in front of the lane branch that uses it)
+#endif
     if (act && j == 0) {
-      constexpr MoRef r0 = moref_lt(0), m0 = moref_mt(0);
+#if MO_BR_SWEEP
       double obj = pk.om * mo_lt_val<r0.kind, r0.off>(rec);
       if (last) obj += pk.om * mo_mt_val<m0.kind, m0.off>(rec);
+#else
+      double obj = pk.om * lt0;
+      if (last) obj += pk.om * mt0;
+#endif
       if constexpr (NE > 0) {
 #pragma unroll
         for (int q = 0; q < NSE; ++q) obj += Q.sf * DOMPC_EPS_PEN[q] * epv[q];
@@ -734,7 +780,7 @@ __device__ inline int sweep_quads(const Thr&, const Prob&, double) { return 0; }
 #if !defined(DOMPC_HOST_EMU) && DOMPC_DEG >= 1 && DOMPC_M >= 1 && DOMPC_NI == 1 && DOMPC_NX + DOMPC_NU + 2 <= 16 && DOMPC_DEG * DOMPC_DEG * DOMPC_NX <= 64
 static_assert(!QUAD_FWD || (2 * NW + NA + DEG * NX <= QF_VG && QL_WB + 4 * QF_VG <= EL_SIZE), "LDS of the four-edge forward pass");
 
-__device__ inline void qd_fw_columns(const ldsd* rec, int j, const double (&res)[DEG], double (&bc)[DEG][DEG * NX]) {
+__device__ inline void qd_fw_columns(MoRec<MO_BR_FWD> rec, int j, const double (&res)[DEG], double (&bc)[DEG][DEG * NX]) {
   constexpr int R = DEG * NX;
   sfor<DEG>([&](auto S_) {
     constexpr int s = S_;
@@ -970,12 +1016,21 @@ __device__ __attribute__((noinline)) void phase_forward_quads(const void* kp, in
 #pragma unroll
       for (int s = 0; s < M; ++s) { rwv[s] = So[QF_SG_EW + 64 * g + NW + s * NX + b]; sgv[s] = So[QF_SG_EW + 64 * g + s * NX + b]; }
     }
-    const ldsd* rec = Ld + bank * QL_MOSZ + (e - e0) * MO_REC;      // (a row beyond the last edge: the last edge's record, as in eval_edge_quad - the same verdict as the sweep's)
+    const MoRec<MO_BR_FWD> rec{Ld + bank * QL_MOSZ + (e - e0) * MO_REC};      // (a row beyond the last edge: the last edge's record, as in eval_edge_quad - the same verdict as the sweep's)
     ldsd* Lv = Ld + QL_WB + g * QF_VG;                        // dw | dy | rhs | rr of this lane's edge
     constexpr int V_DW = 0, V_DY = NW, V_RHS = NW + NA, V_RR = 2 * NW + NA;
     // dy -> LDS (the u part by the lanes NX ..: they hold du[j - NX] like everybody)
+#if MO_BR_FWD
     if (isx) Lv[V_DY + j] = dxn;
     sfor<NU>([&](auto U_) { constexpr int u = U_; if (j == NX + u) Lv[V_DY + NX + u] = du[u]; });
+#else
+    {
+      // (entry j by lane j < NA, one write of a selected value: a write per input behind a lane test of its own was 1 + NU exec-mask branches)
+      double dyv = dxn;
+      sfor<NU>([&](auto U_) { constexpr int u = U_; dyv = (j == NX + u) ? du[u] : dyv; });
+      if (j < NA) Lv[V_DY + j] = dyv;
+    }
+#endif
     // ---- g = G_y dy + r on the collocation rows (jj, b): r - C[0][j] dx_n + J_u du (row b of the input Jacobian of point jj)
     double gv[DEG];
     sfor<DEG>([&](auto J_) {
