@@ -241,9 +241,7 @@ class ApproxMPC(torch.nn.Module):
         st.lbx, st.ubx = _flat(mpc._x_lb).reshape(-1, 1).copy(), _flat(mpc._x_ub).reshape(-1, 1).copy()
         st.lbu, st.ubu = _flat(mpc._u_lb).reshape(-1, 1).copy(), _flat(mpc._u_ub).reshape(-1, 1).copy()
         self.flags = {"setup": False}
-        self._emu = None                  # TEST-ONLY: (header, hash) -> host-emulation library
-        self._lib = None
-        self._h = None
+        self._native = _native.Native("ampc", _bind, build.ampc_code_object)
         self._uploaded = None             # what the handle's weights were packed from
         self._epoch = 0                   # bumped by load_from_state_dict / the trainer
 
@@ -255,6 +253,9 @@ class ApproxMPC(torch.nn.Module):
     def settings(self, val):
         warnings.warn("Cannot change the settings attribute")
 
+    _lib = property(lambda self: self._native.lib)     # the bound library and the native handle (None before first use / after close)
+    _h = property(lambda self: self._native.h)
+
     # ------------------------------------------------------------------ setup
     def setup(self, _lib_path=None, _code_object: Optional[str] = None) -> None:
         """Builds the network and the scaling from the bounds; the settings are final from here on.  With n_hidden_layers = 0 the
@@ -262,9 +263,7 @@ class ApproxMPC(torch.nn.Module):
         with `_code_object=""` selects the host emulation of the kernel."""
         assert self.flags["setup"] is False, "Setup can only be once."
         st, m = self.settings, self.mpc.model
-        if _lib_path is not None:
-            assert _code_object == "", "a library of its own is the host emulation: _code_object must be \"\""
-            self._emu = _lib_path if callable(_lib_path) else (lambda header, model_hash: _lib_path)
+        self._native = _native.Native("ampc", _bind, build.ampc_code_object, _lib_path, _code_object)
         self.rterm = bool(self.mpc.flags["set_rterm"])
         n_in = m.n_x + m.n_u if self.rterm else m.n_x
         self.net = FeedforwardNN(n_in=n_in, n_out=m.n_u, n_hidden_layers=st.n_hidden_layers, n_neurons=st.n_neurons, act_fn=st.act_fn,
@@ -337,17 +336,13 @@ class ApproxMPC(torch.nn.Module):
         assert self.flags["setup"] is True, "MPC was not setup yet. Please call ApproxMPC.setup()."
         st, m = self.settings, self.mpc.model
         if self._h is None:
-            if self._lib is None:
-                self._lib = _bind(self._emu(self.generated_header, self.model_hash) if self._emu else _native.runtime_library())
-            code_object = "" if self._emu else build.ampc_code_object(self.generated_header, self.model_hash)
+            code_object = self._native.load(self.generated_header, self.model_hash)
             act = lowering.AMPC_ACTIVATIONS
             desc = AMPCDesc(n_in=self.net.n_in, n_out=m.n_u, n_hidden_layers=st.n_hidden_layers, n_neurons=st.n_neurons,
                             act=act[st.act_fn], out_act=act[st.act_fn if st.n_hidden_layers == 0 else st.output_act_fn],
                             scaling=1 if st.scaling else 0, nx=m.n_x, code_object_path=code_object.encode(),
                             model_hash=self.model_hash.encode(), device=st.gpu_index)
-            h = C.c_void_p()
-            _native.check(self._lib.dompc_ampc_create(C.byref(desc), C.byref(h)), "dompc_ampc_create failed: ", self._lib.dompc_ampc_last_error)
-            self._h = h
+            self._native.create(desc)
         # (the box was fixed by setup(): settings cannot change afterwards; only the parameters are looked at per step)
         key = (self._epoch, sum(p._version for p in self._params), tuple(p.data_ptr() for p in self._params))
         if key != self._uploaded:
@@ -359,19 +354,11 @@ class ApproxMPC(torch.nn.Module):
         return self._h
 
     def _check(self, rc):
-        _native.check(rc, "dompc_ampc: ", self._lib.dompc_ampc_last_error, self._h)
+        self._native.check(rc)
 
     def close(self):
-        if getattr(self, "_h", None) is not None:
-            self._lib.dompc_ampc_destroy(self._h)
-            self._h = None
-            self._uploaded = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._native.close()
+        self._uploaded = None
 
     def _host_inputs(self, X, U_prev, who):
         """(X [B][nx], U_prev [B][nu] or None) as contiguous float64 arrays"""

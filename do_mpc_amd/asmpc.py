@@ -102,12 +102,7 @@ class ASMPC:
             DoMPCDifferentiator(mpc)                                       # refuses what make_step_batch(..., sensitivities=True) refuses
         self.generated_header = lowering.lower_asmpc(m.n_x, m.n_u)         # refuses n_x > 64 and n_u > 16, by name
         self.model_hash = self.generated_header.rsplit('ASMPC_MODEL_HASH "', 1)[1].split('"')[0]
-        self._emu = None
-        if _lib_path is not None:
-            assert _code_object == "", "a library of its own is the host emulation: _code_object must be \"\""
-            self._emu = _lib_path if callable(_lib_path) else (lambda header, model_hash: _lib_path)
-        self._lib = None
-        self._h = None
+        self._native = _native.Native("asmpc", _bind, build.asmpc_code_object, _lib_path, _code_object)
         self._options = None             # what the handle's bounds, scaling, clip and max_dx were set from
         self._nd = None                  # (solver, active_set_reduction, differentiator)
         self._resident = {}              # device -> the solver's bounds and the input scaling as tensors (solve_device)
@@ -119,19 +114,18 @@ class ASMPC:
         self._u_data = [np.asarray(mpc.u0.master, dtype=float).reshape(-1, 1).copy()]
 
     # ------------------------------------------------------------------ native side
+    _lib = property(lambda self: self._native.lib)     # the bound library and the native handle (None before first use / after close)
+    _h = property(lambda self: self._native.h)
+
     def _handle(self):
         """the runtime handle (created on first use) with the CURRENT options: bounds, scaling, clip and max_dx are uploaded again
         when one of them changed since the last call"""
         m, st = self.mpc.model, self.settings
         if self._h is None:
-            if self._lib is None:
-                self._lib = _bind(self._emu(self.generated_header, self.model_hash) if self._emu else _native.runtime_library())
-            code_object = "" if self._emu else build.asmpc_code_object(self.generated_header, self.model_hash)
+            code_object = self._native.load(self.generated_header, self.model_hash)
             desc = ASMPCDesc(nx=m.n_x, nu=m.n_u, code_object_path=code_object.encode(), model_hash=self.model_hash.encode(),
                              device=int(self.mpc.settings.gpu_index))
-            h = C.c_void_p()
-            _native.check(self._lib.dompc_asmpc_create(C.byref(desc), C.byref(h)), "dompc_asmpc_create failed: ", self._lib.dompc_asmpc_last_error)
-            self._h = h
+            self._native.create(desc)
         if int(st.resolve_every) < 1:
             raise ValueError("ASMPC.settings.resolve_every must be an integer >= 1")
         lb, ub, xs = (np.ascontiguousarray(v.master, dtype=np.float64).reshape(-1) for v in (self.mpc._u_lb, self.mpc._u_ub, self.mpc._x_scaling))
@@ -142,19 +136,11 @@ class ASMPC:
         return self._h
 
     def _check(self, rc):
-        _native.check(rc, "dompc_asmpc: ", self._lib.dompc_asmpc_last_error, self._h)
+        self._native.check(rc)
 
     def close(self):
-        if getattr(self, "_h", None) is not None:
-            self._lib.dompc_asmpc_destroy(self._h)
-            self._h = None
-            self._options = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._native.close()
+        self._options = None
 
     def _differentiator(self):
         red = bool(self.settings.active_set_reduction)

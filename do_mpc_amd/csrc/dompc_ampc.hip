@@ -271,11 +271,14 @@ extern "C" __global__ void dompc_ampc_info_kernel(int64_t* out, char* hash) {
   if (threadIdx.x == 0 && blockIdx.x == 0) AMPC_INFO(out, hash);
 }
 #else
-extern "C" void dompc_ampc_hostemu_info(int64_t* out, char* hash) { AMPC_INFO(out, hash); }
-extern "C" void dompc_ampc_hostemu_run(const dompc_ampck::Args* A) {
+// The host twins take what the runtime passes to dompc_host::Context::run: the kernel's argument block behind a const void*.
+extern "C" void dompc_ampc_hostemu_info(const void* args) { void* const* a = (void* const*)args; AMPC_INFO(((int64_t*)a[0]), ((char*)a[1])); }
+extern "C" void dompc_ampc_hostemu_run(const void* args) {
+  const dompc_ampck::Args* A = (const dompc_ampck::Args*)args;
   for (int64_t first = 0; first < A->batch; first += 32) dompc_ampck::step32(*A, first);
 }
-extern "C" void dompc_ampc_hostemu_jac(const dompc_ampck::JacArgs* J) {
+extern "C" void dompc_ampc_hostemu_jac(const void* args) {
+  const dompc_ampck::JacArgs* J = (const dompc_ampck::JacArgs*)args;
   for (int64_t first = 0; first < J->step.batch; first += 32) dompc_ampck::jac32(*J, first);
 }
 #endif

@@ -1,16 +1,15 @@
 // dompc_ampc_runtime.cpp - host side of the batched approximate-MPC step behind the C ABI of include/dompc_ipm.h (dompc_ampc_*).
 // Generic: sizes come from the per-network code object (dompc_ampc_info_kernel); weights and bounds are data of the handle.
 // Build flavours as dompc_lqr_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU together with
-// dompc_ampc.hip compiled as C++ (tests/_hostemu; never shipped).
+// dompc_ampc.hip compiled as C++ (tests/_hostemu; never shipped).  dompc_host.h knows which one this is; this file does not.
 #include "../../include/dompc_ipm.h"
 #include "dompc_host.h"
 #include "dompc_ampc_args.h"
 
-#ifdef DOMPC_HOST_EMU
-extern "C" void dompc_ampc_hostemu_info(int64_t* out, char* hash);
-extern "C" void dompc_ampc_hostemu_run(const dompc_ampck::Args* A);
-extern "C" void dompc_ampc_hostemu_jac(const dompc_ampck::JacArgs* J);
-#endif
+// the host twins of the kernels (dompc_ampc.hip)
+extern "C" void dompc_ampc_hostemu_info(const void* args);
+extern "C" void dompc_ampc_hostemu_run(const void* args);
+extern "C" void dompc_ampc_hostemu_jac(const void* args);
 
 static thread_local std::string g_ampc_create_error;
 
@@ -24,10 +23,7 @@ struct dompc_ampc : dompc_host::Context {
   double *s_x = nullptr, *s_up = nullptr, *s_u = nullptr;
   int32_t cap_jac = 0;                   // staging of the Jacobian's two outputs (its x, u_prev and u are the step's)
   double *s_dx = nullptr, *s_dup = nullptr;
-#ifndef DOMPC_HOST_EMU
-  hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr, fn_jac = nullptr, fn_info = nullptr;
-#endif
+  dompc_host::Kernel fn, fn_jac;
 };
 
 extern "C" const char* dompc_ampc_last_error(const dompc_ampc* h) { return h ? h->error.c_str() : g_ampc_create_error.c_str(); }
@@ -48,16 +44,10 @@ extern "C" int dompc_ampc_create(const dompc_ampc_desc* desc, dompc_ampc** out) 
   if (desc->nx <= 0 || desc->nx > desc->n_in) { h->error = "nx must be between 1 and n_in"; return fail(); }
   int64_t info[16] = {0};
   char hash[64] = {0};
-#ifndef DOMPC_HOST_EMU
-  if (h->open_device("approximate MPC") ||
-      h->load_module(desc->code_object_path, &h->module,
-                     {{"dompc_ampc_kernel", &h->fn}, {"dompc_ampc_jac_kernel", &h->fn_jac}, {"dompc_ampc_info_kernel", &h->fn_info}},
-                     "code object lacks the network kernels") ||
-      h->query_info(h->fn_info, "dompc_ampc_info_kernel", info, hash))
+  if (h->open("approximate MPC", desc->code_object_path, nullptr,
+              {{"dompc_ampc_kernel", &h->fn, DOMPC_TWIN(dompc_ampc_hostemu_run)}, {"dompc_ampc_jac_kernel", &h->fn_jac, DOMPC_TWIN(dompc_ampc_hostemu_jac)}},
+              "code object lacks the network kernels", "dompc_ampc_info_kernel", DOMPC_TWIN(dompc_ampc_hostemu_info), info, hash))
     return fail();
-#else
-  dompc_ampc_hostemu_info(info, hash);
-#endif
   const int64_t want[7] = {desc->n_in, desc->n_out, desc->n_hidden_layers, desc->n_neurons, desc->act, desc->out_act, desc->scaling ? 1 : 0};
   if (h->check_info("network ", info, want, 7, 7, sizeof(dompc_ampck::Args), hash, desc->model_hash)) return fail();
   if (info[9] != (int64_t)sizeof(dompc_ampck::JacArgs)) { h->error = "network argument layout mismatch between runtime and code object (Jacobian kernel)"; return fail(); }
@@ -87,10 +77,7 @@ extern "C" int dompc_ampc_set_weights(dompc_ampc* h, const float* packed, int64_
   std::vector<double> par((size_t)(2 * ni + 3 * no));
   for (int i = 0; i < ni; ++i) { par[i] = lb_in[i]; par[ni + i] = ub_in[i] - lb_in[i]; }
   for (int i = 0; i < no; ++i) { par[2 * ni + i] = lbu[i]; par[2 * ni + no + i] = ubu[i]; par[2 * ni + 2 * no + i] = ubu[i] - lbu[i]; }
-  if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipDeviceSynchronize());     // no step that still reads the old weights is in flight on any stream
-#endif
+  if (h->set_device() || h->drain()) return 1;     // no step that still reads the old weights is in flight on any stream
   if (h->h2d(h->w, packed, sizeof(float) * (size_t)n) || h->h2d(h->par, par.data(), sizeof(double) * par.size()) || h->sync()) return 1;
   h->have_weights = true;
   return 0;
@@ -108,14 +95,8 @@ extern "C" int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const doub
   G.x = x; G.u_prev = u_prev; G.u = u; G.w = h->w; G.par = h->par;
   G.batch = B; G.nx = d.nx; G.clip = clip ? 1 : 0;
   if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
   // one wavefront per workgroup, 32 samples per wavefront
-  return h->launch(h->fn, (unsigned)(((int64_t)B + 31) / 32), 64, 0, (hipStream_t)stream, &G, sizeof(G));
-#else
-  (void)stream;
-  dompc_ampc_hostemu_run(&G);
-  return 0;
-#endif
+  return h->run(h->fn, (unsigned)(((int64_t)B + 31) / 32), 64, 0, stream, &G, sizeof(G));
 }
 
 extern "C" int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, int32_t clip) {
@@ -146,13 +127,7 @@ extern "C" int dompc_ampc_jacobian_batch_device(dompc_ampc* h, int32_t B, const 
   G.step.batch = B; G.step.nx = d.nx; G.step.clip = clip ? 1 : 0;
   G.du_dx = du_dx; G.du_du_prev = d.n_in > d.nx ? du_du_prev : nullptr;
   if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
-  return h->launch(h->fn_jac, (unsigned)(((int64_t)B + 31) / 32), 64, 0, (hipStream_t)stream, &G, sizeof(G));
-#else
-  (void)stream;
-  dompc_ampc_hostemu_jac(&G);
-  return 0;
-#endif
+  return h->run(h->fn_jac, (unsigned)(((int64_t)B + 31) / 32), 64, 0, stream, &G, sizeof(G));
 }
 
 extern "C" int dompc_ampc_jacobian_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, double* du_dx,

@@ -1,17 +1,17 @@
 // dompc_asmpc_runtime.cpp - host side of the sensitivity-based MPC law behind the C ABI of include/dompc_ipm.h (dompc_asmpc_*).
 // Generic: sizes come from the per-shape code object (dompc_asmpc_info_kernel); the law record, the bounds and the scaling are data
 // of the handle.  Build flavours as dompc_ampc_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU
-// together with dompc_asmpc.hip compiled as C++ (tests/_hostemu; never shipped).
+// together with dompc_asmpc.hip compiled as C++ (tests/_hostemu; never shipped).  dompc_host.h knows which one this is; this file does not.
 #include "../../include/dompc_ipm.h"
 #include "dompc_host.h"
 #include "dompc_asmpc_args.h"
 
-#ifdef DOMPC_HOST_EMU
-extern "C" void dompc_asmpc_hostemu_info(int64_t* out, char* hash);
-extern "C" void dompc_asmpc_hostemu_prepare(const dompc_asmpck::PrepArgs* A);
-extern "C" void dompc_asmpc_hostemu_step(const dompc_asmpck::StepArgs* A);
-extern "C" void dompc_asmpc_hostemu_select(const dompc_asmpck::SelectArgs* A);
-#endif
+// the host twins of the kernels (dompc_asmpc.hip)
+extern "C" void dompc_asmpc_hostemu_info(const void* args);
+extern "C" void dompc_asmpc_hostemu_prepare(const void* args);
+extern "C" void dompc_asmpc_hostemu_step(const void* args);
+extern "C" void dompc_asmpc_hostemu_select_count(const void* args);
+extern "C" void dompc_asmpc_hostemu_select_write(const void* args);
 
 static_assert(sizeof(dompc_affine_law) == sizeof(dompc_affine::Law), "dompc_affine_law of the C ABI and the kernels' law record");
 
@@ -33,10 +33,7 @@ struct dompc_asmpc : dompc_host::Context {
   // per-workgroup counts of the selection: one entry per SELECT_SPAN loops
   int32_t sel_cap = 0;
   int32_t* sel_count = nullptr;
-#ifndef DOMPC_HOST_EMU
-  hipModule_t module = nullptr;
-  hipFunction_t fn_prep = nullptr, fn_step = nullptr, fn_info = nullptr, fn_sel_count = nullptr, fn_sel_write = nullptr;
-#endif
+  dompc_host::Kernel fn_prep, fn_step, fn_sel_count, fn_sel_write;
   int grow_host_staging(int32_t B) {
     const size_t D = sizeof(double);
     return grow_staging(&cap, B, {{(void**)&s_x, D * d.nx}, {(void**)&s_u, D * d.nu}, {(void**)&s_J, D * d.nx * d.nu},
@@ -64,18 +61,13 @@ extern "C" int dompc_asmpc_create(const dompc_asmpc_desc* desc, dompc_asmpc** ou
   if (desc->nx <= 0 || desc->nu <= 0) { h->error = "law without states or without inputs"; return fail(); }
   int64_t info[16] = {0};
   char hash[64] = {0};
-#ifndef DOMPC_HOST_EMU
-  if (h->open_device("sensitivity-based MPC law") ||
-      h->load_module(desc->code_object_path, &h->module, {{"dompc_asmpc_prepare_kernel", &h->fn_prep}, {"dompc_asmpc_step_kernel", &h->fn_step},
-                                                          {"dompc_asmpc_info_kernel", &h->fn_info},
-                                                          {"dompc_asmpc_select_count_kernel", &h->fn_sel_count},
-                                                          {"dompc_asmpc_select_write_kernel", &h->fn_sel_write}},
-                     "code object lacks the law kernels") ||
-      h->query_info(h->fn_info, "dompc_asmpc_info_kernel", info, hash))
+  if (h->open("sensitivity-based MPC law", desc->code_object_path, nullptr,
+              {{"dompc_asmpc_prepare_kernel", &h->fn_prep, DOMPC_TWIN(dompc_asmpc_hostemu_prepare)},
+               {"dompc_asmpc_step_kernel", &h->fn_step, DOMPC_TWIN(dompc_asmpc_hostemu_step)},
+               {"dompc_asmpc_select_count_kernel", &h->fn_sel_count, DOMPC_TWIN(dompc_asmpc_hostemu_select_count)},
+               {"dompc_asmpc_select_write_kernel", &h->fn_sel_write, DOMPC_TWIN(dompc_asmpc_hostemu_select_write)}},
+              "code object lacks the law kernels", "dompc_asmpc_info_kernel", DOMPC_TWIN(dompc_asmpc_hostemu_info), info, hash))
     return fail();
-#else
-  dompc_asmpc_hostemu_info(info, hash);
-#endif
   const int64_t want[2] = {desc->nx, desc->nu};
   if (h->check_info("law ", info, want, 2, 2, sizeof(dompc_asmpck::PrepArgs), hash, desc->model_hash)) return fail();
   if (info[3] != (int64_t)sizeof(dompc_asmpck::StepArgs) || info[4] != (int64_t)sizeof(dompc_asmpck::SelectArgs)) { h->error = "law argument layout mismatch between runtime and code object"; return fail(); }
@@ -94,10 +86,7 @@ extern "C" int dompc_asmpc_set_options(dompc_asmpc* h, const double* lbu, const 
   if (!h) return 1;
   if (!lbu || !ubu || !x_scale) { h->error = "null pointer"; return 1; }
   if (!(max_dx >= 0.0)) { h->error = "max_dx must not be negative"; return 1; }
-  if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipDeviceSynchronize());     // no step that still reads the old bounds is in flight on any stream
-#endif
+  if (h->set_device() || h->drain()) return 1;     // no step that still reads the old bounds is in flight on any stream
   const size_t D = sizeof(double);
   if (h->h2d(h->lb, lbu, D * h->d.nu) || h->h2d(h->ub, ubu, D * h->d.nu) || h->h2d(h->xs, x_scale, D * h->d.nx) || h->sync()) return 1;
   h->clip = clip ? 1 : 0;
@@ -132,14 +121,8 @@ static int launch_prepare(dompc_asmpc* h, int32_t n, const int32_t* slot, const 
   A.row_J = row_J; A.batch_J = batch_J; A.row_G = row_G; A.batch_G = batch_G;
   fill_law(h, A.law);
   A.batch = n;
-#ifndef DOMPC_HOST_EMU
   // one wavefront per workgroup, four loops per wavefront
-  return h->launch(h->fn_prep, (unsigned)((n + 3) / 4), 64, 0, (hipStream_t)stream, &A, sizeof(A));
-#else
-  (void)stream;
-  dompc_asmpc_hostemu_prepare(&A);
-  return 0;
-#endif
+  return h->run(h->fn_prep, (unsigned)((n + 3) / 4), 64, 0, stream, &A, sizeof(A));
 }
 
 extern "C" int dompc_asmpc_prepare_device(dompc_asmpc* h, int32_t B, const double* x_prev, const double* u0, const double* J, int64_t row_J,
@@ -207,23 +190,15 @@ extern "C" int dompc_asmpc_select_device(dompc_asmpc* h, int32_t B, const int32_
   if (h->set_device()) return 1;
   const int32_t groups = (B + dompc_asmpck::SELECT_SPAN - 1) / dompc_asmpck::SELECT_SPAN;
   if (groups > h->sel_cap) {
-#ifndef DOMPC_HOST_EMU
-    HIPCHK(h, hipDeviceSynchronize());     // no selection that still uses the old counts is in flight on any stream
-#endif
+    if (h->drain()) return 1;              // no selection that still uses the old counts is in flight on any stream
     if (h->grow_staging(&h->sel_cap, groups, {{(void**)&h->sel_count, sizeof(int32_t)}})) return 1;
   }
   dompc_asmpck::SelectArgs A;
   memset(&A, 0, sizeof(A));
   A.status = status; A.idx = idx; A.count = count; A.group_count = h->sel_count;
   A.batch = B; A.mask = mask;
-#ifndef DOMPC_HOST_EMU
-  if (h->launch(h->fn_sel_count, (unsigned)groups, dompc_asmpck::SELECT_THREADS, 0, (hipStream_t)stream, &A, sizeof(A))) return 1;
-  return h->launch(h->fn_sel_write, (unsigned)groups, dompc_asmpck::SELECT_THREADS, 0, (hipStream_t)stream, &A, sizeof(A));
-#else
-  (void)stream;
-  dompc_asmpc_hostemu_select(&A);
-  return 0;
-#endif
+  if (h->run(h->fn_sel_count, (unsigned)groups, dompc_asmpck::SELECT_THREADS, 0, stream, &A, sizeof(A))) return 1;
+  return h->run(h->fn_sel_write, (unsigned)groups, dompc_asmpck::SELECT_THREADS, 0, stream, &A, sizeof(A));
 }
 
 extern "C" int dompc_asmpc_set_law(dompc_asmpc* h, int32_t B, const double* x_prev, const double* u0, const double* J, const double* G,
@@ -249,10 +224,7 @@ extern "C" int dompc_asmpc_get_law(dompc_asmpc* h, double* x_ref, double* u_ref,
   if (h->law_B <= 0) { h->error = "no law: nothing has been solved yet"; return 1; }
   const dompc_asmpc_desc& d = h->d;
   const size_t B = (size_t)h->law_B, D = sizeof(double);
-  if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipDeviceSynchronize());     // a preparation on a stream of the caller has finished
-#endif
+  if (h->set_device() || h->drain()) return 1;     // a preparation on a stream of the caller has finished
   std::vector<double> xr(B * d.nx), ur(B * d.nu), m(B * d.nx * d.nu);
   if (h->d2h(xr.data(), h->x_ref, D * xr.size()) || h->d2h(ur.data(), h->u_ref, D * ur.size()) || h->d2h(m.data(), h->M, D * m.size()) ||
       (flags && h->d2h(flags, h->flags, sizeof(int32_t) * B)) || h->sync())
@@ -282,13 +254,7 @@ extern "C" int dompc_asmpc_step_batch_device(dompc_asmpc* h, int32_t B, const do
   fill_law(h, A.law);
   A.batch = B;
   if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
-  return h->launch(h->fn_step, (unsigned)((B + 63) / 64), 64, 0, (hipStream_t)stream, &A, sizeof(A));
-#else
-  (void)stream;
-  dompc_asmpc_hostemu_step(&A);
-  return 0;
-#endif
+  return h->run(h->fn_step, (unsigned)((B + 63) / 64), 64, 0, stream, &A, sizeof(A));
 }
 
 extern "C" int dompc_asmpc_step_batch(dompc_asmpc* h, int32_t B, const double* x, double* u_out, int32_t* status) {

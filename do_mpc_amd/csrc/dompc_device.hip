@@ -141,12 +141,16 @@ extern "C" __global__ void __launch_bounds__(256) dompc_sens_finish_kernel(dompc
   for (int64_t it = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; it < n; it += (int64_t)gridDim.x * blockDim.x) dompc::sens_finish_item(A, it);
 }
 #else
-extern "C" void dompc_hostemu_model_info(const int32_t* in, int64_t* out, char* hash) {
-  dompc::model_info(in, out);
+// The host twins take what the runtime passes to dompc_host::Context::run: the kernel's argument block behind a const void*.
+extern "C" void dompc_hostemu_model_info(const void* args) {
+  void* const* a = (void* const*)args;
+  char* hash = (char*)a[2];
+  dompc::model_info((const int32_t*)a[0], (int64_t*)a[1]);
   const char h[] = DOMPC_MODEL_HASH;
   for (int i = 0; i < (int)sizeof(h); ++i) hash[i] = h[i];
 }
-extern "C" void dompc_hostemu_run(const dompc::KArgs* A) {
+extern "C" void dompc_hostemu_run(const void* args) {
+  const dompc::KArgs* A = (const dompc::KArgs*)args;
   static thread_local double red[dompc::RED_MAX];
   static thread_local double filt[2 * dompc::MAX_FILTER];
   static thread_local int flags[8];
@@ -162,15 +166,22 @@ extern "C" void dompc_hostemu_run(const dompc::KArgs* A) {
     for (int b = 0; b < A->batch; ++b) dompc::debug_newton(T, *A, b, 0);
     return;
   }
-  if (A->mode == 3) {                    // sensitivities: parameter rows, Newton directions, difference quotients
-    for (int64_t it = 0; it < (int64_t)A->batch * A->n_opt_p; ++it) dompc::sens_prep_item(*A, it);
+  if (A->mode == 3) {                    // sensitivities: the Newton directions (twin of dompc_sens_kernel)
     for (int b = 0; b < A->batch; ++b) dompc::sens_newton(T, *A, b, 0);
-    for (int64_t it = 0; it < (int64_t)(A->batch / A->sn_R) * A->sn_nsel * A->sn_ncols; ++it) dompc::sens_finish_item(*A, it);
     return;
   }
   for (int b = 0; b < A->batch; ++b) {
     if (A->mode == 2) dompc::sweep_problem(T, *A, b, 0);
     else dompc::solve_problem(T, *A, b, 0);
   }
+}
+// parameter rows before, difference quotients after the Newton directions (twins of dompc_sens_prep_kernel / dompc_sens_finish_kernel)
+extern "C" void dompc_hostemu_sens_prep(const void* args) {
+  const dompc::KArgs* A = (const dompc::KArgs*)args;
+  for (int64_t it = 0; it < (int64_t)A->batch * A->n_opt_p; ++it) dompc::sens_prep_item(*A, it);
+}
+extern "C" void dompc_hostemu_sens_finish(const void* args) {
+  const dompc::KArgs* A = (const dompc::KArgs*)args;
+  for (int64_t it = 0; it < (int64_t)(A->batch / A->sn_R) * A->sn_nsel * A->sn_ncols; ++it) dompc::sens_finish_item(*A, it);
 }
 #endif

@@ -1,15 +1,14 @@
 // dompc_ekf_runtime.cpp - host side of the batched extended Kalman filter behind the C ABI of include/dompc_ipm.h (dompc_ekf_*).
 // Generic: sizes come from the per-model code object (dompc_ekf_info_kernel).
 // Build flavours as dompc_plant_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU together with
-// dompc_ekf.hip compiled as C++ (tests/_hostemu; never shipped).
+// dompc_ekf.hip compiled as C++ (tests/_hostemu; never shipped).  dompc_host.h knows which one this is; this file does not.
 #include "../../include/dompc_ipm.h"
 #include "dompc_host.h"
 #include "dompc_ekf_args.h"
 
-#ifdef DOMPC_HOST_EMU
-extern "C" void dompc_ekf_hostemu_info(int64_t* out, char* hash);
-extern "C" void dompc_ekf_hostemu_run(const dompc_ekfk::Args* A);
-#endif
+// the host twins of the kernels (dompc_ekf.hip)
+extern "C" void dompc_ekf_hostemu_info(const void* args);
+extern "C" void dompc_ekf_hostemu_run(const void* args);
 
 static thread_local std::string g_ekf_create_error;
 
@@ -19,10 +18,7 @@ struct dompc_ekf : dompc_host::Context {
   double *s_x = nullptr, *s_P = nullptr, *s_y = nullptr, *s_u = nullptr, *s_tvp = nullptr, *s_p = nullptr, *s_Q = nullptr, *s_R = nullptr;
   double* s_z = nullptr;
   int32_t *s_st = nullptr, *s_nw = nullptr;
-#ifndef DOMPC_HOST_EMU
-  hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr, fn_info = nullptr;
-#endif
+  dompc_host::Kernel fn;
 };
 
 extern "C" const char* dompc_ekf_last_error(const dompc_ekf* h) { return h ? h->error.c_str() : g_ekf_create_error.c_str(); }
@@ -44,15 +40,9 @@ extern "C" int dompc_ekf_create(const dompc_ekf_desc* desc, dompc_ekf** out) {
   if (desc->nz < 0 || desc->nz > 16) { h->error = "algebraic states: 0 <= nz <= 16"; return fail(); }
   int64_t info[16] = {0};
   char hash[64] = {0};
-#ifndef DOMPC_HOST_EMU
-  if (h->open_device("extended Kalman filter") ||
-      h->load_module(desc->code_object_path, &h->module, {{"dompc_ekf_kernel", &h->fn}, {"dompc_ekf_info_kernel", &h->fn_info}},
-                     "code object lacks the filter kernels") ||
-      h->query_info(h->fn_info, "dompc_ekf_info_kernel", info, hash))
+  if (h->open("extended Kalman filter", desc->code_object_path, nullptr, {{"dompc_ekf_kernel", &h->fn, DOMPC_TWIN(dompc_ekf_hostemu_run)}},
+              "code object lacks the filter kernels", "dompc_ekf_info_kernel", DOMPC_TWIN(dompc_ekf_hostemu_info), info, hash))
     return fail();
-#else
-  dompc_ekf_hostemu_info(info, hash);
-#endif
   const int64_t want[6] = {desc->nx, desc->nu, desc->np, desc->ntvp, desc->ny, desc->discrete ? 1 : 0};
   if (h->check_info("filter ", info, want, 6, 6, sizeof(dompc_ekfk::Args), hash, desc->model_hash)) return fail();
   if (info[7] != desc->nz) { h->error = "filter code object was built for another number of algebraic states"; return fail(); }
@@ -80,14 +70,8 @@ static int step_device(dompc_ekf* h, int32_t B, double* x, double* P, const doub
   A.z_tol = d.z_tol > 0 ? d.z_tol : 1e-10;
   A.z_max_iter = d.z_max_iter > 0 ? d.z_max_iter : 20;
   if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
   // one wavefront per workgroup, four filters per wavefront
-  return h->launch(h->fn, (unsigned)((B + 3) / 4), 64, 0, (hipStream_t)stream, &A, sizeof(A));
-#else
-  (void)stream;
-  dompc_ekf_hostemu_run(&A);
-  return 0;
-#endif
+  return h->run(h->fn, (unsigned)((B + 3) / 4), 64, 0, stream, &A, sizeof(A));
 }
 
 extern "C" int dompc_ekf_step_batch_device(dompc_ekf* h, int32_t B, double* x, double* P, const double* y, const double* u,

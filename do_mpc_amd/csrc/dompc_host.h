@@ -1,6 +1,9 @@
-// dompc_host.h - the host device layer shared by dompc_runtime.cpp, dompc_plant_runtime.cpp and dompc_ekf_runtime.cpp: the one
-// place that knows both build flavours of the runtimes (product: HIP; test: -DDOMPC_HOST_EMU, "device" memory = host memory).
-// Host only - no .hip file and no kernel header includes it.  Everything is inline: the three .cpp files are three translation
+// dompc_host.h - the host device layer shared by the six runtimes (dompc_runtime.cpp and dompc_{plant,ekf,lqr,ampc,asmpc}_runtime.cpp):
+// the one place that knows both build flavours of the runtimes (product: HIP; test: -DDOMPC_HOST_EMU, "device" memory = host memory,
+// a kernel = its host twin, the same kernel text compiled by g++).  It hides the device, the stream, tracked allocations, staging
+// buffers and copies, and - behind one Kernel handle - loading a code object, asking its info kernel what it was built for, and
+// launching; a runtime forks on the flavour only for what exists with HIP alone (dompc_runtime.cpp: RCCL, mapped host words, ...).
+// Host only - no .hip file and no kernel header includes it.  Everything is inline: the six .cpp files are six translation
 // units of libdompc_ipm.so and, each one alone, a host-emulation library of the tests.
 #pragma once
 #include <cstdint>
@@ -22,9 +25,25 @@
       return 1;                                                                             \
     }                                                                                       \
   } while (0)
+#define DOMPC_TWIN(f) nullptr            // the product build launches the kernel; its host twin is declared, never defined
+#else
+#define DOMPC_TWIN(f) (f)
 #endif
 
 namespace dompc_host {
+
+// The host twin of a kernel (host emulation): called with the argument block the kernel is launched with.
+using Twin = void (*)(const void* args);
+
+// What a runtime holds per kernel entry of its code object: the loaded function, or the twin in the host emulation.
+#ifndef DOMPC_HOST_EMU
+using Module = hipModule_t;
+struct Kernel { hipFunction_t fn = nullptr; explicit operator bool() const { return fn != nullptr; } };
+#else
+using Module = void*;                    // (nothing is loaded: always null)
+struct Kernel { Twin twin = nullptr; explicit operator bool() const { return twin != nullptr; } };
+#endif
+struct Entry { const char* name; Kernel* kernel; Twin twin; };     // a kernel to look up: Entry{"..._kernel", &k, DOMPC_TWIN(..._hostemu_...)}
 
 struct StagingSlot { void** slot; size_t bytes_per_row; };      // one staging buffer of a host-pointer entry point
 
@@ -82,6 +101,18 @@ struct Context {
     return 0;
   }
   void* stream_ptr() const { return (void*)stream; }
+  int h2d_now(void* dst, const void* src, size_t bytes) {      // has completed on return: `src` may go away
+    HIPCHK(this, hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+  }
+  int fill(void* p, int byte, size_t bytes, void* st) {        // byte fill of an allocation, in the order of stream `st`
+    HIPCHK(this, hipMemsetAsync(p, byte, bytes, (hipStream_t)st));
+    return 0;
+  }
+  int drain() {                          // nothing is in flight on any stream of this device
+    HIPCHK(this, hipDeviceSynchronize());
+    return 0;
+  }
 
   // `component` names the caller in the message a user without a GPU reads ("plant integrator", ...)
   int open_device(const char* component) {
@@ -95,39 +126,35 @@ struct Context {
     return 0;
   }
 
-  struct Kernel { const char* name; hipFunction_t* fn; };
   // load the code object at `path` and look the kernels up; `lacks`: the message when one of them is missing
-  int load_module(const char* path, hipModule_t* module, std::initializer_list<Kernel> kernels, const std::string& lacks) {
+  int load(const char* path, Module* module, std::initializer_list<Entry> kernels, const std::string& lacks) {
     if (!path || hipModuleLoad(module, path) != hipSuccess) {
+      (void)hipGetLastError();           // (see find)
       error = std::string("hipModuleLoad failed for ") + (path ? path : "(null)");
       return 1;
     }
     modules.push_back(*module);
-    for (const Kernel& k : kernels)
-      if (hipModuleGetFunction(k.fn, *module, k.name) != hipSuccess) { error = lacks; return 1; }
+    for (const Entry& e : kernels)
+      if (!find(*module, e)) { error = lacks; return 1; }
     return 0;
   }
-  void unload_module(hipModule_t m) {
+  // one more entry of a loaded code object (an optional kernel, or one looked up on first use): false when it is not there.  The
+  // refusal is the caller's to report: HIP's sticky last error is taken back, or the next launch check of another library in the
+  // process (torch's) reports "named symbol not found" for a kernel of its own.
+  bool find(Module module, const Entry& e) {
+    if (hipModuleGetFunction(&e.kernel->fn, module, e.name) == hipSuccess) return true;
+    (void)hipGetLastError();
+    return false;
+  }
+  void unload(Module m) {
     for (size_t i = 0; i < modules.size(); ++i)
       if (modules[i] == m) { modules.erase(modules.begin() + i); (void)hipModuleUnload(m); return; }
   }
 
-  // launch with the argument block passed as a parameter buffer; `lds_bytes`: dynamic LDS
-  int launch(hipFunction_t fn, unsigned grid, unsigned block, unsigned lds_bytes, hipStream_t st, void* args, size_t args_bytes) {
-    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &args_bytes, HIP_LAUNCH_PARAM_END};
-    HIPCHK(this, hipModuleLaunchKernel(fn, grid, 1, 1, block, 1, 1, lds_bytes, st, nullptr, cfg));
-    return 0;
-  }
-
-  // info kernel of a code object (1 x 64 threads, arguments {int64_t* info, char* hash}): what it was built for
-  int query_info(hipFunction_t fn, const char* kernel_name, int64_t (&info)[16], char (&hash)[64]) {
-    int64_t* info_d; char* hash_d;
-    if (alloc((void**)&info_d, sizeof(info)) || alloc((void**)&hash_d, sizeof(hash))) return 1;
-    struct { int64_t* a; char* b; } args = {info_d, hash_d};
-    if (launch(fn, 1, 64, 0, stream, &args, sizeof(args)) || d2h(info, info_d, sizeof(info)) || d2h(hash, hash_d, sizeof(hash)) || sync()) {
-      error = std::string(kernel_name) + " failed";
-      return 1;
-    }
+  // launch on stream `st` with the argument block passed as a parameter buffer; `lds_bytes`: dynamic LDS
+  int run(Kernel k, unsigned grid, unsigned block, unsigned lds_bytes, void* st, const void* args, size_t args_bytes) {
+    void* cfg[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, const_cast<void*>(args), HIP_LAUNCH_PARAM_BUFFER_SIZE, &args_bytes, HIP_LAUNCH_PARAM_END};
+    HIPCHK(this, hipModuleLaunchKernel(k.fn, grid, 1, 1, block, 1, 1, lds_bytes, (hipStream_t)st, nullptr, cfg));
     return 0;
   }
 
@@ -150,8 +177,51 @@ struct Context {
   int sync() { return 0; }
   int set_device() { return 0; }
   void* stream_ptr() const { return nullptr; }
+  int h2d_now(void* dst, const void* src, size_t bytes) { return h2d(dst, src, bytes); }
+  int fill(void* p, int byte, size_t bytes, void*) { memset(p, byte, bytes); return 0; }
+  int drain() { return 0; }
+  int open_device(const char*) { return 0; }
+  // (nothing to load: the twins are bound, `module` stays null)
+  int load(const char*, Module* module, std::initializer_list<Entry> kernels, const std::string&) {
+    *module = nullptr;
+    for (const Entry& e : kernels) find(*module, e);
+    return 0;
+  }
+  bool find(Module, const Entry& e) { e.kernel->twin = e.twin; return true; }
+  void unload(Module) {}
+  int run(Kernel k, unsigned, unsigned, unsigned, void*, const void* args, size_t) { k.twin(args); return 0; }
   void close() { for (void* p : allocs) free_dev(p); }
 #endif
+
+  // The info kernel of a code object (1 x 64 threads): what it was built for.  Its arguments are {info, hash}, after a copy of the
+  // input block `in` when there is one (the solver's: {in, info, hash}).
+  template <int N>
+  int query(Kernel k, const char* kernel_name, int64_t (&info)[N], char (&hash)[64], const void* in = nullptr, size_t in_bytes = 0) {
+    void* args[3] = {nullptr, nullptr, nullptr};
+    void **in_d = &args[0], **info_d = &args[in ? 1 : 0], **hash_d = info_d + 1;
+    if ((in && alloc(in_d, in_bytes)) || alloc(info_d, sizeof(info)) || alloc(hash_d, sizeof(hash))) return 1;
+    if ((in && h2d(*in_d, in, in_bytes)) || fill(*info_d, 0, sizeof(info), stream_ptr()) ||
+        run(k, 1, 64, 0, stream_ptr(), args, (in ? 3 : 2) * sizeof(void*)) || d2h(info, *info_d, sizeof(info)) ||
+        d2h(hash, *hash_d, sizeof(hash)) || sync()) {
+      error = std::string(kernel_name) + " failed";
+      return 1;
+    }
+    return 0;
+  }
+
+  // The start of every create: the device (`component` names the caller to a user without a GPU), the code object at `path` with
+  // `kernels` (`lacks`: the message when one is missing, the info kernel included) and what its info kernel `info_kernel` reports.
+  // `module`: null unless the caller looks further entries up later (find).
+  template <int N>
+  int open(const char* component, const char* path, Module* module, std::initializer_list<Entry> kernels, const std::string& lacks,
+           const char* info_kernel, Twin info_twin, int64_t (&info)[N], char (&hash)[64], const void* in = nullptr, size_t in_bytes = 0) {
+    Module m;
+    Kernel k_info;
+    if (open_device(component) || load(path, &m, kernels, lacks)) return 1;
+    if (module) *module = m;
+    if (!find(m, Entry{info_kernel, &k_info, info_twin})) { error = lacks; return 1; }
+    return query(k_info, info_kernel, info, hash, in, in_bytes);
+  }
 
   // What the info kernel reported against what the description asks for: the first n_want entries of info[], sizeof(Args) at
   // info[i_args], the model hash.  `what` starts the messages ("plant ", "filter ", "" for the solver).

@@ -1,15 +1,14 @@
 // dompc_lqr_runtime.cpp - host side of the batched LQR design behind the C ABI of include/dompc_ipm.h (dompc_lqr_*).
 // Generic: sizes come from the per-design code object (dompc_lqr_info_kernel).
 // Build flavours as dompc_ekf_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU together with
-// dompc_lqr.hip compiled as C++ (tests/_hostemu; never shipped).
+// dompc_lqr.hip compiled as C++ (tests/_hostemu; never shipped).  dompc_host.h knows which one this is; this file does not.
 #include "../../include/dompc_ipm.h"
 #include "dompc_host.h"
 #include "dompc_lqr_args.h"
 
-#ifdef DOMPC_HOST_EMU
-extern "C" void dompc_lqr_hostemu_info(int64_t* out, char* hash);
-extern "C" void dompc_lqr_hostemu_run(const dompc_lqrk::Args* A);
-#endif
+// the host twins of the kernels (dompc_lqr.hip)
+extern "C" void dompc_lqr_hostemu_info(const void* args);
+extern "C" void dompc_lqr_hostemu_run(const void* args);
 
 static thread_local std::string g_lqr_create_error;
 
@@ -19,10 +18,7 @@ struct dompc_lqr : dompc_host::Context {
   double *s_A = nullptr, *s_B = nullptr, *s_x = nullptr, *s_u = nullptr, *s_tvp = nullptr, *s_p = nullptr, *s_Q = nullptr, *s_R = nullptr,
          *s_Pf = nullptr, *s_K = nullptr, *s_P = nullptr, *s_z = nullptr;
   int32_t* s_st = nullptr;
-#ifndef DOMPC_HOST_EMU
-  hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr, fn_info = nullptr;
-#endif
+  dompc_host::Kernel fn;
 };
 
 extern "C" const char* dompc_lqr_last_error(const dompc_lqr* h) { return h ? h->error.c_str() : g_lqr_create_error.c_str(); }
@@ -45,15 +41,9 @@ extern "C" int dompc_lqr_create(const dompc_lqr_desc* desc, dompc_lqr** out) {
   if (desc->nz < 0 || desc->nz > 16 || (desc->nz && !desc->has_model)) { h->error = "algebraic states: 0 <= nz <= 16, with a model"; return fail(); }
   int64_t info[16] = {0};
   char hash[64] = {0};
-#ifndef DOMPC_HOST_EMU
-  if (h->open_device("LQR design") ||
-      h->load_module(desc->code_object_path, &h->module, {{"dompc_lqr_kernel", &h->fn}, {"dompc_lqr_info_kernel", &h->fn_info}},
-                     "code object lacks the design kernels") ||
-      h->query_info(h->fn_info, "dompc_lqr_info_kernel", info, hash))
+  if (h->open("LQR design", desc->code_object_path, nullptr, {{"dompc_lqr_kernel", &h->fn, DOMPC_TWIN(dompc_lqr_hostemu_run)}},
+              "code object lacks the design kernels", "dompc_lqr_info_kernel", DOMPC_TWIN(dompc_lqr_hostemu_info), info, hash))
     return fail();
-#else
-  dompc_lqr_hostemu_info(info, hash);
-#endif
   const int64_t want[8] = {desc->nx, desc->nu, desc->n, desc->rate ? 1 : 0, desc->has_model ? 1 : 0,
                            (desc->discrete || !desc->has_model) ? 1 : 0, desc->np, desc->ntvp};
   if (h->check_info("design ", info, want, 8, 8, sizeof(dompc_lqrk::Args), hash, desc->model_hash)) return fail();
@@ -85,14 +75,8 @@ static int design_device(dompc_lqr* h, int32_t B, double* A, double* Bm, const d
   G.z_tol = d.z_tol > 0 ? d.z_tol : 1e-10;
   G.z_max_iter = d.z_max_iter > 0 ? (d.z_max_iter < 127 ? d.z_max_iter : 127) : 20;
   if (h->set_device()) return 1;
-#ifndef DOMPC_HOST_EMU
   // one wavefront per workgroup, four designs per wavefront
-  return h->launch(h->fn, (unsigned)((B + 3) / 4), 64, 0, (hipStream_t)stream, &G, sizeof(G));
-#else
-  (void)stream;
-  dompc_lqr_hostemu_run(&G);
-  return 0;
-#endif
+  return h->run(h->fn, (unsigned)((B + 3) / 4), 64, 0, stream, &G, sizeof(G));
 }
 
 extern "C" int dompc_lqr_design_batch_device(dompc_lqr* h, int32_t B, double* A, double* Bm, const double* x, const double* u,

@@ -1,16 +1,16 @@
 // dompc_plant_runtime.cpp - host side of the batched plant integrator behind the C ABI of include/dompc_ipm.h
 // (dompc_plant_*).  Generic: sizes come from the per-model code object (dompc_plant_info_kernel).
 // Build flavours as dompc_runtime.cpp: product = part of libdompc_ipm.so (HIP only); test = g++ -DDOMPC_HOST_EMU
-// together with dompc_plant.hip compiled as C++ (tests/_hostemu; never shipped).
+// together with dompc_plant.hip compiled as C++ (tests/_hostemu; never shipped).  dompc_host.h knows which one this is; this file
+// does not.
 #include "../../include/dompc_ipm.h"
 #include "dompc_host.h"
 #include "dompc_plant_args.h"
 
-#ifdef DOMPC_HOST_EMU
-extern "C" void dompc_plant_hostemu_info(int64_t* out, char* hash);
-extern "C" void dompc_plant_hostemu_run(const dompc_plantk::Args* A);
-extern "C" void dompc_plant_hostemu_rollout(const dompc_plantk::RolloutArgs* R);
-#endif
+// the host twins of the kernels (dompc_plant.hip)
+extern "C" void dompc_plant_hostemu_info(const void* args);
+extern "C" void dompc_plant_hostemu_run(const void* args);
+extern "C" void dompc_plant_hostemu_rollout(const void* args);
 
 static_assert(sizeof(dompc_affine_law) == sizeof(dompc_affine::Law), "dompc_affine_law of the C ABI and the kernels' law record");
 
@@ -28,10 +28,8 @@ struct dompc_plant : dompc_host::Context {
   int32_t z_cap = 0, z_alloc = 0;       // rows with valid start values / rows allocated
   bool z_carry_host = false;            // host entry (dompc_plant_step_batch): rows of consecutive calls are the same trajectories (dompc_plant_set_z_carry)
   bool z_reseed_next = false;
-#ifndef DOMPC_HOST_EMU
-  hipModule_t module = nullptr;
-  hipFunction_t fn = nullptr, fn_info = nullptr, fn_rollout = nullptr;
-#endif
+  dompc_host::Module module = nullptr;
+  dompc_host::Kernel fn, fn_rollout;
 };
 
 extern "C" const char* dompc_plant_last_error(const dompc_plant* h) { return h ? h->error.c_str() : g_plant_create_error.c_str(); }
@@ -52,22 +50,14 @@ extern "C" int dompc_plant_create(const dompc_plant_desc* desc, dompc_plant** ou
   if (!(desc->t_step > 0.0) && !desc->discrete) { h->error = "t_step must be positive"; return fail(); }
   int64_t info[16] = {0};
   char hash[64] = {0};
-#ifndef DOMPC_HOST_EMU
-  if (h->open_device("plant integrator") ||
-      h->load_module(desc->code_object_path, &h->module, {{"dompc_plant_kernel", &h->fn}, {"dompc_plant_info_kernel", &h->fn_info}},
-                     "code object lacks the plant kernels") ||
-      h->query_info(h->fn_info, "dompc_plant_info_kernel", info, hash))
+  if (h->open("plant integrator", desc->code_object_path, &h->module, {{"dompc_plant_kernel", &h->fn, DOMPC_TWIN(dompc_plant_hostemu_run)}},
+              "code object lacks the plant kernels", "dompc_plant_info_kernel", DOMPC_TWIN(dompc_plant_hostemu_info), info, hash))
     return fail();
-#else
-  dompc_plant_hostemu_info(info, hash);
-#endif
   const int64_t want[8] = {desc->nx, desc->nu, desc->np, desc->ntvp, desc->nw, desc->nv, desc->ny, desc->discrete ? 1 : 0};
   if (h->check_info("plant ", info, want, 8, 8, sizeof(dompc_plantk::Args), hash, desc->model_hash)) return fail();
   if (info[9] == 0) {                    // (the rollout entry exists for plants without algebraic states only)
     if (info[10] != (int64_t)sizeof(dompc_plantk::RolloutArgs)) { h->error = "plant rollout argument layout mismatch between runtime and code object"; return fail(); }
-#ifndef DOMPC_HOST_EMU
-    if (hipModuleGetFunction(&h->fn_rollout, h->module, "dompc_plant_rollout_kernel") != hipSuccess) { h->error = "code object lacks the plant kernels"; return fail(); }
-#endif
+    if (!h->find(h->module, {"dompc_plant_rollout_kernel", &h->fn_rollout, DOMPC_TWIN(dompc_plant_hostemu_rollout)})) { h->error = "code object lacks the plant kernels"; return fail(); }
   }
   h->d.code_object_path = nullptr; h->d.model_hash = nullptr;
   h->nz = (int32_t)info[9];
@@ -109,11 +99,7 @@ static int ensure_z(dompc_plant* h, int32_t B, bool reseed) {
   std::vector<double> seed((size_t)B * h->nz);
   for (int32_t b = 0; b < B; ++b)
     for (int i = 0; i < h->nz; ++i) seed[(size_t)b * h->nz + i] = h->z0[(size_t)i];
-#ifndef DOMPC_HOST_EMU
-  HIPCHK(h, hipMemcpy(h->z_dev, seed.data(), seed.size() * sizeof(double), hipMemcpyHostToDevice));
-#else
-  memcpy(h->z_dev, seed.data(), seed.size() * sizeof(double));
-#endif
+  if (h->h2d_now(h->z_dev, seed.data(), seed.size() * sizeof(double))) return 1;      // (`seed` goes away on return)
   if (B > h->z_cap) h->z_cap = B;        // a reseed of the first B rows leaves the carried rows behind them alone
   return 0;
 }
@@ -125,13 +111,7 @@ extern "C" int dompc_plant_set_z_carry(dompc_plant* h, int32_t on) {
 }
 
 static int launch_plant(dompc_plant* h, dompc_plantk::Args& A, void* stream) {
-#ifndef DOMPC_HOST_EMU
-  return h->launch(h->fn, (A.batch + 63) / 64, 64, 0, (hipStream_t)stream, &A, sizeof(A));
-#else
-  (void)h; (void)stream;
-  dompc_plant_hostemu_run(&A);
-  return 0;
-#endif
+  return h->run(h->fn, (A.batch + 63) / 64, 64, 0, stream, &A, sizeof(A));
 }
 
 static void fill_args(const dompc_plant* h, dompc_plantk::Args& A, int32_t B, int32_t shared_mask) {
@@ -214,11 +194,5 @@ extern "C" int dompc_plant_rollout_affine_device(dompc_plant* h, int32_t B, int3
   memcpy(&R.law, law, sizeof(R.law));
   R.X_traj = X_traj; R.U_traj = U_traj; R.tvp_rows = tvp_rows; R.p_rows = p_rows;
   R.plant_status = plant_status; R.law_status = law_status; R.K = K;
-#ifndef DOMPC_HOST_EMU
-  return h->launch(h->fn_rollout, (unsigned)((B + 63) / 64), 64, 0, (hipStream_t)stream, &R, sizeof(R));
-#else
-  (void)stream;
-  dompc_plant_hostemu_rollout(&R);
-  return 0;
-#endif
+  return h->run(h->fn_rollout, (unsigned)((B + 63) / 64), 64, 0, stream, &R, sizeof(R));
 }

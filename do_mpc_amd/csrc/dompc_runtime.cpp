@@ -8,6 +8,9 @@
 //   product : hipcc -shared -fPIC dompc_runtime.cpp            -> libdompc_ipm.so   (HIP only)
 //   test    : g++ -DDOMPC_HOST_EMU dompc_runtime.cpp dompc_device.hip(as C++) -> tests/_hostemu/*.so
 //             ("device" memory = host memory, a workgroup = the calling thread).  Never shipped.
+// Loading, the info query and the launches go through dompc_host.h in both flavours; a DOMPC_HOST_EMU conditional in this file marks
+// something that exists with HIP only (RCCL, the mapped host words and the exchange loop, the shard stream, the watchdog, the occupancy
+// query, the launch-shape overrides and wide mode) or the emulation's one slot.
 #include <chrono>
 #include <dlfcn.h>
 #include <cmath>
@@ -20,10 +23,13 @@
 using dompc_launch::BATCH_ONE_WAVE;
 using dompc_launch::fit_block;
 
-#ifdef DOMPC_HOST_EMU
-extern "C" void dompc_hostemu_model_info(const int32_t* in, int64_t* out, char* hash);
-extern "C" void dompc_hostemu_run(const dompc::KArgs* A);
-#endif
+using dompc_host::Kernel;
+
+// the host twins of the kernels (dompc_device.hip)
+extern "C" void dompc_hostemu_model_info(const void* args);
+extern "C" void dompc_hostemu_run(const void* args);
+extern "C" void dompc_hostemu_sens_prep(const void* args);
+extern "C" void dompc_hostemu_sens_finish(const void* args);
 
 static thread_local std::string g_create_error;
 
@@ -60,6 +66,9 @@ struct dompc_handle : dompc_host::Context {
   int32_t *s_sn_ok = nullptr, *s_sn_tab = nullptr;
   int32_t sn_cap_batch = 0;
   int64_t sn_cap_S = 0, sn_cap_tab = 0;
+  dompc_host::Module module = nullptr, module_batch = nullptr;      // the general object and its batch-only sibling (build.py: batch_only)
+  Kernel fn_solve, fn_solve_batch;
+  Kernel fn_sens, fn_sens_batch, fn_sens_prep, fn_sens_finish;     // looked up by the first sensitivity call
 #ifndef DOMPC_HOST_EMU
   // native RCCL collective (dlopen'ed): communicator of the sharded problem and its stream
   struct RcclUid { char internal[128]; };
@@ -71,9 +80,6 @@ struct dompc_handle : dompc_host::Context {
   const char* (*nccl_error_string)(int) = nullptr;
   void* rccl_comm = nullptr;
   hipStream_t rccl_stream = nullptr;
-  hipModule_t module = nullptr, module_batch = nullptr;
-  hipFunction_t fn_solve = nullptr, fn_info = nullptr, fn_solve_batch = nullptr;
-  hipFunction_t fn_sens = nullptr, fn_sens_batch = nullptr, fn_sens_prep = nullptr, fn_sens_finish = nullptr;     // looked up by the first sensitivity call
   hipStream_t shard_stream = nullptr;    // lowest priority: never shares a hardware queue with the collective's kernels
 #endif
 };
@@ -111,10 +117,6 @@ static int dev_sync_watchdog(dompc_handle* h, hipStream_t st, int rounds = 1) {
              "unfinished problems return status 6", limit, h->watchdog_s, rounds > 1 ? rounds : 1);
     h->error = msg;
   }
-  return 0;
-}
-static int dev_zero(dompc_handle* h, void* p, size_t bytes, hipStream_t s) {
-  HIPCHK(h, hipMemsetAsync(p, 0, bytes, s));
   return 0;
 }
 #endif
@@ -231,21 +233,16 @@ static int64_t pool_doubles(const dompc_handle* h, int block) {
 }
 
 // `block` threads per workgroup (a multiple of 64): the LDS pool is sized for block/64 wavefronts
-static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* stream_v, void* fn_other = nullptr) {
-#ifndef DOMPC_HOST_EMU
-  hipStream_t st = (hipStream_t)stream_v;          // nullptr = HIP default stream
-  if (dev_zero(h, A.work_counter, sizeof(int32_t), st)) return 1;
+// `stream`: nullptr = HIP default stream.  `other`: another entry of the code object with the same argument block and LDS pool
+// (dompc_sens_kernel) in place of the solver kernel.
+static int launch(dompc_handle* h, dompc::KArgs& A, int grid, int block, void* stream, Kernel other = Kernel()) {
+  if (h->fill(A.work_counter, 0, sizeof(int32_t), stream)) return 1;
   A.pool_doubles = (int32_t)pool_doubles(h, block);
   // (batch launches of the solver with one 64-thread workgroup per problem, not sharded, run the build of the kernels that is compiled for
   //  exactly that shape when it was loaded: build.py batch_only)
-  hipFunction_t fn = (h->fn_solve_batch && (A.mode == 0 || A.mode == 2) && A.wide <= 1 && block == 64 && !h->sharded) ? h->fn_solve_batch : h->fn_solve;
-  if (fn_other) fn = (hipFunction_t)fn_other;      // (another entry of the code object with the same argument block and LDS pool: dompc_sens_kernel)
-  return h->launch(fn, grid, block, (unsigned)(A.pool_doubles * sizeof(double)), st, &A, sizeof(A));
-#else
-  (void)h; (void)grid; (void)block; (void)stream_v; (void)fn_other;
-  dompc_hostemu_run(&A);
-  return 0;
-#endif
+  Kernel k = (h->fn_solve_batch && (A.mode == 0 || A.mode == 2) && A.wide <= 1 && block == 64 && !h->sharded) ? h->fn_solve_batch : h->fn_solve;
+  if (other) k = other;
+  return h->run(k, grid, block, (unsigned)(A.pool_doubles * sizeof(double)), stream, &A, sizeof(A));
 }
 
 extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) {
@@ -265,73 +262,54 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   h->block_auto = d.block_threads <= 0;
   if (const char* be = getenv("DOMPC_BLOCK")) { h->block = atoi(be); h->block_auto = false; }   // tuning aid (64/128/256)
   if (h->block != 64 && h->block != 128 && h->block != 256) { h->error = "block_threads must be 64, 128 or 256"; return fail(1); }
-#ifndef DOMPC_HOST_EMU
-  if (h->open_device("IPM backend")) return fail(1);
-  if (hipHostMalloc((void**)&h->abort_word, 64, hipHostMallocMapped) != hipSuccess) { h->error = "hipHostMalloc failed"; return fail(1); }
-  *h->abort_word = 0;
   if (!d.code_object_path) { h->error = "code_object_path is null"; return fail(1); }
   h->code_path = d.code_object_path;
-  if (h->load_module(h->code_path.c_str(), &h->module, {{"dompc_solve_kernel", &h->fn_solve}, {"dompc_model_info_kernel", &h->fn_info}},
-                     "code object lacks dompc kernels: " + h->code_path))
+  if (const char* wd = getenv("DOMPC_WATCHDOG_S")) h->watchdog_s = atof(wd);
+  h->e_pad = ((d.n_edges + 15) / 16) * 16;
+  // ---- the code object and its model info
+  const int32_t in_h[5] = {d.n_opt_x, d.n_g, d.n_edges, h->e_pad, d.n_nodes};
+  int64_t info[24] = {0};
+  char hash[64] = {0};
+  const char* const info_kernel = "dompc_model_info_kernel";
+  if (h->open("IPM backend", h->code_path.c_str(), &h->module, {{"dompc_solve_kernel", &h->fn_solve, DOMPC_TWIN(dompc_hostemu_run)}},
+              "code object lacks dompc kernels: " + h->code_path, info_kernel, DOMPC_TWIN(dompc_hostemu_model_info), info, hash, in_h, sizeof(in_h)))
     return fail(1);
   {
     // optional sibling `<name>_batch.hsaco` (build.py: batch_only): the same kernels compiled for "one 64-thread workgroup per problem" only
     std::string bp = h->code_path;
     const size_t dot = bp.rfind(".hsaco");
-    if (dot != std::string::npos && !getenv("DOMPC_NO_BATCH_OBJECT")) {
-      bp.insert(dot, "_batch");
-      FILE* f = fopen(bp.c_str(), "rb");
-      if (f) {
-        fclose(f);
-        if (h->load_module(bp.c_str(), &h->module_batch, {{"dompc_solve_kernel", &h->fn_solve_batch}}, "hipModuleLoad failed for " + bp))
-          return fail(1);
+    FILE* f = nullptr;
+    if (dot != std::string::npos && !getenv("DOMPC_NO_BATCH_OBJECT")) f = fopen(bp.insert(dot, "_batch").c_str(), "rb");
+    if (f) {
+      fclose(f);
+      if (h->load(bp.c_str(), &h->module_batch, {{"dompc_solve_kernel", &h->fn_solve_batch, DOMPC_TWIN(dompc_hostemu_run)}}, "hipModuleLoad failed for " + bp))
+        return fail(1);
+      // The sibling is only ever launched with the general object's argument block and workspace layout: it must come from the same
+      // sources and the same model (a handle with a small max_batch rebuilds only the general object after a kernel change;
+      // a stale sibling with another KArgs layout would then be launched for every 64-thread batch).  A sibling that does not match is
+      // not used - the general object runs those launches instead.
+      int64_t info_b[24] = {0};
+      char hash_b[64] = {0};
+      Kernel k_info_b;
+      bool same = h->find(h->module_batch, {info_kernel, &k_info_b, DOMPC_TWIN(dompc_hostemu_model_info)}) &&
+                  !h->query(k_info_b, info_kernel, info_b, hash_b, in_h, sizeof(in_h));
+      for (int i = 0; same && i < 24; ++i) same = info_b[i] == info[i];
+      same = same && strncmp(hash, hash_b, 63) == 0;
+      if (!same) {
+        h->unload(h->module_batch);
+        h->module_batch = nullptr;
+        h->fn_solve_batch = Kernel();
+        h->batch_object_stale = true;
+        h->error.clear();
       }
     }
   }
+#ifndef DOMPC_HOST_EMU
+  if (hipHostMalloc((void**)&h->abort_word, 64, hipHostMallocMapped) != hipSuccess) { h->error = "hipHostMalloc failed"; return fail(1); }
+  *h->abort_word = 0;
 #else
   h->block = 1;
   h->abort_word = (int32_t*)calloc(16, sizeof(int32_t));
-#endif
-  if (const char* wd = getenv("DOMPC_WATCHDOG_S")) h->watchdog_s = atof(wd);
-  h->e_pad = ((d.n_edges + 15) / 16) * 16;
-  // ---- model info from the code object
-  int32_t in_h[5] = {d.n_opt_x, d.n_g, d.n_edges, h->e_pad, d.n_nodes};
-  int64_t info[24] = {0};
-  char hash[64] = {0};
-#ifndef DOMPC_HOST_EMU
-  auto query_info = [&](hipFunction_t fn, int64_t* info_o, char* hash_o) -> int {
-    int32_t* in_d; int64_t* out_d; char* hash_d;
-    if (h->alloc((void**)&in_d, sizeof(in_h)) || h->alloc((void**)&out_d, sizeof(info)) ||
-        h->alloc((void**)&hash_d, sizeof(hash))) return 1;
-    if (h->h2d(in_d, in_h, sizeof(in_h))) return 1;
-    if (dev_zero(h, out_d, sizeof(info), h->stream)) return 1;
-    struct { const int32_t* a; int64_t* b; char* c; } args = {in_d, out_d, hash_d};
-    if (h->launch(fn, 1, 64, 0, h->stream, &args, sizeof(args))) { h->error = "launch of dompc_model_info_kernel failed"; return 1; }
-    if (h->d2h(info_o, out_d, sizeof(info)) || h->d2h(hash_o, hash_d, sizeof(hash)) || h->sync()) return 1;
-    return 0;
-  };
-  if (query_info(h->fn_info, info, hash)) return fail(1);
-  if (h->fn_solve_batch) {
-    // The sibling is only ever launched with the general object's argument block and workspace layout: it must come from the same
-    // sources and the same model (a handle with a small max_batch rebuilds only the general object after a kernel change;
-    // a stale sibling with another KArgs layout would then be launched for every 64-thread batch).  A sibling that does not match is
-    // not used - the general object runs those launches instead.
-    int64_t info_b[24] = {0};
-    char hash_b[64] = {0};
-    hipFunction_t fn_info_b = nullptr;
-    bool same = hipModuleGetFunction(&fn_info_b, h->module_batch, "dompc_model_info_kernel") == hipSuccess && !query_info(fn_info_b, info_b, hash_b);
-    for (int i = 0; same && i < 24; ++i) same = info_b[i] == info[i];
-    same = same && strncmp(hash, hash_b, 63) == 0;
-    if (!same) {
-      h->unload_module(h->module_batch);
-      h->module_batch = nullptr;
-      h->fn_solve_batch = nullptr;
-      h->batch_object_stale = true;
-      h->error.clear();
-    }
-  }
-#else
-  dompc_hostemu_model_info(in_h, info, hash);
 #endif
   const int64_t want[9] = {d.nx, d.nu, d.np, d.ntvp, d.ne, d.ns, d.M == 0 ? 0 : d.deg, d.M == 0 ? 1 : d.ni, d.M};
   if (h->check_info("", info, want, 9, 11, sizeof(dompc::KArgs), hash, d.model_hash)) return fail(1);
@@ -350,7 +328,7 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
 #ifndef DOMPC_HOST_EMU
     const size_t lds = sizeof(double) * (size_t)pool_doubles(h, block);
     int occ = 0, cus = 0;
-    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->fn_solve, block, lds) == hipSuccess &&
+    if (hipModuleOccupancyMaxActiveBlocksPerMultiprocessor(&occ, h->fn_solve.fn, block, lds) == hipSuccess &&
         hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device) == hipSuccess && occ > 0 && cus > 0)
       resident = occ * cus;
     h->occupancy = occ;
@@ -463,11 +441,9 @@ extern "C" int dompc_create(const dompc_problem_desc* desc, dompc_handle** out) 
   A.abort_flag = h->abort_word;
 #endif
   if (h->alloc((void**)&A.ws, sizeof(double) * (size_t)h->ws_stride * h->n_slots)) return fail(1);
-#ifndef DOMPC_HOST_EMU
   if (const char* fill = getenv("DOMPC_WS_FILL")) {      // debugging aid: poison the workspace (uninitialised reads)
-    if (hipMemset(A.ws, atoi(fill), sizeof(double) * (size_t)h->ws_stride * h->n_slots) != hipSuccess) { h->error = "hipMemset failed"; return fail(1); }
+    if (h->fill(A.ws, atoi(fill), sizeof(double) * (size_t)h->ws_stride * h->n_slots, h->stream_ptr())) return fail(1);
   }
-#endif
   if (h->alloc((void**)&A.work_counter, 64)) return fail(1);
   A.lb_sh = A.ub_sh = nullptr;
   {
@@ -665,9 +641,7 @@ extern "C" int dompc_edges_per_wavefront(const dompc_handle* h) { return h ? (in
 extern "C" int dompc_riccati_kind(const dompc_handle* h) { return h ? (int)h->riccati_kind : 0; }
 extern "C" int dompc_batch_object_state(const dompc_handle* h) {
   if (!h) return -1;
-#ifndef DOMPC_HOST_EMU
   if (h->fn_solve_batch) return 1;
-#endif
   return h->batch_object_stale ? 2 : 0;
 }
 
@@ -691,11 +665,9 @@ extern "C" int dompc_solve_batch_device(dompc_handle* h, int32_t B, const double
   }
 #ifndef DOMPC_HOST_EMU
   const dompc_shape s = dompc_launch::solve_shape(shape_facts(h), shape_overrides(), B);
-  if (s.wide > 1) {
-    hipStream_t st = (hipStream_t)stream;
-    HIPCHK(h, hipMemsetAsync(A.wide_bar, 0, sizeof(uint32_t) * dompc::WIDE_BAR_STRIDE * 64, st));
-    HIPCHK(h, hipMemsetAsync(A.wide_flags, 0, sizeof(int32_t) * 8 * 64, st));
-  }
+  if (s.wide > 1 && (h->fill(A.wide_bar, 0, sizeof(uint32_t) * dompc::WIDE_BAR_STRIDE * 64, stream) ||
+                     h->fill(A.wide_flags, 0, sizeof(int32_t) * 8 * 64, stream)))
+    return 1;
 #else
   const dompc_shape s = dompc_launch::batch_shape(shape_facts(h), B);      // (a workgroup is the calling thread: grid and block are ignored)
 #endif
@@ -883,19 +855,17 @@ extern "C" int dompc_sens_batch_device(dompc_handle* h, int32_t B, const double*
   if (h->set_device()) return 1;
   if (h->sharded) { h->error = "dompc_sens_batch_device is not available on a sharded handle"; return 1; }
   const dompc_problem_desc& d = h->d;
-#ifndef DOMPC_HOST_EMU
   if (!h->fn_sens) {
-    hipFunction_t f0 = nullptr, f1 = nullptr, f2 = nullptr;
-    if (hipModuleGetFunction(&f0, h->module, "dompc_sens_kernel") != hipSuccess || hipModuleGetFunction(&f1, h->module, "dompc_sens_prep_kernel") != hipSuccess ||
-        hipModuleGetFunction(&f2, h->module, "dompc_sens_finish_kernel") != hipSuccess) {
+    Kernel f0;
+    if (!h->find(h->module, {"dompc_sens_kernel", &f0, DOMPC_TWIN(dompc_hostemu_run)}) ||
+        !h->find(h->module, {"dompc_sens_prep_kernel", &h->fn_sens_prep, DOMPC_TWIN(dompc_hostemu_sens_prep)}) ||
+        !h->find(h->module, {"dompc_sens_finish_kernel", &h->fn_sens_finish, DOMPC_TWIN(dompc_hostemu_sens_finish)})) {
       h->error = "code object lacks the sensitivity kernels: " + h->code_path;
       return 1;
     }
-    h->fn_sens_prep = f1; h->fn_sens_finish = f2;
-    if (h->fn_solve_batch && hipModuleGetFunction(&h->fn_sens_batch, h->module_batch, "dompc_sens_kernel") != hipSuccess) h->fn_sens_batch = nullptr;
+    if (h->fn_solve_batch && !h->find(h->module_batch, {"dompc_sens_kernel", &h->fn_sens_batch, DOMPC_TWIN(dompc_hostemu_run)})) h->fn_sens_batch = Kernel();
     h->fn_sens = f0;
   }
-#endif
   // work buffer: per point n_rows x (n_opt_p + n_sel) doubles; at most 32 Mi doubles (256 MiB) unless one point needs more
   const int64_t per_point = (int64_t)n_rows * (d.n_opt_p + n_sel);
   const int64_t cap_doubles = (int64_t)32 << 20;
@@ -923,15 +893,10 @@ extern "C" int dompc_sens_batch_device(dompc_handle* h, int32_t B, const double*
     A.sn_S = S + q0 * n_sel * n_cols; A.sn_res = residual_step + q0; A.sn_ok = ok + q0;
     A.batch = nq * n_rows; A.mode = 3; A.wide = 1; A.wide_spread = 0;
     const dompc_shape s = dompc_launch::batch_shape(shape_facts(h), A.batch);
-#ifndef DOMPC_HOST_EMU
-    hipStream_t st = (hipStream_t)stream;
     auto blocks_for = [](int64_t n) { const int64_t g = (n + 255) / 256; return (unsigned)(g < 1 ? 1 : (g > 65536 ? 65536 : g)); };
-    if (h->launch(h->fn_sens_prep, blocks_for((int64_t)A.batch * d.n_opt_p), 256, 0, st, &A, sizeof(A))) return 1;
-    if (launch(h, A, s.grid, s.block, stream, (void*)((s.block == 64 && h->fn_sens_batch) ? h->fn_sens_batch : h->fn_sens))) return 1;
-    if (h->launch(h->fn_sens_finish, blocks_for((int64_t)nq * n_sel * n_cols), 256, 0, st, &A, sizeof(A))) return 1;
-#else
-    if (launch(h, A, s.grid, s.block, stream)) return 1;
-#endif
+    if (h->run(h->fn_sens_prep, blocks_for((int64_t)A.batch * d.n_opt_p), 256, 0, stream, &A, sizeof(A))) return 1;
+    if (launch(h, A, s.grid, s.block, stream, (s.block == 64 && h->fn_sens_batch) ? h->fn_sens_batch : h->fn_sens)) return 1;
+    if (h->run(h->fn_sens_finish, blocks_for((int64_t)nq * n_sel * n_cols), 256, 0, stream, &A, sizeof(A))) return 1;
   }
   return 0;
 }

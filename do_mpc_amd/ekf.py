@@ -101,8 +101,10 @@ class EKF:
         self._P0 = np.eye(model.n_x)
         from .controller import MPCData
         self.data = MPCData(model)
-        self._h = None
-        self._lib = None
+        self._native = _native.Native("ekf", _bind, build.ekf_code_object)
+
+    _lib = property(lambda self: self._native.lib)     # the bound library and the native handle (None before setup / after close)
+    _h = property(lambda self: self._native.h)
 
     # ------------------------------------------------------------------ iterated variables
     def _set_x0(self, v):
@@ -185,35 +187,22 @@ class EKF:
         self.generated_header = self._lower()
         self.model_hash = self.generated_header.rsplit('EKF_MODEL_HASH "', 1)[1].split('"')[0]
         self._check_validity()
-        if _lib_path is None:
-            _lib_path = _native.runtime_library()
-            _code_object = build.ekf_code_object(self.generated_header, self.model_hash)
-        self.code_object = _code_object
-        self._lib = _bind(_lib_path)
+        self._native = _native.Native("ekf", _bind, build.ekf_code_object, _lib_path, _code_object)
+        self.code_object = _code_object = self._native.load(self.generated_header, self.model_hash)
         d = EKFDesc(nx=m.n_x, nu=m.n_u, np=m.n_p, ntvp=m.n_tvp, ny=m.n_y, discrete=1 if m.model_type == "discrete" else 0,
-                    code_object_path=(_code_object or "").encode(), model_hash=self.model_hash.encode(),
+                    code_object_path=_code_object.encode(), model_hash=self.model_hash.encode(),
                     device=self.settings.gpu_index, max_steps=self.settings.max_steps,
                     t_step=float(self.settings.t_step), reltol=float(self.settings.reltol), abstol=float(self.settings.abstol),
                     nz=m.n_z, z_max_iter=int(self.settings.z_max_iter), z_tol=float(self.settings.z_tol))
-        h = C.c_void_p()
-        _native.check(self._lib.dompc_ekf_create(C.byref(d), C.byref(h)), "dompc_ekf_create failed: ", self._lib.dompc_ekf_last_error)
-        self._h = h
+        self._native.create(d)
         self.counter = 0
         self.flags["setup"] = True
 
     def _check(self, rc):
-        _native.check(rc, "dompc_ekf: ", self._lib.dompc_ekf_last_error, self._h)
+        self._native.check(rc)
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.dompc_ekf_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._native.close()
 
     def set_initial_guess(self) -> None:
         assert self.flags["setup"] is True, "EKF was not setup yet. Please call EKF.setup()."

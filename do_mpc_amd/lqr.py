@@ -100,8 +100,8 @@ def _rated(A, B):
     return np.block([[A, B], [np.zeros((nu, A.shape[1])), np.identity(nu)]]), np.block([[B], [np.identity(nu)]])
 
 
-class _Design:
-    """one code object + runtime handle: (nx, nu, mode) without a model, or with the Jacobians of one"""
+class _Design(_native.Native):
+    """one code object + runtime handle (`lib`, `h`): (nx, nu, mode) without a model, or with the Jacobians of one"""
 
     def __init__(self, lqr: "LQR", model: Optional[Model]):
         nx, nu, rate = lqr.model.n_x, lqr.model.n_u, lqr.mode == "inputRatePenalization"
@@ -118,8 +118,7 @@ class _Design:
         self.header = hdr
         self.hash = hdr.rsplit('LQR_MODEL_HASH "', 1)[1].split('"')[0]
         self.model = model
-        self.lib = None
-        self.h = None
+        super().__init__("lqr", _bind, build.lqr_code_object, lqr._emu, "")
         self.key = None                   # the settings the handle was created with
 
 
@@ -138,7 +137,7 @@ class LQR:
         self.settings = LQRSettings()
         self.mode = "standard"
         self.flags = {"setup": False}
-        self._emu = None                  # TEST-ONLY: (header, hash) -> host-emulation library
+        self._emu = None                  # TEST-ONLY: the host-emulation library, or (header, hash) -> host-emulation library
         self._designs = {}
 
     # ------------------------------------------------------------------ iterated variables (model/_iteratedvariables.py)
@@ -234,41 +233,24 @@ class LQR:
             ((float(s.z_tol), int(s.z_max_iter)) if nz else ())
         if d.h is not None and d.key == skey:
             return d
-        if d.h is not None:
-            d.lib.dompc_lqr_destroy(d.h)
-            d.h = None
-        if d.lib is None:
-            d.lib = _bind(self._emu(d.header, d.hash) if self._emu else _native.runtime_library())
-        code_object = "" if self._emu else build.lqr_code_object(d.header, d.hash)
+        code_object = d.load(d.header, d.hash)
         desc = LQRDesc(nx=self.model.n_x, nu=self.model.n_u, n=self.n_design, rate=1 if self.mode == "inputRatePenalization" else 0,
                        has_model=0 if model is None else 1, discrete=0 if cont else 1,
                        np=0 if model is None else model.n_p, ntvp=0 if model is None else model.n_tvp,
                        code_object_path=code_object.encode(), model_hash=d.hash.encode(), device=s.gpu_index, n_horizon=nh,
                        max_iter=int(s.max_iter), t_step=float(s.t_step) if cont else 0.0, tol=float(s.tol), nz=nz,
                        z_max_iter=int(s.z_max_iter) if nz else 0, z_tol=float(s.z_tol) if nz else 0.0)
-        h = C.c_void_p()
-        _native.check(d.lib.dompc_lqr_create(C.byref(desc), C.byref(h)), "dompc_lqr_create failed: ", d.lib.dompc_lqr_last_error)
-        d.h, d.key = h, skey
+        d.create(desc)
+        d.key = skey
         return d
 
     def header(self, model: Optional[Model] = None) -> str:
         """the lowered header of this controller's designs (without a model, or with `model`'s Jacobians)"""
         return _Design(self, model).header
 
-    def _check(self, lib, rc, h):
-        _native.check(rc, "dompc_lqr: ", lib.dompc_lqr_last_error, h)
-
     def close(self):
-        for d in getattr(self, "_designs", {}).values():
-            if d.h is not None:
-                d.lib.dompc_lqr_destroy(d.h)
-                d.h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        for d in self._designs.values():
+            d.close()
 
     def _weights(self, Q, R, P, B):
         """design-size weights (Q~ = diag(Q, R), R~ = delR, P~ = diag(P, R) in inputRatePenalization mode, _lqr.py:484-490) from the
@@ -368,7 +350,7 @@ class LQR:
         else:
             rc = lib.dompc_lqr_design_batch(d.h, Bn, ptr(A), ptr(Bm), ptr(X), ptr(U), ptr(tvp), ptr(p), ptr(Qd), ptr(Rd), ptr(Pd), mask,
                                             ptr(K), ptr(Pout), ptr(Ao), ptr(Bo), ptr(status))
-        self._check(lib, rc, d.h)
+        d.check(rc)
         out = {"K": K, "P": Pout, "iters": (status >> 8) & 0xFFFF, "status": status & 0xFF}
         if model is not None:
             out["A"], out["B"] = Ao, Bo
@@ -386,7 +368,7 @@ class LQR:
         rc = d.lib.dompc_lqr_design_batch_device(
             d.h, int(Bn), *args, int(shared_mask), C.c_void_p(int(K)), C.c_void_p(int(P)), C.c_void_p(int(status) if status else None),
             C.c_void_p(int(stream) if stream else None))
-        self._check(d.lib, rc, d.h)
+        d.check(rc)
 
     def gains_at_device(self, model, Bn, x, u, Q, R, K, P, tvp=0, p=0, P_term=0, A=0, B=0, status=0, shared_mask=0, stream=0, z=0,
                         z_out=0):
@@ -402,7 +384,7 @@ class LQR:
         else:
             rc = d.lib.dompc_lqr_design_batch_device(
                 d.h, int(Bn), *[vp(a) for a in (A, B, x, u, tvp, p, Q, R, P_term)], int(shared_mask), vp(K), vp(P), vp(status), vp(stream))
-        self._check(d.lib, rc, d.h)
+        d.check(rc)
 
     # ------------------------------------------------------------------ setup and runtime
     _Q_user = property(lambda self: getattr(self, "_Q0", getattr(self, "Q", None)))
@@ -441,7 +423,7 @@ class LQR:
         self.settings.check_for_mandatory_settings()
         if _lib_path is not None:
             assert _code_object == "", "a library of its own is the host emulation: _code_object must be \"\""
-            self._emu = _lib_path if callable(_lib_path) else (lambda header, model_hash: _lib_path)
+            self._emu = _lib_path
         if self.mode in ["standard", None]:
             self.mode = "standard"
             self._Q0, self._R0, self._P0 = self.Q, self.R, self.P

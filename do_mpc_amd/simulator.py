@@ -108,8 +108,10 @@ class Simulator:
         from .controller import MPCData                 # per-step records like the reference's simulator.data (simulator.py:833-841)
         self.data = MPCData(model)
         self.flags = {"set_tvp_fun": False, "set_p_fun": False, "setup": False, "first_step": True}
-        self._h = None
-        self._lib = None
+        self._native = _native.Native("plant", _bind, build.plant_code_object)
+
+    _lib = property(lambda self: self._native.lib)     # the bound library and the native handle (None before setup / after close)
+    _h = property(lambda self: self._native.h)
 
     # ------------------------------------------------------------------ iterated variables (model/_iteratedvariables.py)
     def _set_iter(self, name, v):
@@ -178,18 +180,15 @@ class Simulator:
         m = self.model
         self.generated_header = self._lower()
         self.model_hash = self.generated_header.rsplit('PLANT_MODEL_HASH "', 1)[1].split('"')[0]
-        if _lib_path is None:
-            _lib_path = _native.runtime_library()
-            _code_object = build.plant_code_object(self.generated_header, self.model_hash)
-        self._lib = _bind(_lib_path)
+        self._native = _native.Native("plant", _bind, build.plant_code_object, _lib_path, _code_object)
+        _code_object = self._native.load(self.generated_header, self.model_hash)
         d = PlantDesc(nx=m.n_x, nu=m.n_u, np=m.n_p, ntvp=m.n_tvp, nw=m.n_w, nv=m.n_v, ny=m.n_y,
                       discrete=1 if m.model_type == "discrete" else 0,
-                      code_object_path=(_code_object or "").encode(), model_hash=self.model_hash.encode(),
+                      code_object_path=_code_object.encode(), model_hash=self.model_hash.encode(),
                       device=self.settings.gpu_index, max_steps=self.settings.max_steps,
                       t_step=float(self.settings.t_step), reltol=float(self.settings.reltol), abstol=float(self.settings.abstol))
-        h = C.c_void_p()
-        _native.check(self._lib.dompc_plant_create(C.byref(d), C.byref(h)), "dompc_plant_create failed: ", self._lib.dompc_plant_last_error)
-        self._h = h
+        self._native.create(d)
+        h = self._h
         tool = str(self.settings.integration_tool).lower()
         methods = {"cvodes": 0, "idas": 0, "auto": 0, "dopri5": 1, "rk45": 1, "sdirk4": 2, "implicit": 2}
         if tool not in methods:
@@ -205,18 +204,10 @@ class Simulator:
             self._lib.dompc_plant_set_z0(self._h, z.ctypes.data_as(C.c_void_p))
 
     def _check(self, rc):
-        _native.check(rc, "dompc_plant: ", self._lib.dompc_plant_last_error, self._h)
+        self._native.check(rc)
 
     def close(self):
-        if getattr(self, "_h", None):
-            self._lib.dompc_plant_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._native.close()
 
     # ------------------------------------------------------------------ runtime
     def set_initial_guess(self) -> None:

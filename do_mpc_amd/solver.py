@@ -173,16 +173,18 @@ class HipIpmSolver:
         self._ctor = dict(structure=structure, header_text=header_text, model_hash=model_hash, nlpsol_opts=nlpsol_opts,
                           device=device, max_batch=max_batch, n_slots=n_slots, block_threads=block_threads)
         self.shard_capable = bool(shard) or _code_object == ""
-        if _lib_path is None:
-            _lib_path = _native.runtime_library()
-            _code_object = build.model_code_object(header_text, model_hash, shard=bool(shard))
-            sibling = _code_object[:-len(".hsaco")] + "_batch.hsaco"
+
+        def code_objects(header_text, model_hash):
+            general = build.model_code_object(header_text, model_hash, shard=bool(shard))
+            sibling = general[:-len(".hsaco")] + "_batch.hsaco"
             # (a sibling left behind by an earlier handle is refreshed with the general object: the runtime launches whatever lies there)
             if not shard and (int(max_batch) >= 4096 or int(block_threads) == 64 or os.path.exists(sibling)) and not os.environ.get("DOMPC_CODE_OBJECT"):
                 # handles that solve large batches (one wavefront per problem from B = 4096 on) also get the build of the kernels that is
                 # compiled for exactly that launch shape: the runtime finds it next to the general object
                 build.model_code_object(header_text, model_hash, batch_only=True)
-        self._lib = _load(_lib_path)
+            return general
+        self._native = _native.Native("", _load, code_objects, _lib_path, _code_object)
+        _code_object = self._native.load(header_text, model_hash)
         self._keep = []
         d = ProblemDesc()
         for k, v in dict(nx=ps.nx, nu=ps.nu, np=ps.np_, ntvp=ps.ntvp, ne=ps.ne, ns=ps.ns, deg=ps.deg, ni=ps.ni,
@@ -199,8 +201,8 @@ class HipIpmSolver:
         om = np.ascontiguousarray(ps.tables["edge_omega"], dtype=np.float64)
         self._keep.append(om)
         d.edge_omega = om.ctypes.data_as(_f64p)
-        d.code_object_path = (_code_object or "").encode()
-        self.code_object_path = _code_object or ""          # the gfx950 code object of this problem class (named by the model hash)
+        d.code_object_path = _code_object.encode()
+        self.code_object_path = _code_object          # the gfx950 code object of this problem class (named by the model hash)
         d.model_hash = model_hash.encode()
         d.device, d.max_batch, d.n_slots, d.block_threads = device, max_batch, n_slots, block_threads
         self._lib.dompc_default_options(C.byref(d.opts))
@@ -222,9 +224,8 @@ class HipIpmSolver:
             else:
                 self.ignored_options.append(k)     # print levels, linear solver, ... : no meaning here
         self.options = d.opts
-        h = C.c_void_p()
-        _native.check(self._lib.dompc_create(C.byref(d), C.byref(h)), "dompc_create failed: ", self._lib.dompc_last_error)
-        self._h = h
+        self._native.create(d)
+        h = self._h
         # 0: no launch-shape-specific sibling code object, 1: loaded, 2: found but stale (other sources / model) and therefore not used
         self.batch_object_state = int(self._lib.dompc_batch_object_state(h))
         self.edges_per_wavefront = int(self._lib.dompc_edges_per_wavefront(h))      # 4: quad sweep (csrc/dompc_quad.h)
@@ -238,19 +239,14 @@ class HipIpmSolver:
         self._host_emulation = _code_object == ""
         self._shard = None
 
-    def close(self):
-        if getattr(self, "_h", None):
-            self._lib.dompc_destroy(self._h)
-            self._h = None
+    _lib = property(lambda self: self._native.lib)     # the bound library and the native handle (None after close)
+    _h = property(lambda self: self._native.h)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+    def close(self):
+        self._native.close()
 
     def _check(self, rc):
-        _native.check(rc, "dompc: ", self._lib.dompc_last_error, self._h)
+        self._native.check(rc)
 
     # ------------------------------------------------------------------ nlpsol-like call
     def __call__(self, x0, lbx, ubx, lbg, ubg, p, lam_x0=None, lam_g0=None) -> dict:

@@ -7,11 +7,12 @@
 #include <math.h>
 #include <stdint.h>
 #include "dompc_lqr_args.h"
-extern "C" void dompc_lqr_hostemu_info(int64_t* out, char* hash);
-extern "C" void dompc_lqr_hostemu_run(const dompc_lqrk::Args* A);
+extern "C" void dompc_lqr_hostemu_info(const void* args);      // {int64_t* info, char* hash}
+extern "C" void dompc_lqr_hostemu_run(const void* args);       // dompc_lqrk::Args
 int main() {
   int64_t info[16] = {0}; char hash[64] = {0};
-  dompc_lqr_hostemu_info(info, hash);
+  void* const info_args[2] = {info, hash};
+  dompc_lqr_hostemu_info(info_args);
   const int nx = info[0], nu = info[1], n = info[2], nz = info[9], B = 7;
   printf("nx %d nu %d n %d nz %d args %lld (sizeof %zu)\n", nx, nu, n, nz, (long long)info[8], sizeof(dompc_lqrk::Args));
   if (info[8] != (int64_t)sizeof(dompc_lqrk::Args)) return 2;
