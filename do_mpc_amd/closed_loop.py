@@ -17,7 +17,7 @@ The parts, each written once, and the six loops composed of them:
   BatchClosedLoop       _ControllerSide -> _PlantSide, state feedback
   BatchClosedLoopMHE    _ControllerSide -> _PlantSide (measuring) -> moving horizon estimator (its chain problem lives in the class)
   BatchClosedLoopEKF    _ControllerSide -> _PlantSide (measuring, noise) -> extended Kalman filter (its buffers live in the class)
-  BatchClosedLoopLQR    gain (a torch expression) -> _PlantSide; run = _record_run
+  BatchClosedLoopLQR    gain (a torch expression) -> _PlantSide; run = _record_run, or fused: the gain as the law of the plant rollout
   BatchClosedLoopAMPC   network kernel -> _PlantSide; run = _record_run
   BatchClosedLoopASMPC  _ControllerSide (solved through ASMPC.solve_device, with multipliers) -> affine law -> _PlantSide; events, rollout
 
@@ -104,11 +104,15 @@ class _PlantSide:
             if m.n_tvp:
                 self.tvp.copy_(self.dv.to_dev(tv[0]))
 
-    def step(self, U, stream, shared_mask: int = 2 | 4 | 8 | 16) -> None:
+    def step(self, U, stream, shared_mask: int = 2 | 4 | 8 | 16, W=None) -> None:
         """one plant step of all loops with the inputs U [B][nu]; X is the new state afterwards.  shared_mask: _tvp and _p are one row
-        for the batch (bits 1, 2), and so are the noise inputs (bits 3, 4) unless the loop clears their bits"""
+        for the batch (bits 1, 2), and so are the noise inputs (bits 3, 4) unless the loop clears their bits.  W: [B][nw] process
+        noise of this step, one row per loop (bit 3 is cleared for it), or None"""
+        if W is not None:
+            shared_mask &= ~8
         self.sim.step_batch_device(self.B, self.X.data_ptr(), U.data_ptr(), self.tvp.data_ptr(), self.p.data_ptr(), self.Xn.data_ptr(),
                                    self.Y.data_ptr() if self.Y is not None else 0, self.pstat.data_ptr(),
+                                   w=W.data_ptr() if W is not None else 0,
                                    v=self.V.data_ptr() if self.V is not None else 0, shared_mask=shared_mask, stream=stream)
         self.X, self.Xn = self.Xn, self.X
 
@@ -429,6 +433,7 @@ class BatchClosedLoopLQR:
     (/root/reference/examples/lqr_examples/CSTR_lqr/main.py:75-78).  State feedback: the plant's measurement must be its state.
     X0: [B][nx]; K: None (lqr.K for every loop) or [B][nu][n], e.g. the schedule of LQR.gains_at; XSS / USS: None (the set-point of
     set_setpoint), one set-point or one per loop, of the model's size; U_prev0: [B][nu] (default 0, like lqr.u0 after reset).
+    `run(n, fused=True)` runs the steps inside the general plant rollout instead, the gain as its law: one launch per chunk of steps.
     device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests)."""
 
     def __init__(self, lqr, simulator, X0, K=None, XSS=None, USS=None, device=0, U_prev0=None):
@@ -453,19 +458,110 @@ class BatchClosedLoopLQR:
         self.U = t(np.zeros((B, m.n_u)) if U_prev0 is None else np.asarray(U_prev0, float).reshape(B, m.n_u))
         self.k = 0
 
-    def step(self) -> dict:
-        """one control step of all B loops; returns the inputs applied, the new states and the plant status"""
+    def _noise(self, w):
+        """process noise of one step or of several, host array or tensor -> device tensor [...][B][nw] (None stays None)"""
+        if w is None:
+            return None
+        nw = self.sim.model.n_w
+        assert nw > 0, "process noise for a plant whose model has none (set_rhs(..., process_noise=True))"
+        w = w if type(w).__module__.startswith("torch") else self.dv.to_dev(w)
+        return w.to(self.dv.dev).reshape(-1, self.B, nw).contiguous()
+
+    def step(self, w=None) -> dict:
+        """one control step of all B loops; returns the inputs applied, the new states and the plant status.  w: [B][nw], the process
+        noise of this step (default: none)"""
         plant = self.plant
         plant.refresh(self.k)
+        w = self._noise(w)
         self.U = self.lqr.make_step_batch(plant.X, K=self.K, XSS=self.xss, USS=self.uss, U_prev=self.U).contiguous()
-        plant.step(self.U, self.dv.stream())
+        plant.step(self.U, self.dv.stream(), W=None if w is None else w[0])
         self.k += 1
         self.dv.sync()
         return {"u0": self.U.cpu().numpy(), "x": plant.X.cpu().numpy(), "plant_status": plant.status()[0]}
 
-    def run(self, n: int) -> dict:
-        """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step"""
-        return _record_run(self, n)
+    def _law(self):
+        """The loop's gain as a law of the general plant rollout, formed once: (record, G, up_ref, tensors that own the memory).  A
+        shared gain or set-point is expanded to the batch (ld = B); x_scale = 1, max_dx = inf, no clip.  Standard mode: x_ref = xss,
+        u_ref = uss, M = K.  inputRatePenalization mode, u = u_prev + Kx (x - xss) + Ku (u_prev - uss) with K = [Kx Ku]: x_ref = xss,
+        u_ref = up_ref = uss, M = Kx, G = I + Ku."""
+        if getattr(self, "_law_rec", None) is None:
+            from .asmpc import AffineLaw
+            torch, B, m = self.dv.torch, self.B, self.sim.model
+            nx, nu = m.n_x, m.n_u
+            K = self.K.expand(B, nu, self.K.shape[2])
+            keep = {"x_ref": self.xss.expand(B, nx).t().contiguous(), "u_ref": self.uss.expand(B, nu).t().contiguous(),
+                    "M": K[:, :, :nx].permute(1, 2, 0).contiguous(), "x_scale": self.dv.to_dev(np.ones(nx))}
+            G = None
+            if self.lqr.mode == "inputRatePenalization":
+                eye = torch.eye(nu, dtype=torch.float64, device=self.dv.dev)
+                G = keep["G"] = (eye[None] + K[:, :, nx:]).permute(1, 2, 0).contiguous()
+            rec = AffineLaw(x_ref=keep["x_ref"].data_ptr(), u_ref=keep["u_ref"].data_ptr(), M=keep["M"].data_ptr(), flags=None, lb=None,
+                            ub=None, x_scale=keep["x_scale"].data_ptr(), ld=B, max_dx=float("inf"), clip=0, pad=0)
+            self._law_rec = (rec, G, keep["u_ref"] if G is not None else None, keep)
+        return self._law_rec[:3]
+
+    def _rollout(self, K, W):
+        """K control steps in one launch, one synchronisation and one copy to the host; W: [K][B][nw] on the device, or None.
+        Returns (x [K][B][nx], u [K][B][nu], plant status [K][B])"""
+        dv, plant, m, B = self.dv, self.plant, self.sim.model, self.B
+        torch = dv.torch
+        nX, nU = (K + 1) * B * m.n_x, K * B * m.n_u
+        buf = dv.empty(nX + nU + (K * B + 1) // 2)             # states, inputs and the status words behind one another: one copy
+        Xt, Ut = buf[:nX].view(K + 1, B, m.n_x), buf[nX:nX + nU].view(K, B, m.n_u)
+        pst = buf[nX + nU:].view(torch.int32)[:K * B].view(K, B)
+        tv, pp = (dv.to_dev(a) for a in plant.rows(self.k, K))
+        Xt[0].copy_(plant.X)
+        law, G, up_ref = self._law()
+        self.sim.rollout_device(B, K, Xt.data_ptr(), Ut.data_ptr(), law=law, G=G.data_ptr() if G is not None else 0,
+                                up_ref=up_ref.data_ptr() if G is not None else 0, U_prev0=self.U.data_ptr() if G is not None else 0,
+                                W_traj=W.data_ptr() if W is not None else 0, tvp_rows=tv.data_ptr() if m.n_tvp else 0,
+                                p_rows=pp.data_ptr() if m.n_p else 0, plant_status=pst.data_ptr(), stream=dv.stream())
+        plant.X.copy_(Xt[K])
+        self.U = Ut[K - 1].clone()
+        plant.pstat.copy_(pst[K - 1])
+        self.k += K
+        dv.sync()
+        host = buf.cpu().numpy()
+        st = host[nX + nU:].view(np.int32)[:K * B].reshape(K, B)
+        return host[B * m.n_x:nX].reshape(K, B, m.n_x), host[nX:nX + nU].reshape(K, B, m.n_u), st & 1
+
+    def run(self, n: int, fused: bool = False, chunk=None, W=None) -> dict:
+        """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step.
+        W: process noise of the plant, [n][B][nw] or a callable k -> [B][nw] (k = 0 .. n - 1: the step of this run).
+        fused=True: the steps run as ceil(n / chunk) launches of the general plant rollout (`Simulator.rollout_device`) with the gain as
+        its law (`_law`), one synchronisation and one copy to the host after each launch - instead of a handful of launches, a
+        synchronisation and three copies per step.  chunk=None: one launch.  Device memory per launch: (chunk + 1) B nx + chunk B nu
+        float64 and chunk B int32 for the records, chunk B nw float64 more with noise, chunk rows of the plant's `_tvp` and `_p`.  The
+        inputs differ from those of the step-wise path by the order of the additions in K (x - xss) (an fma chain here, a torch
+        product there).  `k`, the states and the inputs applied last are left where n calls of step() leave them: the two can be
+        mixed.  Plants with algebraic states are served."""
+        n = int(n)
+        m = self.sim.model
+        if W is not None and not callable(W):
+            W = self._noise(W)
+            assert W.shape[0] == n, f"W must hold the noise of {n} steps"
+
+        def noise(i, K):
+            """W of the steps i .. i + K - 1 on the device: [K][B][nw], or None"""
+            if W is None:
+                return None
+            return self._noise(np.stack([np.asarray(W(i + j), float) for j in range(K)])) if callable(W) else W[i:i + K]
+        if not fused and W is None:
+            return _record_run(self, n)
+        xs, us, st = [self.plant.X.cpu().numpy().copy()[None]], [], []
+        i = 0
+        while i < n:
+            if fused:
+                K = n - i if chunk is None else min(int(chunk), n - i)
+                x, u, s = self._rollout(K, noise(i, K))
+            else:
+                K = 1
+                r = self.step(w=noise(i, 1)[0])
+                x, u, s = r["x"].copy()[None], r["u0"].copy()[None], r["plant_status"][None]
+            xs.append(x); us.append(u); st.append(s)
+            i += K
+        cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dtype=dt)      # noqa: E731
+        return {"x": np.concatenate(xs), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(st, (0, self.B), np.int32)}
 
 
 class BatchClosedLoopAMPC:

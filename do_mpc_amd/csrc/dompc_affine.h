@@ -1,6 +1,6 @@
 // dompc_affine.h - the affine state feedback  u = sat(u_ref + M (x - x_ref))  of one loop, the law record it reads, and nothing else.
-// Two kernels include it: the law step of dompc_asmpc.hip (one launch per control step) and the plant rollout of dompc_plant.hip
-// (K control steps in one launch).  Both have to give the same bits, on the device and on the host, so the arithmetic is spelled
+// Two kernel sources include it: the law step of dompc_asmpc.hip (one launch per control step) and the plant rollouts of dompc_plant.hip
+// (K control steps in one launch; the general one through step_prev below).  All have to give the same bits, on the device and on the host, so the arithmetic is spelled
 // out: one subtraction per state, then u_i = fma(M[i][k], x_k - x_ref_k, u_i) for k ASCENDING from u_i = u_ref_i, then the clip as
 // two comparisons (not fmin / fmax: a NaN stays a NaN in its own row).  Nothing here may be rewritten as a sum the compiler is free
 // to reassociate or contract differently in the two kernels.
@@ -51,6 +51,41 @@ DOMPC_AFFINE_FN int step(const Law& L, int64_t b, const double* x, double* u) {
     double ui = L.u_ref[i * L.ld + b];
     DOMPC_AFFINE_UNROLL
     for (int k = 0; k < NX; ++k) ui = fma(L.M[((int64_t)i * NX + k) * L.ld + b], dx[k], ui);
+    if (L.clip) {
+      if (ui < L.lb[i]) { ui = L.lb[i]; st |= 4; }
+      if (ui > L.ub[i]) { ui = L.ub[i]; st |= 4; }
+    }
+    u[i] = ui;
+  }
+  return st;
+}
+
+// The law with a previous-input term (the general plant rollout of dompc_plant.hip):
+//   u = sat(u_ref + M (x - x_ref) + G (u_prev - up_ref)),   G [nu][nu][ld], up_ref [nu][ld] (it may alias u_ref), u_prev [NU].
+// dx, `far` and the M chain are those of step(); with G non-null the SAME chain goes on, u_i = fma(G[i][j], u_prev_j - up_ref_j, u_i)
+// for j ASCENDING, then the clip.  With G == nullptr this gives the bits of step() (nothing of u_prev or up_ref is read).
+// u may not alias u_prev.
+template <int NX, int NU>
+DOMPC_AFFINE_FN int step_prev(const Law& L, const double* G, const double* up_ref, int64_t b, const double* x, const double* u_prev,
+                              double* u) {
+  int st = L.flags ? (L.flags[b] & 3) : 0;
+  double dx[NX];
+  bool far = false;
+  DOMPC_AFFINE_UNROLL
+  for (int k = 0; k < NX; ++k) {
+    dx[k] = x[k] - L.x_ref[k * L.ld + b];
+    far = far || fabs(dx[k] / L.x_scale[k]) > L.max_dx;
+  }
+  if (far) st |= 8;
+  DOMPC_AFFINE_UNROLL
+  for (int i = 0; i < NU; ++i) {
+    double ui = L.u_ref[i * L.ld + b];
+    DOMPC_AFFINE_UNROLL
+    for (int k = 0; k < NX; ++k) ui = fma(L.M[((int64_t)i * NX + k) * L.ld + b], dx[k], ui);
+    if (G) {
+      DOMPC_AFFINE_UNROLL
+      for (int j = 0; j < NU; ++j) ui = fma(G[((int64_t)i * NU + j) * L.ld + b], u_prev[j] - up_ref[j * L.ld + b], ui);
+    }
     if (L.clip) {
       if (ui < L.lb[i]) { ui = L.lb[i]; st |= 4; }
       if (ui > L.ub[i]) { ui = L.ub[i]; st |= 4; }

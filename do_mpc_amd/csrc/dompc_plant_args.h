@@ -28,4 +28,19 @@ struct RolloutArgs {
   int32_t *plant_status, *law_status;        // [K][B] each (may be null)
   int32_t K, pad;
 };
+// The general rollout (dompc_plant_loop_kernel), for every plant: K control steps of one loop per thread, with the inputs from a law
+// (has_law; optionally with a previous-input term G) or given in U_traj, noise, measurements, parameters per loop and algebraic
+// states.  Per step k: u = law(X_traj[k], u_prev) -> U_traj[k] (or U_traj[k] is read), then the plant step of `plant` from X_traj[k]
+// with U_traj[k], W_traj[k], V_traj[k] to X_traj[k + 1], Y_traj[k] and - from plant.z_guess - Z_traj[k].
+struct LoopArgs {
+  Args plant;                                // batch, method, tolerances, limits, z_guess; the per-step fields are set per step
+  dompc_affine::Law law;                     // read only with has_law
+  const double *G, *up_ref, *U_prev0;        // [nu][nu][ld], [nu][ld], [B][nu]: the previous-input term of the law (G null: none)
+  double *X_traj, *U_traj;                   // [K + 1][B][nx] (row 0: the start, in), [K][B][nu] (out with a law, in without)
+  const double *W_traj, *V_traj;             // [K][B][nw], [K][B][nv] (either may be null: zeros)
+  double *Y_traj, *Z_traj;                   // [K][B][ny], [K][B][nz] (either may be null): measurement and algebraic states at X_traj[k + 1]
+  const double *tvp_rows, *p_rows, *p_loops; // [K][ntvp], and either [K][np] shared by the batch or [B][np] per loop, constant over the steps
+  int32_t *plant_status, *law_status;        // [K][B] each (may be null)
+  int32_t K, has_law;
+};
 }  // namespace dompc_plantk

@@ -11,6 +11,7 @@
 extern "C" void dompc_plant_hostemu_info(const void* args);
 extern "C" void dompc_plant_hostemu_run(const void* args);
 extern "C" void dompc_plant_hostemu_rollout(const void* args);
+extern "C" void dompc_plant_hostemu_loop(const void* args);
 
 static_assert(sizeof(dompc_affine_law) == sizeof(dompc_affine::Law), "dompc_affine_law of the C ABI and the kernels' law record");
 
@@ -29,7 +30,7 @@ struct dompc_plant : dompc_host::Context {
   bool z_carry_host = false;            // host entry (dompc_plant_step_batch): rows of consecutive calls are the same trajectories (dompc_plant_set_z_carry)
   bool z_reseed_next = false;
   dompc_host::Module module = nullptr;
-  dompc_host::Kernel fn, fn_rollout;
+  dompc_host::Kernel fn, fn_rollout, fn_loop;
 };
 
 extern "C" const char* dompc_plant_last_error(const dompc_plant* h) { return h ? h->error.c_str() : g_plant_create_error.c_str(); }
@@ -59,6 +60,9 @@ extern "C" int dompc_plant_create(const dompc_plant_desc* desc, dompc_plant** ou
     if (info[10] != (int64_t)sizeof(dompc_plantk::RolloutArgs)) { h->error = "plant rollout argument layout mismatch between runtime and code object"; return fail(); }
     if (!h->find(h->module, {"dompc_plant_rollout_kernel", &h->fn_rollout, DOMPC_TWIN(dompc_plant_hostemu_rollout)})) { h->error = "code object lacks the plant kernels"; return fail(); }
   }
+  // the general rollout: every plant has it
+  if (info[11] != (int64_t)sizeof(dompc_plantk::LoopArgs)) { h->error = "plant loop argument layout mismatch between runtime and code object"; return fail(); }
+  if (!h->find(h->module, {"dompc_plant_loop_kernel", &h->fn_loop, DOMPC_TWIN(dompc_plant_hostemu_loop)})) { h->error = "code object lacks the plant kernels"; return fail(); }
   h->d.code_object_path = nullptr; h->d.model_hash = nullptr;
   h->nz = (int32_t)info[9];
   h->z0.assign((size_t)(h->nz > 0 ? h->nz : 0), 0.0);
@@ -195,4 +199,39 @@ extern "C" int dompc_plant_rollout_affine_device(dompc_plant* h, int32_t B, int3
   R.X_traj = X_traj; R.U_traj = U_traj; R.tvp_rows = tvp_rows; R.p_rows = p_rows;
   R.plant_status = plant_status; R.law_status = law_status; R.K = K;
   return h->run(h->fn_rollout, (unsigned)((B + 63) / 64), 64, 0, stream, &R, sizeof(R));
+}
+
+extern "C" int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, const dompc_plant_rollout_desc* r, void* stream) {
+  if (!h) return 1;
+  if (B <= 0 || K <= 0) return 0;
+  const dompc_plant_desc& d = h->d;
+  const char* me = "dompc_plant_rollout_device: ";
+  auto refuse = [&](const char* what) { h->error = std::string(me) + what; return 1; };
+  if (!r) return refuse("null description");
+  if (!r->X_traj) return refuse("X_traj is null");
+  if (d.nu && !r->U_traj) return refuse("U_traj is null");
+  if (d.np && !r->p_rows && !r->p_loops) return refuse("the plant has parameters: p_rows or p_loops is needed");
+  if (r->p_rows && r->p_loops) return refuse("p_rows and p_loops are both given (one of them)");
+  if (d.ntvp && !r->tvp_rows) return refuse("the plant has time-varying parameters: tvp_rows is needed");
+  const dompc_affine_law* law = r->law;
+  if (law && d.nu <= 0) return refuse("a law on a plant without inputs");
+  if (law && (!law->x_ref || !law->u_ref || !law->M || !law->x_scale || (law->clip && (!law->lb || !law->ub)) || law->ld < B))
+    return refuse("incomplete law record (x_ref, u_ref, M, x_scale, with clip lb and ub; ld >= B)");
+  if (r->G && !law) return refuse("G without a law");
+  if (r->G && !r->up_ref) return refuse("G without up_ref");
+  if (r->G && !r->U_prev0) return refuse("G without U_prev0");
+  if (r->Z_traj && h->nz <= 0) return refuse("Z_traj on a plant without algebraic states");
+  if (h->set_device()) return 1;
+  // the per-loop Newton starts of the algebraic states: as dompc_plant_step_batch_device treats them, or seeded from z0 first
+  if (ensure_z(h, B, r->reseed_z != 0 || h->z_reseed_next)) return 1;
+  h->z_reseed_next = false;
+  dompc_plantk::LoopArgs R;
+  memset(&R, 0, sizeof(R));
+  fill_args(h, R.plant, B, 0);
+  if (law) { memcpy(&R.law, law, sizeof(R.law)); R.has_law = 1; }
+  R.G = law ? r->G : nullptr; R.up_ref = r->up_ref; R.U_prev0 = r->U_prev0;
+  R.X_traj = r->X_traj; R.U_traj = r->U_traj; R.W_traj = r->W_traj; R.V_traj = r->V_traj; R.Y_traj = r->Y_traj; R.Z_traj = r->Z_traj;
+  R.tvp_rows = r->tvp_rows; R.p_rows = r->p_rows; R.p_loops = r->p_loops;
+  R.plant_status = r->plant_status; R.law_status = r->law_status; R.K = K;
+  return h->run(h->fn_loop, (unsigned)((B + 63) / 64), 64, 0, stream, &R, sizeof(R));
 }

@@ -38,8 +38,9 @@ JACKET_CAPACITY = 5 * 2             # mass times heat capacity of the jacket
 K_A = 14.448                        # heat transfer to the jacket [kJ/(min K)]
 
 
-def build_model() -> Model:
-    """the nonlinear plant: mass balances of A and B, energy balances of reactor and jacket"""
+def build_model(process_noise: bool = False) -> Model:
+    """the nonlinear plant: mass balances of A and B, energy balances of reactor and jacket; process_noise: additive noise on every
+    right-hand side (Monte-Carlo studies of the closed loop)"""
     mdl = Model("continuous")
     ca, cb, t_r, t_j = (mdl.set_variable("_x", name, (1, 1)) for name in ("C_a", "C_b", "T_R", "T_J"))
     feed = mdl.set_variable("_u", "F")
@@ -50,10 +51,10 @@ def build_model() -> Model:
     dilution = lambda: feed / VOLUME      # noqa: E731  (one node per use, like the template: the lowered text is compared)
     to_jacket = lambda: t_r - t_j      # noqa: E731
     reaction_heat = DH_AB * (-rate_ab) + DH_BC * (-rate_bc)
-    mdl.set_rhs("C_a", dilution() * (CA_FEED - ca) - rate_ab)
-    mdl.set_rhs("C_b", -dilution() * cb + rate_ab - rate_bc)
-    mdl.set_rhs("T_R", dilution() * (T_FEED - t_r) - (K_A / (RHO_CP * VOLUME)) * to_jacket() + (1 / RHO_CP) * reaction_heat)
-    mdl.set_rhs("T_J", (1 / JACKET_CAPACITY) * (-cooling + K_A * to_jacket()))
+    mdl.set_rhs("C_a", dilution() * (CA_FEED - ca) - rate_ab, process_noise=process_noise)
+    mdl.set_rhs("C_b", -dilution() * cb + rate_ab - rate_bc, process_noise=process_noise)
+    mdl.set_rhs("T_R", dilution() * (T_FEED - t_r) - (K_A / (RHO_CP * VOLUME)) * to_jacket() + (1 / RHO_CP) * reaction_heat, process_noise=process_noise)
+    mdl.set_rhs("T_J", (1 / JACKET_CAPACITY) * (-cooling + K_A * to_jacket()), process_noise=process_noise)
     mdl.setup()
     return mdl
 

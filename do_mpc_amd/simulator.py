@@ -49,6 +49,13 @@ class PlantDesc(C.Structure):
                 ("t_step", C.c_double), ("reltol", C.c_double), ("abstol", C.c_double)]
 
 
+class RolloutDesc(C.Structure):
+    """dompc_plant_rollout_desc of include/dompc_ipm.h"""
+    _fields_ = [(n, C.c_void_p) for n in ("law", "G", "up_ref", "U_prev0", "X_traj", "U_traj", "W_traj", "V_traj", "Y_traj", "Z_traj",
+                                          "tvp_rows", "p_rows", "p_loops", "plant_status", "law_status")] + \
+               [("reseed_z", C.c_int32), ("pad", C.c_int32)]
+
+
 def _bind(lib_path: str) -> C.CDLL:
     lib = C.CDLL(lib_path)
     vp = C.c_void_p
@@ -71,6 +78,8 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_plant_num_alg_states.restype = C.c_int32
     lib.dompc_plant_rollout_affine_device.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 8
     lib.dompc_plant_rollout_affine_device.restype = C.c_int
+    lib.dompc_plant_rollout_device.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(RolloutDesc), vp]
+    lib.dompc_plant_rollout_device.restype = C.c_int
     return lib
 
 
@@ -288,6 +297,86 @@ class Simulator:
         rc = self._lib.dompc_plant_rollout_affine_device(self._h, int(B), int(K), C.c_void_p(C.addressof(law)), *ptrs,
                                                          C.c_void_p(int(stream) if stream else None))
         self._check(rc)
+
+    def rollout_device(self, B, K, X_traj, U_traj, law=None, G=0, up_ref=0, U_prev0=0, W_traj=0, V_traj=0, Y_traj=0, Z_traj=0,
+                       tvp_rows=0, p_rows=0, p_loops=0, plant_status=0, law_status=0, reseed_z=False, stream=0):
+        """K control steps of B loops in ONE launch, for every plant (`dompc_plant_rollout_device`, include/dompc_ipm.h).  Raw device
+        addresses, asynchronous on `stream`.  X_traj [K + 1][B][nx] with row 0 filled; per step k the plant step of `step_batch_device`
+        from X_traj[k] to X_traj[k + 1] with
+          the input   `law` (a ctypes `dompc_affine_law` record) at X_traj[k], written to U_traj[k] [K][B][nu], its status to law_status
+                      [K][B]; with G [nu][nu][ld] the law has a previous-input term, u = sat(u_ref + M (x - x_ref) + G (u_prev - up_ref)),
+                      up_ref [nu][ld], u_prev = U_prev0 [B][nu] at k = 0 and the (clipped) input of step k - 1 afterwards.  Without a law
+                      U_traj[k] is read: an open-loop simulation;
+          parameters  tvp_rows [K][n_tvp] shared by the batch; p_rows [K][n_p] shared by the batch OR p_loops [B][n_p], one row per loop;
+          noise       W_traj [K][B][nw], V_traj [K][B][nv] (0: none);
+          records     Y_traj [K][B][ny] (the measurement at X_traj[k + 1]), Z_traj [K][B][nz] (the algebraic states there), plant_status
+                      [K][B] (0: not kept).
+        The Newton starts of the algebraic states are carried from step to step and from call to call like those of
+        `step_batch_device`; reseed_z: they start from `simulator.z0`.  A loop whose plant step fails goes on from the state it reached."""
+        r = RolloutDesc()
+        r.law = C.addressof(law) if law is not None else None
+        for name, a in (("G", G), ("up_ref", up_ref), ("U_prev0", U_prev0), ("X_traj", X_traj), ("U_traj", U_traj), ("W_traj", W_traj),
+                        ("V_traj", V_traj), ("Y_traj", Y_traj), ("Z_traj", Z_traj), ("tvp_rows", tvp_rows), ("p_rows", p_rows),
+                        ("p_loops", p_loops), ("plant_status", plant_status), ("law_status", law_status)):
+            setattr(r, name, int(a) if a else None)
+        r.reseed_z = 1 if reseed_z else 0
+        rc = self._lib.dompc_plant_rollout_device(self._h, int(B), int(K), C.byref(r), C.c_void_p(int(stream) if stream else None))
+        self._check(rc)
+
+    def simulate_batch(self, X0, U, W=None, V=None, P=None, carry_z: bool = False) -> dict:
+        """Open-loop simulation of B plants over K control steps in one launch (`rollout_device`).  X0: [B][nx]; U: [K][B][nu], or
+        [K][nu] shared by the batch; W, V: process and measurement noise, likewise (None: none); P: [B][np], one parameter row per plant,
+        constant over the steps (default: p_fun at the K times t0 + k t_step, shared by the batch); `_tvp`: tvp_fun at those times.
+        Returns {'x' [K + 1][B][nx] (with the start), 'y' [K][B][ny], 'z' [K][B][nz], 'status', 'n_steps' [K][B]} (status bits as
+        `make_step_batch`).  Like `make_step_batch` it does not touch x0, t0 or data.  DAE plants: the Newton iteration of every plant
+        starts from `simulator.z0` - unless `carry_z`, which says that row b continues the trajectory of row b of the previous call."""
+        assert self.flags["setup"], "Simulator is not setup. Call simulator.setup() first."
+        import torch
+        m = self.model
+        X0 = np.ascontiguousarray(np.asarray(X0, dtype=np.float64)).reshape(-1, m.n_x)
+        B = X0.shape[0]
+        K = int(np.asarray(U).shape[0])
+
+        def rows(a, n, name):
+            """[K][B][n] from [K][B][n] or [K][n]"""
+            a = np.asarray(a, dtype=np.float64)
+            if a.shape == (K, n):
+                a = np.broadcast_to(a[:, None, :], (K, B, n))
+            if a.shape != (K, B, n):
+                raise ValueError(f"Simulator.simulate_batch: {name} must have the shape ({K}, {B}, {n}) or ({K}, {n}), got {a.shape}")
+            return np.ascontiguousarray(a)
+
+        # (the host emulation of the tests: "device" memory is host memory)
+        dev = torch.device("cpu") if self._native._lib_path is not None else torch.device("cuda", self.settings.gpu_index)
+        t = lambda a: torch.tensor(a, dtype=torch.float64, device=dev)      # noqa: E731
+        e = lambda *shape, dt=torch.float64: torch.zeros(shape, dtype=dt, device=dev)      # noqa: E731
+        t0, dt = float(self._t0[0]), float(self.settings.t_step)
+        ts = [t0 + k * dt for k in range(K)]
+        Ut = t(rows(U, m.n_u, "U"))
+        Wt = t(rows(W, m.n_w, "W")) if W is not None and m.n_w else None
+        Vt = t(rows(V, m.n_v, "V")) if V is not None and m.n_v else None
+        tv = t(np.array([_flat_struct(self.tvp_fun(s), m.n_tvp) for s in ts])) if m.n_tvp else None
+        p_rows = p_loops = None
+        if m.n_p and P is not None:
+            P = np.ascontiguousarray(np.asarray(P, dtype=np.float64))
+            if P.shape != (B, m.n_p):
+                raise ValueError(f"Simulator.simulate_batch: P must have the shape ({B}, {m.n_p}), got {P.shape}")
+            p_loops = t(P)
+        elif m.n_p:
+            p_rows = t(np.array([_flat_struct(self.p_fun(s), m.n_p) for s in ts]))
+        Xt, Yt, st = e(K + 1, B, m.n_x), e(K, B, max(m.n_y, 1)), e(K, B, dt=torch.int32)
+        Zt = e(K, B, m.n_z) if m.n_z else None
+        Xt[0].copy_(t(X0))
+        ptr = lambda a: a.data_ptr() if a is not None else 0      # noqa: E731
+        stream = torch.cuda.current_stream(dev).cuda_stream if dev.type == "cuda" else 0
+        self.rollout_device(B, K, ptr(Xt), ptr(Ut), W_traj=ptr(Wt), V_traj=ptr(Vt), Y_traj=ptr(Yt) if m.n_y else 0, Z_traj=ptr(Zt),
+                            tvp_rows=ptr(tv), p_rows=ptr(p_rows), p_loops=ptr(p_loops), plant_status=ptr(st), reseed_z=not carry_z,
+                            stream=stream)
+        if dev.type == "cuda":
+            torch.cuda.synchronize(dev)
+        status = st.cpu().numpy()
+        return {"x": Xt.cpu().numpy(), "y": Yt.cpu().numpy()[:, :, :m.n_y], "z": Zt.cpu().numpy() if Zt is not None else np.zeros((K, B, 0)),
+                "status": status & 0xFF, "n_steps": status >> 8}
 
     def make_step(self, u0=None, v0=None, w0=None) -> np.ndarray:
         """One closed-loop sample (simulator.py:757-850): integrates x0 over t_step with u0 and the current p / tvp,

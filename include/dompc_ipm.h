@@ -490,6 +490,36 @@ int dompc_plant_rollout_affine_device(dompc_plant* h, int32_t B, int32_t K, cons
                                       const double* tvp_rows, const double* p_rows, int32_t* plant_status, int32_t* law_status,
                                       void* stream);
 
+/* The general rollout (dompc_plant_loop_kernel), for every plant, those with algebraic states included: K control steps of B loops in
+ * ONE launch, one thread per loop.  Every pointer of the description is a DEVICE address, except `law`, a host pointer to a record of
+ * device addresses (NULL: open loop).  Per loop b and step k = 0 .. K-1:
+ *   input   with a law: u = sat(u_ref + M (x - x_ref) + G (u_prev - up_ref)) at x = X_traj[k] goes to U_traj[k], its status bits to
+ *           law_status[k]; G [nu][nu][ld] and up_ref [nu][ld] are laid out like the law's arrays (up_ref may be the law's u_ref); u_prev
+ *           is U_prev0 [B][nu] at k = 0 and the input applied at k - 1 - the clipped one - afterwards.  G = NULL: the law of
+ *           dompc_plant_rollout_affine_device, with its bits.  Without a law U_traj[k] is read, and nothing is written there.
+ *   plant   the step of dompc_plant_step_batch_device, unchanged, from X_traj[k] to X_traj[k+1] with tvp_rows[k] [K][ntvp] (shared by
+ *           the batch) and EITHER p_rows[k] [K][np] (shared by the batch) OR p_loops [B][np] (one row per loop, constant over the K
+ *           steps); process noise W_traj [K][B][nw] and measurement noise V_traj [K][B][nv] (NULL: zero); the measurement at X_traj[k+1]
+ *           to Y_traj [K][B][ny] (NULL: none); status to plant_status[k].
+ *   z       the per-loop Newton starts of the algebraic states are the handle's, as in dompc_plant_step_batch_device: carried from step
+ *           to step and from call to call; reseed_z != 0 seeds them with z0 (dompc_plant_set_z0) first.  Z_traj [K][B][nz] (NULL: none)
+ *           receives the algebraic states at X_traj[k+1].
+ * X_traj [K+1][B][nx] with row 0 filled by the caller.  A loop whose plant step fails goes on from the state it reached.  Refused, with
+ * the reason in dompc_plant_last_error: null X_traj / U_traj, parameters without p_rows or p_loops (or with both), _tvp without
+ * tvp_rows, a law on a plant without inputs, an incomplete law record, G without a law, up_ref or U_prev0, Z_traj on a plant without
+ * algebraic states.  B <= 0 or K <= 0: nothing is launched.  Asynchronous on `stream`. */
+typedef struct dompc_plant_rollout_desc {
+  const dompc_affine_law* law;
+  const double *G, *up_ref, *U_prev0;
+  double *X_traj, *U_traj;
+  const double *W_traj, *V_traj;
+  double *Y_traj, *Z_traj;
+  const double *tvp_rows, *p_rows, *p_loops;
+  int32_t *plant_status, *law_status;
+  int32_t reseed_z, pad;
+} dompc_plant_rollout_desc;
+int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, const dompc_plant_rollout_desc* r, void* stream);
+
 /* ---- sensitivity-based MPC between two solves (csrc/dompc_asmpc.hip): the class ASMPC of the reference's
  * examples/batch_reactor_differentiator, u = (I - G)^-1 (u0 + J (x - x_prev) - G u0) with J = du0/dx0, G = du0/du_prev - the affine law
  * u = u0 + M (x - x_prev), M = (I - G)^-1 J - for B loops.  The code object is built for the sizes (nx <= 64, nu <= 16); the law

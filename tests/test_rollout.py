@@ -1,0 +1,46 @@
+"""The general plant rollout - Simulator.rollout_device, Simulator.simulate_batch, BatchClosedLoopLQR.run(fused=True) - on the host
+emulation of csrc/dompc_plant.hip (dompc_plant_loop_kernel's host twin): the checks of tests/rollout_common.py."""
+import pytest
+
+import rollout_common as rc
+
+
+@pytest.mark.parametrize("B,K", [(67, 4), (1, 1)])
+def test_same_bits_as_the_law_rollout(B, K):
+    rc.check_same_bits_as_law_rollout(True, B, K)
+
+
+def test_open_loop_with_noise_equals_stepwise_launches():
+    rc.check_open_loop_with_noise(True)
+
+
+@pytest.mark.parametrize("which", ["family", "oscillating_masses_dae"])
+def test_plants_with_algebraic_states(which):
+    rc.check_dae_plant(which, True)
+
+
+def test_previous_input_term():
+    rc.check_previous_input_term(True)
+
+
+@pytest.mark.parametrize("name", rc.LQR_CASES)
+def test_lqr_loop_fused_equals_stepwise(name):
+    rc.check_lqr_fused(name, True)
+
+
+def test_lqr_loop_standard_mode_far_from_the_set_point():
+    rc.check_lqr_law_far(True)
+
+
+@pytest.mark.parametrize("name", ["one_term", "oscillating_masses"])
+def test_lqr_loop_chunks_and_mixing_with_steps(name):
+    rc.check_lqr_chunks_and_mixing(name, True)
+
+
+@pytest.mark.parametrize("kind", ["ode", "dae"])
+def test_simulate_batch_equals_make_step_batch(kind):
+    rc.check_simulate_batch(kind, True)
+
+
+def test_refusals():
+    rc.check_refusals(True)
