@@ -185,6 +185,8 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_ampc_packed_size.restype = C.c_int64
     lib.dompc_ampc_set_weights.argtypes = [vp, vp, C.c_int64, vp, vp, vp, vp]
     lib.dompc_ampc_set_weights.restype = C.c_int
+    lib.dompc_ampc_device_weights.argtypes = [vp, C.POINTER(vp), C.POINTER(vp)]
+    lib.dompc_ampc_device_weights.restype = C.c_int
     lib.dompc_ampc_step_batch.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32]
     lib.dompc_ampc_step_batch.restype = C.c_int
     lib.dompc_ampc_step_batch_device.argtypes = [vp, C.c_int32, vp, vp, vp, C.c_int32, vp]
@@ -337,10 +339,7 @@ class ApproxMPC(torch.nn.Module):
         st, m = self.settings, self.mpc.model
         if self._h is None:
             code_object = self._native.load(self.generated_header, self.model_hash)
-            act = lowering.AMPC_ACTIVATIONS
-            desc = AMPCDesc(n_in=self.net.n_in, n_out=m.n_u, n_hidden_layers=st.n_hidden_layers, n_neurons=st.n_neurons,
-                            act=act[st.act_fn], out_act=act[st.act_fn if st.n_hidden_layers == 0 else st.output_act_fn],
-                            scaling=1 if st.scaling else 0, nx=m.n_x, code_object_path=code_object.encode(),
+            desc = AMPCDesc(**self.shape_fields(), nx=m.n_x, code_object_path=code_object.encode(),
                             model_hash=self.model_hash.encode(), device=st.gpu_index)
             self._native.create(desc)
         # (the box was fixed by setup(): settings cannot change afterwards; only the parameters are looked at per step)
@@ -352,6 +351,21 @@ class ApproxMPC(torch.nn.Module):
             self._check(self._lib.dompc_ampc_set_weights(self._h, ptr(packed), packed.size, *[ptr(a) for a in box]))
             self._uploaded = key
         return self._h
+
+    def shape_fields(self) -> dict:
+        """the network's shape as the native descriptions name it (dompc_ampc_desc, dompc_plant_ampc_loop_desc)"""
+        st, act = self.settings, lowering.AMPC_ACTIVATIONS
+        return dict(n_in=self.net.n_in, n_out=self.mpc.model.n_u, n_hidden_layers=st.n_hidden_layers, n_neurons=st.n_neurons,
+                    act=act[st.act_fn], out_act=act[st.act_fn if st.n_hidden_layers == 0 else st.output_act_fn],
+                    scaling=1 if st.scaling else 0)
+
+    def device_weights(self):
+        """(w, par): the device addresses of the handle's packed weights and of its scaling and bounds, holding the CURRENT weights
+        (`dompc_ampc_device_weights`) - what the fused loop of `Simulator.rollout_ampc_device` reads"""
+        h = self._handle()
+        w, par = C.c_void_p(), C.c_void_p()
+        self._check(self._lib.dompc_ampc_device_weights(h, C.byref(w), C.byref(par)))
+        return w.value, par.value
 
     def _check(self, rc):
         self._native.check(rc)

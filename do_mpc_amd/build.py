@@ -241,6 +241,44 @@ def ampc_code_object(header_text: str, model_hash: str, force: bool = False, rem
     return _kernel_code_object("ampc", "dompc_ampc.hip", "DOMPC_AMPC_HEADER", "ampc_gen.h", "network", header_text, model_hash, force, remarks)
 
 
+def ampc_loop_pair_hash(plant_hash: str, network_hash: str) -> str:
+    """the hash of a (plant, network shape) pair: made of the two model hashes"""
+    return f"{plant_hash}_{network_hash}"
+
+
+def ampc_loop_code_object(plant_header: str, network_header: str, pair_hash: str, force: bool = False, remarks: bool = False):
+    """gfx950 code object of the fused approximate-MPC loop (csrc/dompc_ampc_loop.hip) for one PAIR of a lowered plant model and a
+    lowered network shape: the plant's kernels plus dompc_ampc_loop_kernel, two generated headers behind -DDOMPC_PLANT_HEADER and
+    -DDOMPC_AMPC_HEADER (the weights are runtime data).  `pair_hash`: ampc_loop_pair_hash of the two model hashes.  Digest cache and
+    lock as in _kernel_code_object.  remarks=True: as ekf_code_object (profiles/ampc_loop_resource_usage.txt)."""
+    d = model_dir("ampc_loop_" + pair_hash)
+    hdrs = [(os.path.join(d, "plant_gen.h"), plant_header), (os.path.join(d, "ampc_gen.h"), network_header)]
+    out = os.path.join(d, f"dompc_ampc_loop_{ARCH}.hsaco")
+    stamp = out + ".stamp"
+    dig = _sources_digest() + hashlib.sha256((plant_header + "\0" + network_header).encode()).hexdigest()[:12]
+    cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "--genco", f"-DDOMPC_PLANT_HEADER=\"{hdrs[0][0]}\"",
+           f"-DDOMPC_AMPC_HEADER=\"{hdrs[1][0]}\"", "-I", CSRC, os.path.join(CSRC, "dompc_ampc_loop.hip")]
+    if not force and not remarks and _fresh(out, stamp, dig):
+        return out
+    with _locked(d):
+        if not force and not remarks and _fresh(out, stamp, dig):
+            return out
+        for hdr, text in hdrs:
+            if not (os.path.exists(hdr) and open(hdr).read() == text):
+                _write_atomic(hdr, text)
+        if remarks:
+            tmp = f"{out}.{os.getpid()}.remarks.tmp"
+            try:
+                text = _run(cmd + ["-Rpass-analysis=kernel-resource-usage", "-o", tmp], f"resource usage of the loop pair {pair_hash}")
+            finally:
+                if os.path.exists(tmp):
+                    os.remove(tmp)
+            return out, text
+        _compile_to(cmd, out, f"lowering the loop pair {pair_hash} to {ARCH}")
+        _write_atomic(stamp, dig)
+    return out
+
+
 def asmpc_code_object(header_text: str, model_hash: str, force: bool = False, remarks: bool = False):
     """gfx950 code object of the sensitivity-based MPC law (csrc/dompc_asmpc.hip: law preparation and law step) for one pair of sizes
     (n_x, n_u); no model in it, the law is runtime data.  remarks=True: as ekf_code_object (profiles/asmpc_resource_usage.txt)."""

@@ -18,7 +18,7 @@ The parts, each written once, and the six loops composed of them:
   BatchClosedLoopMHE    _ControllerSide -> _PlantSide (measuring) -> moving horizon estimator (its chain problem lives in the class)
   BatchClosedLoopEKF    _ControllerSide -> _PlantSide (measuring, noise) -> extended Kalman filter (its buffers live in the class)
   BatchClosedLoopLQR    gain (a torch expression) -> _PlantSide; run = _record_run, or fused: the gain as the law of the plant rollout
-  BatchClosedLoopAMPC   network kernel -> _PlantSide; run = _record_run
+  BatchClosedLoopAMPC   network kernel -> _PlantSide; run = _record_run, or fused: network and plant alternate inside one launch
   BatchClosedLoopASMPC  _ControllerSide (solved through ASMPC.solve_device, with multipliers) -> affine law -> _PlantSide; events, rollout
 
 The reference's per-sample loop re-evaluates tvp_fun / p_fun at the current time in EVERY make_step of controller, plant and
@@ -104,13 +104,17 @@ class _PlantSide:
             if m.n_tvp:
                 self.tvp.copy_(self.dv.to_dev(tv[0]))
 
-    def step(self, U, stream, shared_mask: int = 2 | 4 | 8 | 16, W=None) -> None:
+    def step(self, U, stream, shared_mask: int = 2 | 4 | 8 | 16, W=None, P=None) -> None:
         """one plant step of all loops with the inputs U [B][nu]; X is the new state afterwards.  shared_mask: _tvp and _p are one row
         for the batch (bits 1, 2), and so are the noise inputs (bits 3, 4) unless the loop clears their bits.  W: [B][nw] process
-        noise of this step, one row per loop (bit 3 is cleared for it), or None"""
+        noise of this step, one row per loop (bit 3 is cleared for it), or None.  P: [B][np], the plant's `_p` per loop in place of
+        the row of p_fun (bit 2 is cleared for it), or None"""
         if W is not None:
             shared_mask &= ~8
-        self.sim.step_batch_device(self.B, self.X.data_ptr(), U.data_ptr(), self.tvp.data_ptr(), self.p.data_ptr(), self.Xn.data_ptr(),
+        if P is not None:
+            shared_mask &= ~4
+        self.sim.step_batch_device(self.B, self.X.data_ptr(), U.data_ptr(), self.tvp.data_ptr(),
+                                   (self.p if P is None else P).data_ptr(), self.Xn.data_ptr(),
                                    self.Y.data_ptr() if self.Y is not None else 0, self.pstat.data_ptr(),
                                    w=W.data_ptr() if W is not None else 0,
                                    v=self.V.data_ptr() if self.V is not None else 0, shared_mask=shared_mask, stream=stream)
@@ -568,9 +572,11 @@ class BatchClosedLoopAMPC:
     """B closed loops approximate MPC -> plant advancing together with X and U resident in device memory (float64): per control step
     TWO launches, the network kernel (ApproxMPC.make_step_batch_device) and ONE batched plant step.  The per-sample loop of the
     reference is `u0 = approx_mpc.make_step(x0)`, `x0 = simulator.make_step(u0)`
-    (/root/reference/examples/CSTR_approximate_mpc/main.py:164-170).  State feedback: the plant's measurement must be its state.
+    (/root/reference/examples/CSTR_approximate_mpc/main.py:164-170).  State feedback: the network acts on the plant's state.
     X0: [B][nx]; U_prev0: [B][nu], the inputs before the first step (default: ampc.u0 for every loop; read only when the controller
-    has an rterm).  device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests)."""
+    has an rterm).  device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests).
+    `run(n, fused=True)` runs the steps inside the fused loop kernel of the pair (plant, network shape) instead: one launch per chunk
+    of steps, with process noise and plant parameters per loop if asked for."""
 
     def __init__(self, ampc, simulator, X0, U_prev0=None, device=0, clip_to_bounds=True):
         self.ampc, self.sim, self.clip = ampc, simulator, bool(clip_to_bounds)
@@ -581,29 +587,119 @@ class BatchClosedLoopAMPC:
         X0 = np.asarray(X0, dtype=float).reshape(-1, m.n_x)
         self.B = B = X0.shape[0]
         dv = self.dv = _Device(device, host_ok=True)
-        self.plant = _PlantSide(simulator, dv, X0)
+        # (a plant whose measurement is not its state: the network is a law on the STATE, the loop validates it on the true states; the
+        #  step-wise path then keeps the measurement of the last step in plant.Y)
+        self.plant = _PlantSide(simulator, dv, X0, measure=m.n_y != m.n_x)
         if U_prev0 is None:
             u0 = ampc.u0
             U_prev0 = np.tile(np.asarray(u0.master if hasattr(u0, "master") else u0, dtype=float).reshape(1, m.n_u), (B, 1))
         self.U = dv.to_dev(np.asarray(U_prev0, float).reshape(B, m.n_u))
         self.Un = dv.torch.empty_like(self.U)
+        self.P = None                     # [B][np]: the plant's `_p` per loop (run(P=...)); None: the row of the plant's p_fun
         self.k = 0
 
-    def step(self) -> dict:
-        """one control step of all B loops; returns the inputs applied, the new states and the plant status"""
+    def _noise(self, w):
+        """process noise of one step or of several, host array or tensor -> device tensor [...][B][nw] (None stays None)"""
+        if w is None:
+            return None
+        nw = self.sim.model.n_w
+        assert nw > 0, "process noise for a plant whose model has none (set_rhs(..., process_noise=True))"
+        w = w if type(w).__module__.startswith("torch") else self.dv.to_dev(w)
+        return w.to(self.dv.dev).reshape(-1, self.B, nw).contiguous()
+
+    def step(self, w=None) -> dict:
+        """one control step of all B loops; returns the inputs applied, the new states and the plant status.  w: [B][nw], the process
+        noise of this step (default: none)"""
         plant, stream = self.plant, self.dv.stream()
         plant.refresh(self.k)
+        w = self._noise(w)
         self.ampc.make_step_batch_device(self.B, plant.X.data_ptr(), self.U.data_ptr() if self.ampc.rterm else 0, self.Un.data_ptr(),
                                          stream=stream, clip_to_bounds=self.clip)
         self.U, self.Un = self.Un, self.U
-        plant.step(self.U, stream)
+        plant.step(self.U, stream, W=None if w is None else w[0], P=self.P)
         self.k += 1
         self.dv.sync()
         return {"u0": self.U.cpu().numpy(), "x": plant.X.cpu().numpy(), "plant_status": plant.status()[0]}
 
-    def run(self, n: int) -> dict:
-        """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step"""
-        return _record_run(self, n)
+    def _rollout(self, K, W):
+        """K control steps in one launch (`Simulator.rollout_ampc_device`), one synchronisation and one copy to the host; W: [K][B][nw]
+        on the device, or None.  Returns (x [K + 1][B][nx] with the state the launch started from, u [K][B][nu], plant status [K][B]);
+        x and u are views of the one host buffer of the copy - on a GPU page-locked memory, which the copy fills at the bus's rate
+        and torch hands out again once the records of an earlier run are dropped"""
+        dv, plant, m, B = self.dv, self.plant, self.sim.model, self.B
+        torch = dv.torch
+        nX, nU = (K + 1) * B * m.n_x, K * B * m.n_u
+        buf = dv.empty(nX + nU + (K * B + 1) // 2)             # states, inputs and the status words behind one another: one copy
+        Xt, Ut = buf[:nX].view(K + 1, B, m.n_x), buf[nX:nX + nU].view(K, B, m.n_u)
+        pst = buf[nX + nU:].view(torch.int32)[:K * B].view(K, B)
+        tv, pp = (dv.to_dev(a) for a in plant.rows(self.k, K))
+        Xt[0].copy_(plant.X)
+        per_loop = self.P is not None
+        self.sim.rollout_ampc_device(self.ampc, B, K, Xt.data_ptr(), Ut.data_ptr(), U_prev0=self.U.data_ptr() if self.ampc.rterm else 0,
+                                     W_traj=W.data_ptr() if W is not None else 0, tvp_rows=tv.data_ptr() if m.n_tvp else 0,
+                                     p_rows=pp.data_ptr() if m.n_p and not per_loop else 0, p_loops=self.P.data_ptr() if per_loop else 0,
+                                     plant_status=pst.data_ptr(), clip_to_bounds=self.clip, stream=dv.stream())
+        plant.X.copy_(Xt[K])
+        self.U.copy_(Ut[K - 1])
+        plant.pstat.copy_(pst[K - 1])
+        self.k += K
+        if dv.dev.type == "cuda":
+            host_t = torch.empty(buf.shape, dtype=buf.dtype, pin_memory=True)
+            host_t.copy_(buf, non_blocking=True)
+        else:
+            host_t = buf
+        dv.sync()
+        host = host_t.numpy()
+        st = host[nX + nU:].view(np.int32)[:K * B].reshape(K, B)
+        return host[:nX].reshape(K + 1, B, m.n_x), host[nX:nX + nU].reshape(K, B, m.n_u), st & 1
+
+    def run(self, n: int, fused: bool = False, chunk=None, W=None, P=None) -> dict:
+        """n control steps; returns the records 'x' [n + 1][B][nx] (with the start), 'u' [n][B][nu] and the plant status of every step.
+        W: process noise of the plant, [n][B][nw] or a callable k -> [B][nw] (k = 0 .. n - 1: the step of this run).
+        P: [B][np], the plant's `_p` per loop - validation under parametric uncertainty; it replaces the row of the plant's p_fun and
+        stays the loop's from then on (step() applies it too; None: no change).
+        fused=True: the steps run as ceil(n / chunk) launches of the fused loop kernel (`Simulator.rollout_ampc_device`,
+        csrc/dompc_ampc_loop.hip: the network step and the plant step alternate inside one launch), one synchronisation and one copy to
+        the host after each launch - instead of two launches, a synchronisation and three copies per step.  chunk=None: one launch.
+        Device memory per launch: (chunk + 1) B nx + chunk B nu float64 and chunk B int32 for the records, chunk B nw float64 more with
+        noise, chunk rows of the plant's `_tvp` and `_p`.  The records equal those of the step-wise path bit for bit: both run the
+        same functions on the same operands.  `k`, the states, the inputs applied last, the plant status and - for a plant with
+        algebraic states - the Newton starts are left where n calls of step() leave them: the two can be mixed."""
+        n = int(n)
+        m = self.sim.model
+        if P is not None:
+            assert m.n_p > 0, "per-loop parameters for a plant whose model has none"
+            P = P if type(P).__module__.startswith("torch") else self.dv.to_dev(P)
+            self.P = P.to(self.dv.dev).reshape(self.B, m.n_p).contiguous()
+        if W is not None and not callable(W):
+            W = self._noise(W)
+            assert W.shape[0] == n, f"W must hold the noise of {n} steps"
+
+        def noise(i, K):
+            """W of the steps i .. i + K - 1 on the device: [K][B][nw], or None"""
+            if W is None:
+                return None
+            return self._noise(np.stack([np.asarray(W(i + j), float) for j in range(K)])) if callable(W) else W[i:i + K]
+        if not fused and W is None:
+            return _record_run(self, n)
+        xs, us, st = [], [], []
+        if not fused or n <= 0:
+            xs.append(self.plant.X.cpu().numpy().copy()[None])
+        i = 0
+        while i < n:
+            if fused:
+                K = n - i if chunk is None else min(int(chunk), n - i)
+                x, u, s = self._rollout(K, noise(i, K))
+                x = x if i == 0 else x[1:]                     # (the first launch's record starts with the start of the run)
+            else:
+                K = 1
+                r = self.step(w=noise(i, 1)[0])
+                x, u, s = r["x"].copy()[None], r["u0"].copy()[None], r["plant_status"][None]
+            xs.append(x); us.append(u); st.append(s)
+            i += K
+        # (one launch: its records as they came from the device, not copied once more)
+        cat = lambda parts, shape, dt: (parts[0] if len(parts) == 1 else np.concatenate(parts)) if parts else np.zeros(shape, dtype=dt)      # noqa: E731
+        return {"x": cat(xs, None, float), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(st, (0, self.B), np.int32)}
 
 
 class BatchClosedLoopASMPC:

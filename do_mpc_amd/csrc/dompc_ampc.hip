@@ -260,7 +260,9 @@ AMPC_DEV void jac32(const JacArgs& J, int64_t first) {
     for (int i = 0; i < (int)sizeof(h_); ++i) hash[i] = h_[i];                                                                \
   } while (0)
 
-#ifndef DOMPC_HOST_EMU
+#ifdef DOMPC_AMPC_NO_ENTRY
+// (included by dompc_ampc_loop.hip for step32: the entry points belong to the network's own code object)
+#elif !defined(DOMPC_HOST_EMU)
 extern "C" __global__ void __launch_bounds__(64) dompc_ampc_kernel(dompc_ampck::Args A) {
   dompc_ampck::step32(A, (int64_t)blockIdx.x * 32);
 }

@@ -83,6 +83,14 @@ extern "C" int dompc_ampc_set_weights(dompc_ampc* h, const float* packed, int64_
   return 0;
 }
 
+extern "C" int dompc_ampc_device_weights(dompc_ampc* h, const float** w, const double** par) {
+  if (!h) return 1;
+  if (!w || !par) { h->error = "null pointer"; return 1; }
+  if (!h->have_weights) { h->error = "no weights: call dompc_ampc_set_weights first"; return 1; }
+  *w = h->w; *par = h->par;
+  return 0;
+}
+
 extern "C" int dompc_ampc_step_batch_device(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u, int32_t clip,
                                             void* stream) {
   if (!h) return 1;

@@ -6,12 +6,16 @@
 #include "../../include/dompc_ipm.h"
 #include "dompc_host.h"
 #include "dompc_plant_args.h"
+#include "dompc_ampc_loop_args.h"
 
 // the host twins of the kernels (dompc_plant.hip)
 extern "C" void dompc_plant_hostemu_info(const void* args);
 extern "C" void dompc_plant_hostemu_run(const void* args);
 extern "C" void dompc_plant_hostemu_rollout(const void* args);
 extern "C" void dompc_plant_hostemu_loop(const void* args);
+// ... and of the fused approximate-MPC loop (dompc_ampc_loop.hip): there only in the host library of a (plant, network shape) pair
+extern "C" void dompc_ampc_loop_hostemu_info(const void* args) __attribute__((weak));
+extern "C" void dompc_ampc_loop_hostemu_run(const void* args) __attribute__((weak));
 
 static_assert(sizeof(dompc_affine_law) == sizeof(dompc_affine::Law), "dompc_affine_law of the C ABI and the kernels' law record");
 
@@ -31,6 +35,10 @@ struct dompc_plant : dompc_host::Context {
   bool z_reseed_next = false;
   dompc_host::Module module = nullptr;
   dompc_host::Kernel fn, fn_rollout, fn_loop;
+  // the fused approximate-MPC loop of a pair object, looked up on first use: 0 not looked for yet, 1 there, -1 the object has none
+  int ampc_loop_state = 0;
+  dompc_host::Kernel fn_ampc_loop;
+  int64_t ampc_loop_info[16] = {0};     // what dompc_ampc_loop_info_kernel reported: sizeof(AmpcLoopArgs), then the network's shape
 };
 
 extern "C" const char* dompc_plant_last_error(const dompc_plant* h) { return h ? h->error.c_str() : g_plant_create_error.c_str(); }
@@ -234,4 +242,81 @@ extern "C" int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, 
   R.tvp_rows = r->tvp_rows; R.p_rows = r->p_rows; R.p_loops = r->p_loops;
   R.plant_status = r->plant_status; R.law_status = r->law_status; R.K = K;
   return h->run(h->fn_loop, (unsigned)((B + 63) / 64), 64, 0, stream, &R, sizeof(R));
+}
+
+extern "C" int dompc_plant_z_guess_device(dompc_plant* h, int32_t B, int32_t reseed, double** z_guess) {
+  if (!h) return 1;
+  if (!z_guess) { h->error = "null pointer"; return 1; }
+  *z_guess = nullptr;
+  if (h->nz <= 0 || B <= 0) return 0;
+  if (h->set_device()) return 1;
+  if (ensure_z(h, B, reseed != 0 || h->z_reseed_next)) return 1;
+  h->z_reseed_next = false;
+  *z_guess = h->z_dev;
+  return 0;
+}
+
+// the loop kernel of a pair object and what its info kernel reports, looked up once per handle
+static int find_ampc_loop(dompc_plant* h) {
+  if (h->ampc_loop_state != 0) return h->ampc_loop_state > 0 ? 0 : 1;
+  h->ampc_loop_state = -1;
+  dompc_host::Kernel k_info;
+  h->find(h->module, {"dompc_ampc_loop_kernel", &h->fn_ampc_loop, DOMPC_TWIN(dompc_ampc_loop_hostemu_run)});
+  h->find(h->module, {"dompc_ampc_loop_info_kernel", &k_info, DOMPC_TWIN(dompc_ampc_loop_hostemu_info)});
+  if (!h->fn_ampc_loop || !k_info) return 1;
+  char hash[64] = {0};
+  if (h->query(k_info, "dompc_ampc_loop_info_kernel", h->ampc_loop_info, hash)) return 1;
+  h->ampc_loop_state = 1;
+  return 0;
+}
+
+extern "C" int dompc_plant_ampc_loop_device(dompc_plant* h, int32_t B, int32_t K, const dompc_plant_ampc_loop_desc* r, void* stream) {
+  if (!h) return 1;
+  if (B <= 0 || K <= 0) return 0;
+  const dompc_plant_desc& d = h->d;
+  const char* me = "dompc_plant_ampc_loop_device: ";
+  auto refuse = [&](const char* what) { h->error = std::string(me) + what; return 1; };
+  if (!r) return refuse("null description");
+  if (!r->X_traj) return refuse("X_traj is null");
+  if (!r->U_traj) return refuse("U_traj is null");
+  if (d.np && !r->p_rows && !r->p_loops) return refuse("the plant has parameters: p_rows or p_loops is needed");
+  if (r->p_rows && r->p_loops) return refuse("p_rows and p_loops are both given (one of them)");
+  if (d.ntvp && !r->tvp_rows) return refuse("the plant has time-varying parameters: tvp_rows is needed");
+  if (r->Z_traj && h->nz <= 0) return refuse("Z_traj on a plant without algebraic states");
+  if (r->n_out != d.nu) return refuse("the network's n_out differs from the plant's nu");
+  if (r->n_in != d.nx && r->n_in != d.nx + d.nu) return refuse("the network's n_in is neither the plant's nx nor nx + nu");
+  if (r->n_in > d.nx && !r->U_prev0) return refuse("the network has an rterm (n_in = nx + nu): U_prev0 is needed");
+  if (!r->w || !r->par) return refuse("the network's weights (w, par) are null");
+  if (h->set_device()) return 1;
+  if (find_ampc_loop(h)) {
+    if (h->ampc_loop_state < 0 && !h->fn_ampc_loop) return refuse("the handle's code object has no loop kernel (dompc_ampc_loop_kernel: create the handle on the object of a (plant, network) pair)");
+    return refuse("dompc_ampc_loop_info_kernel failed");
+  }
+  const int64_t* info = h->ampc_loop_info;
+  if (info[0] != (int64_t)sizeof(dompc_ampc_loopk::AmpcLoopArgs)) return refuse("loop argument layout mismatch between runtime and code object");
+  const int64_t want[7] = {r->n_in, r->n_out, r->n_hidden_layers, r->n_neurons, r->act, r->out_act, r->scaling ? 1 : 0};
+  for (int i = 0; i < 7; ++i)
+    if (info[1 + i] != want[i]) return refuse("the code object was built for another network shape");
+  // the per-loop Newton starts of the algebraic states: the caller's (another handle's, dompc_plant_z_guess_device) or this handle's own
+  double* z = nullptr;
+  if (h->nz > 0) {
+    if (r->z_guess) z = r->z_guess;
+    else {
+      if (ensure_z(h, B, r->reseed_z != 0 || h->z_reseed_next)) return 1;
+      h->z_reseed_next = false;
+      z = h->z_dev;
+    }
+  }
+  dompc_ampc_loopk::AmpcLoopArgs R;
+  memset(&R, 0, sizeof(R));
+  dompc_plantk::LoopArgs& L = R.loop;
+  fill_args(h, L.plant, B, 0);
+  L.plant.z_guess = z;
+  L.U_prev0 = r->n_in > d.nx ? r->U_prev0 : nullptr;
+  L.X_traj = r->X_traj; L.U_traj = r->U_traj; L.W_traj = r->W_traj; L.V_traj = r->V_traj; L.Y_traj = r->Y_traj; L.Z_traj = r->Z_traj;
+  L.tvp_rows = r->tvp_rows; L.p_rows = r->p_rows; L.p_loops = r->p_loops;
+  L.plant_status = r->plant_status; L.K = K; L.has_law = 0;
+  R.w = r->w; R.par = r->par; R.nx = d.nx; R.clip = r->clip ? 1 : 0;
+  // one wavefront per workgroup, 64 loops per wavefront
+  return h->run(h->fn_ampc_loop, (unsigned)(((int64_t)B + 63) / 64), 64, 0, stream, &R, sizeof(R));
 }

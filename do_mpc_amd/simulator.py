@@ -56,6 +56,15 @@ class RolloutDesc(C.Structure):
                [("reseed_z", C.c_int32), ("pad", C.c_int32)]
 
 
+class AmpcLoopDesc(C.Structure):
+    """dompc_plant_ampc_loop_desc of include/dompc_ipm.h"""
+    SHAPE = ("n_in", "n_out", "n_hidden_layers", "n_neurons", "act", "out_act", "scaling")
+    _fields_ = [("w", C.c_void_p), ("par", C.c_void_p)] + [(n, C.c_int32) for n in SHAPE + ("clip",)] + \
+               [(n, C.c_void_p) for n in ("U_prev0", "X_traj", "U_traj", "W_traj", "V_traj", "Y_traj", "Z_traj", "tvp_rows", "p_rows",
+                                          "p_loops", "plant_status", "z_guess")] + \
+               [("reseed_z", C.c_int32), ("pad", C.c_int32)]
+
+
 def _bind(lib_path: str) -> C.CDLL:
     lib = C.CDLL(lib_path)
     vp = C.c_void_p
@@ -80,6 +89,10 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_plant_rollout_affine_device.restype = C.c_int
     lib.dompc_plant_rollout_device.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(RolloutDesc), vp]
     lib.dompc_plant_rollout_device.restype = C.c_int
+    lib.dompc_plant_ampc_loop_device.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(AmpcLoopDesc), vp]
+    lib.dompc_plant_ampc_loop_device.restype = C.c_int
+    lib.dompc_plant_z_guess_device.argtypes = [vp, C.c_int32, C.c_int32, C.POINTER(vp)]
+    lib.dompc_plant_z_guess_device.restype = C.c_int
     return lib
 
 
@@ -118,6 +131,8 @@ class Simulator:
         self.data = MPCData(model)
         self.flags = {"set_tvp_fun": False, "set_p_fun": False, "setup": False, "first_step": True}
         self._native = _native.Native("plant", _bind, build.plant_code_object)
+        self._pairs = {}                  # network hash -> the plant handle on the pair object of (this plant, that network shape)
+        self._ampc_loop_lib = None        # TEST-ONLY: (plant header, network header, pair hash) -> host-emulation library of a pair
 
     _lib = property(lambda self: self._native.lib)     # the bound library and the native handle (None before setup / after close)
     _h = property(lambda self: self._native.h)
@@ -217,6 +232,9 @@ class Simulator:
 
     def close(self):
         self._native.close()
+        for nat in self._pairs.values():
+            nat.close()
+        self._pairs = {}
 
     # ------------------------------------------------------------------ runtime
     def set_initial_guess(self) -> None:
@@ -322,6 +340,67 @@ class Simulator:
         r.reseed_z = 1 if reseed_z else 0
         rc = self._lib.dompc_plant_rollout_device(self._h, int(B), int(K), C.byref(r), C.c_void_p(int(stream) if stream else None))
         self._check(rc)
+
+    def _pair(self, ampc) -> "_native.Native":
+        """the plant handle on the code object of the pair (this plant, the shape of `ampc`'s network): built or loaded on first use,
+        kept per network shape; the settings of setup() apply to it as to the plant's own handle"""
+        nat = self._pairs.get(ampc.model_hash)
+        if nat is not None and nat.h is not None:
+            return nat
+        m, st = self.model, self.settings
+        plant_hdr, net_hdr = self.generated_header, ampc.generated_header
+        pair_hash = build.ampc_loop_pair_hash(self.model_hash, ampc.model_hash)
+        emu = self._ampc_loop_lib
+        nat = _native.Native("plant", _bind, lambda *_: build.ampc_loop_code_object(plant_hdr, net_hdr, pair_hash),
+                             (lambda *_: emu(plant_hdr, net_hdr, pair_hash)) if emu is not None else None, "" if emu is not None else None)
+        code_object = nat.load(plant_hdr, self.model_hash)
+        d = PlantDesc(nx=m.n_x, nu=m.n_u, np=m.n_p, ntvp=m.n_tvp, nw=m.n_w, nv=m.n_v, ny=m.n_y,
+                      discrete=1 if m.model_type == "discrete" else 0, code_object_path=code_object.encode(),
+                      model_hash=self.model_hash.encode(), device=st.gpu_index, max_steps=st.max_steps, t_step=float(st.t_step),
+                      reltol=float(st.reltol), abstol=float(st.abstol))
+        nat.create(d)
+        methods = {"cvodes": 0, "idas": 0, "auto": 0, "dopri5": 1, "rk45": 1, "sdirk4": 2, "implicit": 2}
+        nat.check(nat.lib.dompc_plant_set_method(nat.h, methods[str(st.integration_tool).lower()], int(st.integration_opts.get("explicit_limit", 0))))
+        self._pairs[ampc.model_hash] = nat
+        return nat
+
+    def rollout_ampc_device(self, ampc, B, K, X_traj, U_traj, U_prev0=0, W_traj=0, V_traj=0, Y_traj=0, Z_traj=0, tvp_rows=0, p_rows=0,
+                            p_loops=0, plant_status=0, clip_to_bounds=True, reseed_z=False, stream=0):
+        """K control steps approximate MPC -> plant of B loops in ONE launch (`dompc_plant_ampc_loop_device`, csrc/dompc_ampc_loop.hip):
+        per step k the network step of `ampc.make_step_batch_device` at X_traj[k] - with an rterm also on the inputs applied before,
+        U_prev0 [B][nu] at k = 0 and U_traj[k - 1] afterwards - writes U_traj[k], then the plant step of `step_batch_device` goes from
+        X_traj[k] to X_traj[k + 1]; bit for bit the K pairs of launches.  Raw device addresses, asynchronous on `stream`; the
+        parameters, noise, records and status are those of `rollout_device`.  The code object of the pair (this plant, the network's
+        shape) is built or loaded on first use and kept; the network's CURRENT weights are used (they are data, as in
+        `make_step_batch_device`).  The Newton starts of a plant with algebraic states are those of `step_batch_device`: the two paths
+        can be mixed; reseed_z: they start from `simulator.z0`."""
+        assert self.flags["setup"], "Simulator is not setup. Call simulator.setup() first."
+        m = self.model
+        who = "dompc_plant: dompc_plant_ampc_loop_device: "
+        n_in, n_out = int(ampc.net.n_in), int(ampc.mpc.model.n_u)
+        # (the sizes are compile-time facts of the pair's code object: what the entry point refuses is refused before one is built)
+        if n_out != m.n_u:
+            raise RuntimeError(who + "the network's n_out differs from the plant's nu")
+        if n_in not in (m.n_x, m.n_x + m.n_u):
+            raise RuntimeError(who + "the network's n_in is neither the plant's nx nor nx + nu")
+        if int(B) <= 0 or int(K) <= 0:
+            return
+        nat = self._pair(ampc)
+        r = AmpcLoopDesc()
+        r.w, r.par = ampc.device_weights()
+        for name, v in ampc.shape_fields().items():
+            setattr(r, name, v)
+        r.clip = 1 if clip_to_bounds else 0
+        for name, a in (("U_prev0", U_prev0), ("X_traj", X_traj), ("U_traj", U_traj), ("W_traj", W_traj), ("V_traj", V_traj),
+                        ("Y_traj", Y_traj), ("Z_traj", Z_traj), ("tvp_rows", tvp_rows), ("p_rows", p_rows), ("p_loops", p_loops),
+                        ("plant_status", plant_status)):
+            setattr(r, name, int(a) if a else None)
+        if m.n_z and nat is not self._native:
+            z = C.c_void_p()
+            self._check(self._lib.dompc_plant_z_guess_device(self._h, int(B), 1 if reseed_z else 0, C.byref(z)))
+            r.z_guess = z.value
+        r.reseed_z = 1 if reseed_z else 0
+        nat.check(nat.lib.dompc_plant_ampc_loop_device(nat.h, int(B), int(K), C.byref(r), C.c_void_p(int(stream) if stream else None)))
 
     def simulate_batch(self, X0, U, W=None, V=None, P=None, carry_z: bool = False) -> dict:
         """Open-loop simulation of B plants over K control steps in one launch (`rollout_device`).  X0: [B][nx]; U: [K][B][nu], or

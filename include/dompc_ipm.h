@@ -446,6 +446,9 @@ int64_t dompc_ampc_packed_size(const dompc_ampc* h);          /* floats of the p
  * the box of the network input (shift = lb_in, range = ub_in - lb_in); lbu / ubu [n_out].  Host pointers; returns when the copy is done. */
 int dompc_ampc_set_weights(dompc_ampc* h, const float* packed_f32, int64_t n, const double* lb_in, const double* ub_in,
                            const double* lbu, const double* ubu);
+/* the handle's DEVICE arrays of the last dompc_ampc_set_weights: the packed weights and shift, range, lbu, ubu, ubu - lbu - what
+ * dompc_plant_ampc_loop_device takes as w and par.  Valid until the handle is destroyed; their content follows dompc_ampc_set_weights. */
+int dompc_ampc_device_weights(dompc_ampc* h, const float** w, const double** par);
 /* host buffers */
 int dompc_ampc_step_batch(dompc_ampc* h, int32_t B, const double* x, const double* u_prev, double* u_out, int32_t clip_to_bounds);
 /* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*) */
@@ -519,6 +522,41 @@ typedef struct dompc_plant_rollout_desc {
   int32_t reseed_z, pad;
 } dompc_plant_rollout_desc;
 int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, const dompc_plant_rollout_desc* r, void* stream);
+
+/* The fused approximate-MPC loop (csrc/dompc_ampc_loop.hip: dompc_ampc_loop_kernel): K control steps network -> plant of B loops in
+ * ONE launch, one wavefront per 64 loops.  The plant handle is created on the code object of a PAIR - one plant model and one network
+ * shape; it holds every plant kernel too, so the handle serves every other dompc_plant_* call as well.  Every pointer of the
+ * description is a DEVICE address.  Per loop b and step k = 0 .. K-1:
+ *   network the step of dompc_ampc_step_batch_device, unchanged, at x = X_traj[k] with u_prev = U_prev0 [B][nu] at k = 0 and the input
+ *           applied at k - 1 - the clipped one - afterwards (n_in = nx + nu; with n_in = nx there is no u_prev and U_prev0 is not read);
+ *           the input goes to U_traj[k].  w and par are the network handle's device arrays (dompc_ampc_device_weights), the shape
+ *           fields its description's; clip as clip_to_bounds there.
+ *   plant   the step of dompc_plant_step_batch_device, unchanged, with the parameters, noise, records and status of
+ *           dompc_plant_rollout_device.
+ *   z       the per-loop Newton starts of the algebraic states: z_guess [B][nz], e.g. those of the handle that runs the same loops step
+ *           by step (dompc_plant_z_guess_device) - the two paths then carry ONE set of starts; NULL: this handle's own, reseed_z != 0
+ *           seeds them with z0 first.
+ * Refused, with the reason in dompc_plant_last_error: null X_traj / U_traj, parameters without p_rows or p_loops (or with both), _tvp
+ * without tvp_rows, Z_traj on a plant without algebraic states, n_out != nu, n_in neither nx nor nx + nu, n_in = nx + nu without
+ * U_prev0, null w / par, a handle whose code object has no loop kernel or was built for another network shape.  B <= 0 or K <= 0:
+ * nothing is launched.  Asynchronous on `stream`. */
+typedef struct dompc_plant_ampc_loop_desc {
+  const float* w;
+  const double* par;
+  int32_t n_in, n_out, n_hidden_layers, n_neurons, act, out_act, scaling, clip;
+  const double* U_prev0;
+  double *X_traj, *U_traj;
+  const double *W_traj, *V_traj;
+  double *Y_traj, *Z_traj;
+  const double *tvp_rows, *p_rows, *p_loops;
+  int32_t* plant_status;
+  double* z_guess;
+  int32_t reseed_z, pad;
+} dompc_plant_ampc_loop_desc;
+int dompc_plant_ampc_loop_device(dompc_plant* h, int32_t B, int32_t K, const dompc_plant_ampc_loop_desc* d, void* stream);
+/* The handle's per-loop Newton starts for B loops, a DEVICE array [B][nz] (NULL for a plant without algebraic states): allocated and
+ * seeded as the next step of B samples would (reseed != 0: with z0).  Valid until the handle's buffer grows or the handle is destroyed. */
+int dompc_plant_z_guess_device(dompc_plant* h, int32_t B, int32_t reseed, double** z_guess);
 
 /* ---- sensitivity-based MPC between two solves (csrc/dompc_asmpc.hip): the class ASMPC of the reference's
  * examples/batch_reactor_differentiator, u = (I - G)^-1 (u0 + J (x - x_prev) - G u0) with J = du0/dx0, G = du0/du_prev - the affine law
