@@ -77,6 +77,8 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_asmpc_law.argtypes = [vp, C.POINTER(AffineLaw)]
     lib.dompc_asmpc_step_batch.argtypes = [vp, i32, vp, vp, vp]
     lib.dompc_asmpc_step_batch_device.argtypes = [vp, i32, vp, vp, vp, vp]
+    lib.dompc_asmpc_step_law_device.argtypes = [vp, C.POINTER(AffineLaw), i32, vp, vp, vp, vp]
+    lib.dompc_asmpc_step_law_device.restype = C.c_int
     lib.dompc_asmpc_select_device.argtypes = [vp, i32, vp, i32, vp, vp, vp]
     lib.dompc_asmpc_update_device.argtypes = [vp, i32, vp, vp, vp, vp, i64, i64, vp, i64, i64, vp, vp]
     lib.dompc_asmpc_update_law.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
@@ -88,6 +90,28 @@ def _bind(lib_path: str) -> C.CDLL:
 
 def _ptr(a):
     return a.ctypes.data_as(C.c_void_p) if a is not None else None
+
+
+class LawStep:
+    """The law-step kernel of the (n_x, n_u) law object on a record of the caller's: u = sat(u_ref + M (x - x_ref)) for B loops in one
+    launch (`dompc_asmpc_step_law_device`), without an MPC behind it - closed_loop.BatchClosedLoopTVLQR steps its time-varying law with it.
+    TEST-ONLY: `_lib_path` (a path, or a callable (header, hash) -> path) selects the host emulation of the kernels."""
+
+    def __init__(self, n_x: int, n_u: int, device: int = 0, _lib_path=None):
+        self.generated_header = lowering.lower_asmpc(n_x, n_u)
+        self.model_hash = self.generated_header.rsplit('ASMPC_MODEL_HASH "', 1)[1].split('"')[0]
+        self._native = _native.Native("asmpc", _bind, build.asmpc_code_object, _lib_path, "" if _lib_path is not None else None)
+        code_object = self._native.load(self.generated_header, self.model_hash)
+        self._native.create(ASMPCDesc(nx=n_x, nu=n_u, code_object_path=code_object.encode(), model_hash=self.model_hash.encode(), device=int(device)))
+
+    def step_device(self, law: AffineLaw, B, X_ptr, U_ptr, status_ptr=0, stream=0) -> None:
+        """raw device addresses, asynchronous on `stream`"""
+        vp = lambda a: C.c_void_p(int(a) if a else None)      # noqa: E731
+        self._native.check(self._native.lib.dompc_asmpc_step_law_device(self._native.h, C.byref(law), int(B), vp(X_ptr), vp(U_ptr),
+                                                                        vp(status_ptr), vp(stream)))
+
+    def close(self):
+        self._native.close()
 
 
 class ASMPC:

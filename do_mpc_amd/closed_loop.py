@@ -6,7 +6,7 @@ out over processes (`do_mpc.sampling.Sampler`, /root/reference/do_mpc/sampling/_
 advance together: one launch per controller, plant and estimator and control step, all on the same stream; states, inputs,
 parameters and the warm-start solution stay in device memory (torch tensors are only the allocator).
 
-The parts, each written once, and the six loops composed of them:
+The parts, each written once, and the seven loops composed of them:
 
   _Device          the torch device of a loop, host array -> device tensor (always a copy), its stream and its synchronisation
   _PlantSide       the plant: states, status, its `_p` / `_tvp` at the loop time, the batched step, optionally measurement and noise
@@ -18,6 +18,7 @@ The parts, each written once, and the six loops composed of them:
   BatchClosedLoopMHE    _ControllerSide -> _PlantSide (measuring) -> moving horizon estimator (its chain problem lives in the class)
   BatchClosedLoopEKF    _ControllerSide -> _PlantSide (measuring, noise) -> extended Kalman filter (its buffers live in the class)
   BatchClosedLoopLQR    gain (a torch expression) -> _PlantSide; run = _record_run, or fused: the gain as the law of the plant rollout
+  BatchClosedLoopTVLQR  time-varying gains along a reference (LQR.gains_along_device) -> the plant rollout with a law record per step
   BatchClosedLoopAMPC   network kernel -> _PlantSide; run = _record_run, or fused: network and plant alternate inside one launch
   BatchClosedLoopASMPC  _ControllerSide (solved through ASMPC.solve_device, with multipliers) -> affine law -> _PlantSide; events, rollout
 
@@ -566,6 +567,169 @@ class BatchClosedLoopLQR:
             i += K
         cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dtype=dt)      # noqa: E731
         return {"x": np.concatenate(xs), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(st, (0, self.B), np.int32)}
+
+
+class BatchClosedLoopTVLQR:
+    """B closed loops that track a trajectory under the time-varying LQR law u_k = u*_k + K_k (x_k - x*_k), states, reference and gains
+    resident in device memory.  X0: [B][nx]; X_ref: [K + 1][B or 1][nx] (only the first K rows are knots), U_ref: [K][B or 1][nu] - e.g. a
+    record of `Simulator.simulate_batch`; K_traj: the gains [K][B or 1][nu][nx], or None: `design()` forms them on the resident
+    reference (`LQR.gains_along_device` on the plant's model with the controller's weights, the gains written by the kernel in the
+    layout of the law record).  `step()` is one control step - two launches: the law step at the step's record (`asmpc.LawStep`), then
+    the plant step -, `run()` the steps inside the general plant rollout with a law record per step
+    (`Simulator.rollout_device(law_step=)`).  The loop ends at step K: a step past it raises.  Standard mode only.  State
+    feedback: the plant's measurement must be its state.  The pairs are formed with the plant's `_tvp` at the K loop times and its `_p`
+    at the first one.  device: index of the HIP device, or "cpu" with a controller and a plant on the host emulation (tests; TEST-ONLY
+    `_law_lib`: the host-emulation library of the law-step kernel, as `asmpc.LawStep` takes it)."""
+
+    def __init__(self, lqr, simulator, X0, X_ref, U_ref, K_traj=None, device=0, _law_lib=None):
+        if lqr.mode == "inputRatePenalization":
+            raise NotImplementedError("BatchClosedLoopTVLQR: a controller in inputRatePenalization mode is not served (the time-varying "
+                                      "input-rate law is not built); use the standard mode")
+        self.lqr, self.sim = lqr, simulator
+        m, ml = simulator.model, lqr.model
+        assert (m.n_x, m.n_u) == (ml.n_x, ml.n_u), "controller and plant must share states and inputs"
+        X0 = np.asarray(X0, dtype=float).reshape(-1, m.n_x)
+        self.B = B = X0.shape[0]
+        U_ref = np.asarray(U_ref, dtype=float)
+        self.K = K = int(U_ref.shape[0])
+        if K < 1:
+            raise ValueError("BatchClosedLoopTVLQR: U_ref must hold at least one step")
+        U_ref = np.ascontiguousarray(np.broadcast_to(U_ref.reshape(K, -1, m.n_u), (K, B, m.n_u)))
+        X_ref = np.asarray(X_ref, dtype=float)
+        if X_ref.shape[0] != K + 1:
+            raise ValueError(f"BatchClosedLoopTVLQR: X_ref must have {K + 1} rows for the {K} rows of U_ref, got {X_ref.shape[0]}")
+        X_ref = np.ascontiguousarray(np.broadcast_to(X_ref.reshape(K + 1, -1, m.n_x), (K + 1, B, m.n_x)))
+        dv = self.dv = _Device(device, host_ok=True)
+        t = dv.to_dev
+        self.plant = _PlantSide(simulator, dv, X0)
+        self.X_ref, self.U_ref = t(X_ref), t(U_ref)                           # step-major: the knots of the pairs launch
+        # the law arrays, loop index fastest: x_ref [K][nx][B], u_ref [K][nu][B], M [K][nu][nx][B], flags [K][B]
+        self.x_ref, self.u_ref = self.X_ref[:K].permute(0, 2, 1).contiguous(), self.U_ref.permute(0, 2, 1).contiguous()
+        self.M = dv.zeros(K, m.n_u, m.n_x, B)
+        self.flags = dv.zeros(K, B, dtype=dv.torch.int32)
+        self.x_scale = t(np.ones(m.n_x))
+        self.U = dv.zeros(B, m.n_u)
+        self.lstat = dv.zeros(B, dtype=dv.torch.int32)
+        self._law_lib, self._law_step = _law_lib, None
+        self.k = 0
+        self.design_status = None
+        if K_traj is None:
+            self.design()
+        else:
+            Kt = np.asarray(K_traj, dtype=float)
+            Kt = np.broadcast_to(Kt.reshape(K, -1, m.n_u, m.n_x), (K, B, m.n_u, m.n_x))
+            self.M.copy_(t(np.ascontiguousarray(Kt.transpose(0, 2, 3, 1))))
+
+    def design(self) -> dict:
+        """the gains along the resident reference, two launches and no transposition: pairs, then the recursion writing M.  Returns
+        {'status' [B], 'step' [B], 'pair_status' [K][B]} (LQR.gains_along) and keeps it in `design_status`; a trajectory that failed at
+        step k replays U_ref up to k."""
+        dv, m, B, K, lqr = self.dv, self.sim.model, self.B, self.K, self.lqr
+        torch = dv.torch
+        Qd, Rd, Pd, mask = lqr._weights(None, None, None, B, finite="tv")
+        Q, R, P = dv.to_dev(Qd), dv.to_dev(Rd), dv.to_dev(Pd)
+        A, Bm, P0 = dv.empty(K, B, m.n_x, m.n_x), dv.empty(K, B, m.n_x, m.n_u), dv.empty(B, m.n_x, m.n_x)
+        st, ps = dv.zeros(B, dtype=torch.int32), dv.zeros(K, B, dtype=torch.int32)
+        tv, pp = self.plant.rows(0, K)
+        tvp, p = dv.to_dev(tv), dv.to_dev(pp[0])
+        z = None
+        if m.n_z:
+            z0 = np.asarray(self.sim._z0.master, float)            # (the Newton start of the plant)
+            z = dv.to_dev(np.ascontiguousarray(np.broadcast_to(z0.reshape(1, 1, m.n_z), (K, B, m.n_z))))
+        lqr.gains_along_device(m, B, K, self.X_ref.data_ptr(), self.U_ref.data_ptr(), A.data_ptr(), Bm.data_ptr(), Q.data_ptr(), R.data_ptr(),
+                               P.data_ptr(), P0.data_ptr(), tvp=tvp.data_ptr() if m.n_tvp else 0, p=p.data_ptr() if m.n_p else 0,
+                               z=z.data_ptr() if z is not None else 0, law_M=self.M.data_ptr(), ld=B, pair_status=ps.data_ptr(),
+                               status=st.data_ptr(), shared_mask=mask | 8 | 16, stream=dv.stream())
+        dv.sync()
+        s = st.cpu().numpy()
+        self.design_status = {"status": s & 0xFF, "step": (s >> 8) & 0xFFFF, "pair_status": ps.cpu().numpy() & 0xFF}
+        return self.design_status
+
+    _noise = BatchClosedLoopLQR._noise
+
+    def _law(self, k: int):
+        """the law record of step k: the arrays advanced by hand (what law_step does inside the rollout)"""
+        from .asmpc import AffineLaw
+        return AffineLaw(x_ref=self.x_ref[k].data_ptr(), u_ref=self.u_ref[k].data_ptr(), M=self.M[k].data_ptr(), flags=self.flags[k].data_ptr(),
+                         lb=None, ub=None, x_scale=self.x_scale.data_ptr(), ld=self.B, max_dx=float("inf"), clip=0, pad=0)
+
+    def _rollout(self, K, W):
+        """K control steps from step self.k in one launch of the general rollout with a law record per step, one synchronisation and
+        one copy to the host; W: [K][B][nw] on the device, or None.  Returns (x [K][B][nx], u [K][B][nu], plant status [K][B], law
+        status [K][B])"""
+        dv, plant, m, B = self.dv, self.plant, self.sim.model, self.B
+        if self.k + K > self.K:
+            raise ValueError(f"BatchClosedLoopTVLQR: step {self.k + K} is past the end of the reference ({self.K} steps)")
+        torch = dv.torch
+        nX, nU = (K + 1) * B * m.n_x, K * B * m.n_u
+        buf = dv.empty(nX + nU + K * B)                        # states, inputs and the two status words behind one another: one copy
+        Xt, Ut = buf[:nX].view(K + 1, B, m.n_x), buf[nX:nX + nU].view(K, B, m.n_u)
+        stw = buf[nX + nU:].view(torch.int32)[:2 * K * B].view(2, K, B)
+        tv, pp = (dv.to_dev(a) for a in plant.rows(self.k, K))
+        Xt[0].copy_(plant.X)
+        self.sim.rollout_device(B, K, Xt.data_ptr(), Ut.data_ptr(), law=self._law(self.k), W_traj=W.data_ptr() if W is not None else 0,
+                                tvp_rows=tv.data_ptr() if m.n_tvp else 0, p_rows=pp.data_ptr() if m.n_p else 0,
+                                plant_status=stw[0].data_ptr(), law_status=stw[1].data_ptr(), stream=dv.stream(), law_step=B)
+        plant.X.copy_(Xt[K])
+        self.U = Ut[K - 1].clone()
+        plant.pstat.copy_(stw[0, K - 1])
+        self.lstat.copy_(stw[1, K - 1])
+        self.k += K
+        dv.sync()
+        host = buf.cpu().numpy()
+        st = host[nX + nU:].view(np.int32)[:2 * K * B].reshape(2, K, B)
+        return host[B * m.n_x:nX].reshape(K, B, m.n_x), host[nX:nX + nU].reshape(K, B, m.n_u), st[0] & 1, st[1].copy()
+
+    def step(self, w=None) -> dict:
+        """one control step of all B loops, two launches: the law step of dompc_affine.h at the record of step `k` (the arrays advanced
+        by hand), then the batched plant step.  w: [B][nw], the process noise of this step"""
+        if self.k >= self.K:
+            raise ValueError(f"BatchClosedLoopTVLQR: step {self.k + 1} is past the end of the reference ({self.K} steps)")
+        plant, m = self.plant, self.sim.model
+        if self._law_step is None:
+            from .asmpc import LawStep
+            self._law_step = LawStep(m.n_x, m.n_u, 0 if self.dv.dev.type == "cpu" else self.dv.dev.index, _lib_path=self._law_lib)
+        plant.refresh(self.k)
+        w = self._noise(w)
+        stream = self.dv.stream()
+        self._law_step.step_device(self._law(self.k), self.B, plant.X.data_ptr(), self.U.data_ptr(), self.lstat.data_ptr(), stream)
+        plant.step(self.U, stream, W=None if w is None else w[0])
+        self.k += 1
+        self.dv.sync()
+        return {"u0": self.U.cpu().numpy(), "x": plant.X.cpu().numpy(), "plant_status": plant.status()[0], "law_status": self.lstat.cpu().numpy()}
+
+    def run(self, n=None, fused: bool = True, chunk=None, W=None) -> dict:
+        """n control steps (default: to the end of the reference); returns the records 'x' [n + 1][B][nx] (with the start), 'u'
+        [n][B][nu], 'plant_status' and 'law_status' [n][B].  fused=True: ceil(n / chunk) launches of the rollout with a law record per
+        step, one synchronisation and one copy each (chunk=None: one launch); fused=False: n calls of step().  W: process noise,
+        [n][B][nw] or a callable k -> [B][nw].  Both leave `k`, the states and the inputs where n calls of step() leave them."""
+        n = self.K - self.k if n is None else int(n)
+        m = self.sim.model
+        if self.k + n > self.K:
+            raise ValueError(f"BatchClosedLoopTVLQR: step {self.k + n} is past the end of the reference ({self.K} steps)")
+        if W is not None and not callable(W):
+            W = self._noise(W)
+            assert W.shape[0] == n, f"W must hold the noise of {n} steps"
+
+        def noise(i, K):
+            if W is None:
+                return None
+            return self._noise(np.stack([np.asarray(W(i + j), float) for j in range(K)])) if callable(W) else W[i:i + K]
+        xs, us, st, ls = [self.plant.X.cpu().numpy().copy()[None]], [], [], []
+        i = 0
+        while i < n:
+            if fused:
+                K = n - i if chunk is None else min(int(chunk), n - i)
+                x, u, s, l = self._rollout(K, noise(i, K))
+            else:
+                K, w = 1, noise(i, 1)
+                r = self.step(w=None if w is None else w[0])
+                x, u, s, l = r["x"].copy()[None], r["u0"].copy()[None], r["plant_status"][None], r["law_status"][None]
+            xs.append(x); us.append(u); st.append(s); ls.append(l)
+            i += K
+        cat = lambda parts, shape, dt: np.concatenate(parts) if parts else np.zeros(shape, dtype=dt)      # noqa: E731
+        return {"x": np.concatenate(xs), "u": cat(us, (0, self.B, m.n_u), float), "plant_status": cat(st, (0, self.B), np.int32),
+                "law_status": cat(ls, (0, self.B), np.int32)}
 
 
 class BatchClosedLoopAMPC:

@@ -257,6 +257,25 @@ extern "C" int dompc_asmpc_step_batch_device(dompc_asmpc* h, int32_t B, const do
   return h->run(h->fn_step, (unsigned)((B + 63) / 64), 64, 0, stream, &A, sizeof(A));
 }
 
+// the law step on a record of the CALLER's (e.g. one step of a time-varying law, dompc_lqr_tv_device): the handle lends its kernel
+extern "C" int dompc_asmpc_step_law_device(dompc_asmpc* h, const dompc_affine_law* law, int32_t B, const double* x, double* u,
+                                           int32_t* status, void* stream) {
+  if (!h) return 1;
+  if (B <= 0) return 0;
+  if (!law || !x || !u) { h->error = "null pointer"; return 1; }
+  if (!law->x_ref || !law->u_ref || !law->M || !law->x_scale || (law->clip && (!law->lb || !law->ub)) || law->ld < B) {
+    h->error = "dompc_asmpc_step_law_device: incomplete law record (x_ref, u_ref, M, x_scale, with clip lb and ub; ld >= B)";
+    return 1;
+  }
+  dompc_asmpck::StepArgs A;
+  memset(&A, 0, sizeof(A));
+  A.x = x; A.u = u; A.status = status;
+  memcpy(&A.law, law, sizeof(A.law));
+  A.batch = B;
+  if (h->set_device()) return 1;
+  return h->run(h->fn_step, (unsigned)((B + 63) / 64), 64, 0, stream, &A, sizeof(A));
+}
+
 extern "C" int dompc_asmpc_step_batch(dompc_asmpc* h, int32_t B, const double* x, double* u_out, int32_t* status) {
   if (!h) return 1;
   if (B <= 0) return 0;

@@ -25,4 +25,33 @@ struct Args {
   double z_tol;                              // Newton stops at max |g| <= z_tol ...
   int32_t z_max_iter;                        // ... or after z_max_iter updates z <- z - g_z^-1 g (at most 127)
 };
+// dompc_lqr_pairs_kernel: the discrete pairs of a model at the B x K knots of B trajectories, one item (k, b) per row of 16 lanes
+struct PairsArgs {
+  const double *x, *u;                       // knots, step-major: [K][B][nx], [K][B][nu]
+  const double *tvp, *p;                     // tvp of item (k, b) at k * stride_tvp_step + b * stride_tvp_loop ([K][ntvp] shared by the
+                                             // batch: (ntvp, 0); [K][B][ntvp]: (B ntvp, ntvp)); p of loop b at b * stride_p
+  const double* z;                           // [K][B][nz] Newton start of the algebraic states (LQR_NZ > 0)
+  double *A, *B;                             // out: [K][B][nx][nx], [K][B][nx][nu]; zeros at a knot that failed
+  double* z_out;                             // [K][B][nz] (may be null): the consistent algebraic states
+  int32_t* status;                           // [K][B] (may be null): bit 1 = the exponential failed, bit 2 = Newton or the reduction
+                                             // failed; Newton updates in bits 24 .. 30
+  int32_t batch, steps;
+  int64_t stride_tvp_step, stride_tvp_loop, stride_p;
+  double t_step, z_tol;
+  int32_t z_max_iter;
+};
+
+// dompc_lqr_tv_kernel: the time-varying backward recursion over K pairs for B trajectories, one trajectory per row of 16 lanes
+struct TvArgs {
+  const double *A, *B;                       // [K][B][nx][nx], [K][B][nx][nu]: the discrete pairs (model size)
+  const int32_t* pair_status;                // [K][B] (may be null), the status words of the pairs launch: a non-zero low byte is a failed pair
+  const double *Q, *R, *Pf;                  // design-size weights, per trajectory or shared (stride 0)
+  double* K;                                 // out (may be null): gains [K][B][nu][n]
+  double* M;                                 // out (may be null, standard mode only): law layout [K][nu][nx][ld], loop index fastest
+  double* P;                                 // out (may be null): cost-to-go [K+1][B][n][n]
+  double* P0;                                // out: [B][n][n]
+  int32_t* status;                           // [B] (may be null): bit 1 = singular or non-finite block, bit 2 = failed or non-finite
+                                             // pair, at the step in bits 8 .. 23: K_j = 0 for j <= step, P_0 = Q
+  int32_t batch, steps, ld, stride_q, stride_r, stride_pf;
+};
 }  // namespace dompc_lqrk

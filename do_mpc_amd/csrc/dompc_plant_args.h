@@ -43,4 +43,11 @@ struct LoopArgs {
   int32_t *plant_status, *law_status;        // [K][B] each (may be null)
   int32_t K, has_law;
 };
+// The general rollout with a law record per step (dompc_plant_tvloop_kernel): the record of step k is `loop.law` with x_ref, u_ref, M
+// and flags advanced by k nx law_step, k nu law_step, k nu nx law_step and k law_step elements - arrays [K][nx][ld], [K][nu][ld],
+// [K][nu][nx][ld], [K][ld] with law_step = ld; lb, ub, x_scale, clip and max_dx are shared by the steps.  has_law = 1, G = null.
+struct TvLoopArgs {
+  LoopArgs loop;
+  int64_t law_step;
+};
 }  // namespace dompc_plantk

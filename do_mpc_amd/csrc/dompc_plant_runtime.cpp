@@ -13,6 +13,7 @@ extern "C" void dompc_plant_hostemu_info(const void* args);
 extern "C" void dompc_plant_hostemu_run(const void* args);
 extern "C" void dompc_plant_hostemu_rollout(const void* args);
 extern "C" void dompc_plant_hostemu_loop(const void* args);
+extern "C" void dompc_plant_hostemu_tvloop(const void* args);
 // ... and of the fused approximate-MPC loop (dompc_ampc_loop.hip): there only in the host library of a (plant, network shape) pair
 extern "C" void dompc_ampc_loop_hostemu_info(const void* args) __attribute__((weak));
 extern "C" void dompc_ampc_loop_hostemu_run(const void* args) __attribute__((weak));
@@ -34,7 +35,7 @@ struct dompc_plant : dompc_host::Context {
   bool z_carry_host = false;            // host entry (dompc_plant_step_batch): rows of consecutive calls are the same trajectories (dompc_plant_set_z_carry)
   bool z_reseed_next = false;
   dompc_host::Module module = nullptr;
-  dompc_host::Kernel fn, fn_rollout, fn_loop;
+  dompc_host::Kernel fn, fn_rollout, fn_loop, fn_tvloop;
   // the fused approximate-MPC loop of a pair object, looked up on first use: 0 not looked for yet, 1 there, -1 the object has none
   int ampc_loop_state = 0;
   dompc_host::Kernel fn_ampc_loop;
@@ -71,6 +72,8 @@ extern "C" int dompc_plant_create(const dompc_plant_desc* desc, dompc_plant** ou
   // the general rollout: every plant has it
   if (info[11] != (int64_t)sizeof(dompc_plantk::LoopArgs)) { h->error = "plant loop argument layout mismatch between runtime and code object"; return fail(); }
   if (!h->find(h->module, {"dompc_plant_loop_kernel", &h->fn_loop, DOMPC_TWIN(dompc_plant_hostemu_loop)})) { h->error = "code object lacks the plant kernels"; return fail(); }
+  if (info[12] != (int64_t)sizeof(dompc_plantk::TvLoopArgs)) { h->error = "plant loop argument layout mismatch between runtime and code object (dompc_plant_tvloop_kernel)"; return fail(); }
+  if (!h->find(h->module, {"dompc_plant_tvloop_kernel", &h->fn_tvloop, DOMPC_TWIN(dompc_plant_hostemu_tvloop)})) { h->error = "code object lacks the plant kernels"; return fail(); }
   h->d.code_object_path = nullptr; h->d.model_hash = nullptr;
   h->nz = (int32_t)info[9];
   h->z0.assign((size_t)(h->nz > 0 ? h->nz : 0), 0.0);
@@ -228,6 +231,10 @@ extern "C" int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, 
   if (r->G && !law) return refuse("G without a law");
   if (r->G && !r->up_ref) return refuse("G without up_ref");
   if (r->G && !r->U_prev0) return refuse("G without U_prev0");
+  if (r->law_step < 0) return refuse("law_step is negative");
+  if (r->law_step > 0 && !law) return refuse("law_step without a law");
+  if (r->law_step > 0 && (r->G || r->up_ref)) return refuse("law_step with G / up_ref (the time-varying input-rate law is not built)");
+  if (r->law_step > 0 && r->law_step < B) return refuse("law_step < B");
   if (r->Z_traj && h->nz <= 0) return refuse("Z_traj on a plant without algebraic states");
   if (h->set_device()) return 1;
   // the per-loop Newton starts of the algebraic states: as dompc_plant_step_batch_device treats them, or seeded from z0 first
@@ -241,6 +248,12 @@ extern "C" int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, 
   R.X_traj = r->X_traj; R.U_traj = r->U_traj; R.W_traj = r->W_traj; R.V_traj = r->V_traj; R.Y_traj = r->Y_traj; R.Z_traj = r->Z_traj;
   R.tvp_rows = r->tvp_rows; R.p_rows = r->p_rows; R.p_loops = r->p_loops;
   R.plant_status = r->plant_status; R.law_status = r->law_status; R.K = K;
+  if (r->law_step > 0) {                 // a law record per step: an entry of its own, the one above is what it was
+    dompc_plantk::TvLoopArgs T;
+    memset(&T, 0, sizeof(T));
+    T.loop = R; T.law_step = r->law_step;
+    return h->run(h->fn_tvloop, (unsigned)((B + 63) / 64), 64, 0, stream, &T, sizeof(T));
+  }
   return h->run(h->fn_loop, (unsigned)((B + 63) / 64), 64, 0, stream, &R, sizeof(R));
 }
 

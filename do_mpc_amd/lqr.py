@@ -70,6 +70,12 @@ def _bind(lib_path: str) -> C.CDLL:
     lib.dompc_lqr_design_dae_batch.restype = C.c_int
     lib.dompc_lqr_design_dae_batch_device.argtypes = [vp, C.c_int32] + [vp] * 10 + [C.c_int32] + [vp] * 5
     lib.dompc_lqr_design_dae_batch_device.restype = C.c_int
+    lib.dompc_lqr_pairs_device.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 5 + [C.c_int32] + [vp] * 5
+    lib.dompc_lqr_pairs_device.restype = C.c_int
+    lib.dompc_lqr_tv_device.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 6 + [C.c_int32, vp, vp, C.c_int32] + [vp] * 4
+    lib.dompc_lqr_tv_device.restype = C.c_int
+    lib.dompc_lqr_tv.argtypes = [vp, C.c_int32, C.c_int32] + [vp] * 10 + [C.c_int32] + [vp] * 8
+    lib.dompc_lqr_tv.restype = C.c_int
     return lib
 
 
@@ -252,15 +258,18 @@ class LQR:
         for d in self._designs.values():
             d.close()
 
-    def _weights(self, Q, R, P, B):
+    def _weights(self, Q, R, P, B, finite=None):
         """design-size weights (Q~ = diag(Q, R), R~ = delR, P~ = diag(P, R) in inputRatePenalization mode, _lqr.py:484-490) from the
         arguments or, where they are missing, from set_objective / set_rterm -> (Q, R, P or None, shared mask bits 0..2)"""
         rate = self.mode == "inputRatePenalization"
         n_x, n_u, n = self.model.n_x, self.model.n_u, self.n_design
-        finite = self.settings.n_horizon is not None
+        tv = finite == "tv"                          # (the time-varying recursion: always finite, P defaults to Q)
+        finite = self.settings.n_horizon is not None if finite is None else bool(finite)
         Qs = self._Q_user if Q is None else Q
         Rs = self._R_user if R is None else R
         Ps = (self._P_user if P is None else P) if finite else None
+        if tv and (Ps is None or np.size(Ps) == 0):
+            Ps = Qs
         assert Qs is not None and Rs is not None and np.size(Qs) != 0 and np.size(Rs) != 0, \
             "Enter tuning parameter Q and R for the lqr problem using set_objective() function."
         if finite:
@@ -385,6 +394,113 @@ class LQR:
             rc = d.lib.dompc_lqr_design_batch_device(
                 d.h, int(Bn), *[vp(a) for a in (A, B, x, u, tvp, p, Q, R, P_term)], int(shared_mask), vp(K), vp(P), vp(status), vp(stream))
         d.check(rc)
+
+    # ------------------------------------------------------------------ time-varying designs along trajectories
+    def _run_tv(self, model, Bn, K, A, Bm, X, U, Z, tvp, p, mask, Q, R, P, P_traj) -> dict:
+        d = self._design(model)
+        m = self.model
+        n, n_u = self.n_design, m.n_u
+        Qd, Rd, Pd, wmask = self._weights(Q, R, P, Bn, finite="tv")
+        Kout = np.empty((K, Bn, n_u, n))
+        P0 = np.empty((Bn, n, n))
+        Pt = np.empty((K + 1, Bn, n, n)) if P_traj else None
+        Ao = np.empty((K, Bn, m.n_x, m.n_x)) if model is not None else None
+        Bo = np.empty((K, Bn, m.n_x, m.n_u)) if model is not None else None
+        Zo = np.empty((K, Bn, model.n_z)) if model is not None and model.n_z else None
+        ps = np.zeros((K, Bn), dtype=np.int32) if model is not None else None
+        status = np.zeros(Bn, dtype=np.int32)
+        ptr = lambda a: a.ctypes.data_as(C.c_void_p) if a is not None else None      # noqa: E731
+        d.check(d.lib.dompc_lqr_tv(d.h, Bn, K, ptr(A), ptr(Bm), ptr(X), ptr(U), ptr(Z), ptr(tvp), ptr(p), ptr(Qd), ptr(Rd), ptr(Pd),
+                                   mask | wmask, ptr(Kout), ptr(P0), ptr(Pt), ptr(Ao), ptr(Bo), ptr(Zo), ptr(ps), ptr(status)))
+        out = {"K": Kout, "P0": P0, "status": status & 0xFF, "step": (status >> 8) & 0xFFFF}
+        if Pt is not None:
+            out["P"] = Pt
+        if model is not None:
+            out["A"], out["B"], out["pair_status"], out["newton"] = Ao, Bo, ps & 0xFF, ps >> 24
+            if Zo is not None:
+                out["Z"] = Zo
+        return out
+
+    def gains_tv_batch(self, A, B, Q=None, R=None, P=None, P_traj: bool = False) -> dict:
+        """Time-varying LQR for Bn trajectories of K discrete pairs A [K][Bn][nx][nx], B [K][Bn][nx][nu] (one trajectory: without the
+        batch axis) in one launch: P = P_f, then K_k = -(B_k'PB_k + R)^-1 B_k'PA_k, P <- Q + A_k'P(A_k + B_k K_k) for k = K-1 .. 0, in
+        this controller's mode.  Q, R, P (terminal weight, default Q): as in gains_batch, one per trajectory or shared; there are no
+        per-step weights.  settings.n_horizon is not read: the horizon is K.  Returns {'K': [K][Bn][nu][n], 'P0': [Bn][n][n], 'status',
+        'step'} and, with P_traj=True, 'P': [K+1][Bn][n][n].  status bit 1 = singular or non-finite block, bit 2 = non-finite pair,
+        met at step 'step': K_j = 0 for j <= step, the gains behind it are kept, P0 = Q."""
+        m = self.model
+        A = np.ascontiguousarray(np.asarray(A, dtype=np.float64))
+        Bm = np.ascontiguousarray(np.asarray(B, dtype=np.float64))
+        if A.ndim == 3:
+            A, Bm = A[:, None], Bm[:, None]
+        if A.ndim != 4 or A.shape[2:] != (m.n_x, m.n_x) or A.shape[0] < 1:
+            raise ValueError(f"A: expected shape (K, Bn, {m.n_x}, {m.n_x}) with K >= 1, got {A.shape}")
+        K, Bn = A.shape[:2]
+        if Bm.shape != (K, Bn, m.n_x, m.n_u):
+            raise ValueError(f"B: expected shape ({K}, {Bn}, {m.n_x}, {m.n_u}), got {Bm.shape}")
+        return self._run_tv(None, Bn, K, np.ascontiguousarray(A), np.ascontiguousarray(Bm), None, None, None, None, None, 0, Q, R, P, P_traj)
+
+    def gains_along(self, model: Model, X_traj, U_traj, TVP=None, PAR=None, Q=None, R=None, P=None, Z0=None, P_traj: bool = False) -> dict:
+        """Time-varying LQR along Bn trajectories of the nonlinear `model`: knots X_traj [K][Bn][nx], U_traj [K][Bn][nu] (step-major,
+        as the rollouts record them; one trajectory: without the batch axis).  One launch forms the discrete pair of every knot - the
+        pair gains_at forms there: Jacobians frozen at (x*_k, u*_k), zero-order hold over settings.t_step for a continuous model,
+        Newton and reduction for algebraic states (Z0 [K][Bn][nz], [nz] or None = 0) - and a second one runs the recursion of
+        gains_tv_batch.  TVP: [ntvp], [K][ntvp] (shared by the trajectories) or [K][Bn][ntvp]; PAR: [np] or [Bn][np].  Returns what
+        gains_tv_batch returns plus 'A', 'B' (the pairs), 'pair_status' [K][Bn] (bit 1 = the exponential failed, bit 2 = Newton or the
+        reduction failed: the pair is zero and the trajectory reports status bit 2 at that step), 'newton' and, for a model with
+        algebraic states, 'Z' [K][Bn][nz]."""
+        m = self.model
+        X = np.asarray(X_traj, dtype=np.float64)
+        if X.ndim == 2:
+            X = X[:, None]
+        if X.ndim != 3 or X.shape[2] != m.n_x or X.shape[0] < 1:
+            raise ValueError(f"X_traj: expected shape (K, Bn, {m.n_x}) with K >= 1, got {X.shape}")
+        K, Bn = X.shape[:2]
+        X = np.ascontiguousarray(X)
+        U = np.ascontiguousarray(np.asarray(U_traj, dtype=np.float64).reshape(K, Bn, m.n_u))
+        if model.model_type == "continuous":
+            self.settings.check_for_mandatory_settings()
+        mask, tvp, p = 8 | 16, None, None
+        if model.n_tvp:
+            tvp = np.zeros(model.n_tvp) if TVP is None else np.asarray(TVP, dtype=np.float64)
+            if tvp.ndim == 3:
+                if tvp.shape != (K, Bn, model.n_tvp):
+                    raise ValueError(f"TVP: expected shape ({K}, {Bn}, {model.n_tvp}), got {tvp.shape}")
+                mask &= ~8
+            else:
+                tvp = np.broadcast_to(tvp.reshape(-1, model.n_tvp), (K, model.n_tvp))
+            tvp = np.ascontiguousarray(tvp)
+        if model.n_p:
+            p, sp = _rows(PAR, model.n_p, Bn)
+            mask = mask if sp else mask & ~16
+        Z = None
+        if model.n_z:
+            Z = np.zeros(model.n_z) if Z0 is None else np.asarray(Z0, dtype=np.float64)
+            Z = np.ascontiguousarray(np.broadcast_to(Z if Z.ndim == 3 else Z.reshape(-1, model.n_z)[:1], (K, Bn, model.n_z)))
+        return self._run_tv(model, Bn, K, None, None, X, U, Z, tvp, p, mask, Q, R, P, P_traj)
+
+    def gains_tv_batch_device(self, Bn, K, A, B, Q, R, P_term, P0, K_traj=0, law_M=0, ld=0, P_traj=0, pair_status=0, status=0,
+                              shared_mask=0, stream=0, _design=None):
+        """gains_tv_batch on raw device addresses, asynchronous on `stream`.  Q, R, P_term are of DESIGN size (shared_mask bit 0/1/2 =
+        one matrix shared by all trajectories).  Gains go to K_traj [K][Bn][nu][n] and / or, in standard mode, to law_M
+        [K][nu][nx][ld] (ld >= Bn): the layout of the rollout's law record with law_step = ld."""
+        d = self._design(None) if _design is None else _design
+        vp = lambda a: C.c_void_p(int(a) if a else None)      # noqa: E731
+        d.check(d.lib.dompc_lqr_tv_device(d.h, int(Bn), int(K), vp(A), vp(B), vp(pair_status), vp(Q), vp(R), vp(P_term), int(shared_mask),
+                                          vp(K_traj), vp(law_M), int(ld), vp(P_traj), vp(P0), vp(status), vp(stream)))
+
+    def gains_along_device(self, model, Bn, K, x, u, A, B, Q, R, P_term, P0, tvp=0, p=0, z=0, z_out=0, K_traj=0, law_M=0, ld=0, P_traj=0,
+                           pair_status=0, status=0, shared_mask=0, stream=0, recursion=True):
+        """gains_along on raw device addresses: the pairs launch (into A [K][Bn][nx][nx], B [K][Bn][nx][nu], which the caller
+        provides) and the recursion launch behind it on `stream`.  shared_mask: bit 0/1/2 = Q/R/P_term shared, bit 3 = tvp is
+        [K][ntvp], bit 4 = p is [np].  pair_status [K][Bn] (optional) lets the recursion see a failed knot; without it such a knot is
+        a pair of zeros.  recursion=False: the pairs launch alone."""
+        d = self._design(model)
+        vp = lambda a: C.c_void_p(int(a) if a else None)      # noqa: E731
+        d.check(d.lib.dompc_lqr_pairs_device(d.h, int(Bn), int(K), vp(x), vp(u), vp(z), vp(tvp), vp(p), int(shared_mask), vp(A), vp(B),
+                                             vp(z_out), vp(pair_status), vp(stream)))
+        if recursion:
+            self.gains_tv_batch_device(Bn, K, A, B, Q, R, P_term, P0, K_traj, law_M, ld, P_traj, pair_status, status, shared_mask, stream, d)
 
     # ------------------------------------------------------------------ setup and runtime
     _Q_user = property(lambda self: getattr(self, "_Q0", getattr(self, "Q", None)))

@@ -453,7 +453,7 @@ def linearize(model: Model, xss: np.ndarray = None, uss: np.ndarray = None, tvp0
     assert model._z.size == 0, "Linearization around steady state is not supported for DAEs"
     A, B, C, D = model.get_linear_system_matrices(xss, uss, tvp=tvp0, p=p0)
     if not all(isinstance(M, np.ndarray) for M in (A, B, C, D)):
-        raise NotImplementedError("LTV models are not yet implemented.")
+        raise NotImplementedError("LTV models are not yet implemented. (gains along a trajectory: LQR.gains_along)")
     linear = LinearModel(model.model_type, model.symvar_type)
     model._transfer_variables(model, linear)
     n_x, n_u = model.n_x, model.n_u

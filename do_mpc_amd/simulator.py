@@ -53,7 +53,7 @@ class RolloutDesc(C.Structure):
     """dompc_plant_rollout_desc of include/dompc_ipm.h"""
     _fields_ = [(n, C.c_void_p) for n in ("law", "G", "up_ref", "U_prev0", "X_traj", "U_traj", "W_traj", "V_traj", "Y_traj", "Z_traj",
                                           "tvp_rows", "p_rows", "p_loops", "plant_status", "law_status")] + \
-               [("reseed_z", C.c_int32), ("pad", C.c_int32)]
+               [("reseed_z", C.c_int32), ("pad", C.c_int32), ("law_step", C.c_int64)]
 
 
 class AmpcLoopDesc(C.Structure):
@@ -317,14 +317,17 @@ class Simulator:
         self._check(rc)
 
     def rollout_device(self, B, K, X_traj, U_traj, law=None, G=0, up_ref=0, U_prev0=0, W_traj=0, V_traj=0, Y_traj=0, Z_traj=0,
-                       tvp_rows=0, p_rows=0, p_loops=0, plant_status=0, law_status=0, reseed_z=False, stream=0):
+                       tvp_rows=0, p_rows=0, p_loops=0, plant_status=0, law_status=0, reseed_z=False, stream=0, law_step=0):
         """K control steps of B loops in ONE launch, for every plant (`dompc_plant_rollout_device`, include/dompc_ipm.h).  Raw device
         addresses, asynchronous on `stream`.  X_traj [K + 1][B][nx] with row 0 filled; per step k the plant step of `step_batch_device`
         from X_traj[k] to X_traj[k + 1] with
           the input   `law` (a ctypes `dompc_affine_law` record) at X_traj[k], written to U_traj[k] [K][B][nu], its status to law_status
                       [K][B]; with G [nu][nu][ld] the law has a previous-input term, u = sat(u_ref + M (x - x_ref) + G (u_prev - up_ref)),
                       up_ref [nu][ld], u_prev = U_prev0 [B][nu] at k = 0 and the (clipped) input of step k - 1 afterwards.  Without a law
-                      U_traj[k] is read: an open-loop simulation;
+                      U_traj[k] is read: an open-loop simulation.  law_step = s > 0: a law record PER STEP - the record of step k is
+                      `law` with x_ref, u_ref, M and flags advanced by k nx s, k nu s, k nu nx s and k s elements (arrays [K][nx][ld],
+                      [K][nu][ld], [K][nu][nx][ld], [K][ld] with s = ld: the layout `LQR.gains_along_device(law_M=)` writes); lb, ub,
+                      x_scale, clip and max_dx are shared by the steps; refused together with G / up_ref;
           parameters  tvp_rows [K][n_tvp] shared by the batch; p_rows [K][n_p] shared by the batch OR p_loops [B][n_p], one row per loop;
           noise       W_traj [K][B][nw], V_traj [K][B][nv] (0: none);
           records     Y_traj [K][B][ny] (the measurement at X_traj[k + 1]), Z_traj [K][B][nz] (the algebraic states there), plant_status
@@ -338,6 +341,7 @@ class Simulator:
                         ("p_loops", p_loops), ("plant_status", plant_status), ("law_status", law_status)):
             setattr(r, name, int(a) if a else None)
         r.reseed_z = 1 if reseed_z else 0
+        r.law_step = int(law_step)
         rc = self._lib.dompc_plant_rollout_device(self._h, int(B), int(K), C.byref(r), C.c_void_p(int(stream) if stream else None))
         self._check(rc)
 

@@ -423,6 +423,32 @@ int dompc_lqr_design_dae_batch_device(dompc_lqr* h, int32_t B, double* A, double
                                       const double* z, const double* tvp, const double* p, const double* Q, const double* R,
                                       const double* Pf, int32_t shared_mask, double* K, double* P, double* z_out, int32_t* status,
                                       void* stream);
+/* ... time-varying LQR along B trajectories of K steps (dompc_lqr_pairs_kernel, dompc_lqr_tv_kernel): one backward recursion
+ * K_k = -(B_k'PB_k + R)^-1 B_k'PA_k, P <- Q + A_k'P(A_k + B_k K_k) from P = Pf over k = K-1 .. 0, a pair and a gain per step.  The
+ * horizon is K: desc.n_horizon is not read.  All trajectory arrays are STEP-MAJOR: x_traj [K][B][nx], u_traj [K][B][nu], z0 / z_out
+ * [K][B][nz], A_traj [K][B][nx][nx], B_traj [K][B][nx][nu], K_traj [K][B][nu][n], P_traj [K+1][B][n][n] (entry K is Pf), P0 [B][n][n].
+ * pairs: needs a code object WITH a model; the pair of knot (k, b) is what dompc_lqr_design_batch forms at that point (Jacobians
+ * frozen at the knot, zero-order hold over t_step for a continuous model, reduction of algebraic states).  tvp is [K][ntvp] with bit 3
+ * of shared_mask set, else [K][B][ntvp]; p is [np] with bit 4 set, else [B][np].  pair status [K][B]: bit 1 = the exponential failed,
+ * bit 2 = Newton or the reduction failed (the pair is zero either way); Newton updates = status >> 24.
+ * tv: reads model-size pairs whatever the code object; Q, R, Pf in design size with bits 0/1/2 of shared_mask as above (no per-step
+ * weights); pair_status (may be NULL) marks failed pairs.  K_traj and / or law_M (standard mode only) receive the gains, law_M in the
+ * layout of the plant rollout's law record, [K][nu][nx][ld] with the trajectory index fastest and ld >= B; P_traj may be NULL; P0 is
+ * always written.  status[b]: bit 1 = singular or non-finite block, bit 2 = failed or non-finite pair, met at step (status >> 8) &
+ * 0xFFFF: K_j = 0 for j <= that step (the law replays u* there), the gains of the steps behind it are kept, P0 = Q, never NaN.
+ * B <= 0 launches nothing; K <= 0 launches nothing when every output is NULL and is refused otherwise. */
+int dompc_lqr_pairs_device(dompc_lqr* h, int32_t B, int32_t K, const double* x_traj, const double* u_traj, const double* z0,
+                           const double* tvp, const double* p, int32_t shared_mask, double* A_traj, double* B_traj, double* z_out,
+                           int32_t* status, void* stream);
+int dompc_lqr_tv_device(dompc_lqr* h, int32_t B, int32_t K, const double* A_traj, const double* B_traj, const int32_t* pair_status,
+                        const double* Q, const double* R, const double* Pf, int32_t shared_mask, double* K_traj, double* law_M,
+                        int32_t ld, double* P_traj, double* P0, int32_t* status, void* stream);
+/* host buffers: with a model the knots -> pairs -> recursion (A_traj / B_traj are not read; z0 NULL = 0), without one the pairs
+ * themselves; P_out, A_out, B_out, Z_out, pair_status, status may be NULL */
+int dompc_lqr_tv(dompc_lqr* h, int32_t B, int32_t K, const double* A_traj, const double* B_traj, const double* x_traj,
+                 const double* u_traj, const double* z0, const double* tvp, const double* p, const double* Q, const double* R,
+                 const double* Pf, int32_t shared_mask, double* K_out, double* P0_out, double* P_out, double* A_out, double* B_out,
+                 double* Z_out, int32_t* pair_status, int32_t* status);
 
 /* ---- batched approximate MPC (csrc/dompc_ampc.hip): what do_mpc.approximateMPC.ApproxMPC.make_step computes - scale the input
  * [x; u_prev] by its bounds box, evaluate a feed-forward network in float32, rescale the output to [lbu, ubu] and clip - for B
@@ -520,6 +546,9 @@ typedef struct dompc_plant_rollout_desc {
   const double *tvp_rows, *p_rows, *p_loops;
   int32_t *plant_status, *law_status;
   int32_t reseed_z, pad;
+  int64_t law_step;                  /* 0: one law record for the K steps.  s > 0: the record of step k is `law` with x_ref, u_ref, M, flags
+                                        advanced by k nx s, k nu s, k nu nx s, k s elements ([K][nx][ld], ... with s = ld); lb, ub, x_scale,
+                                        clip, max_dx are shared by the steps.  Refused with G / up_ref, without a law, and with s < B */
 } dompc_plant_rollout_desc;
 int dompc_plant_rollout_device(dompc_plant* h, int32_t B, int32_t K, const dompc_plant_rollout_desc* r, void* stream);
 
@@ -592,6 +621,10 @@ int dompc_asmpc_law(dompc_asmpc* h, dompc_affine_law* out);
 int dompc_asmpc_step_batch(dompc_asmpc* h, int32_t B, const double* x, double* u_out, int32_t* status);
 /* DEVICE buffers, asynchronous on `stream` (hipStream_t as void*) */
 int dompc_asmpc_step_batch_device(dompc_asmpc* h, int32_t B, const double* x, double* u, int32_t* status, void* stream);
+/* ... the same step on a law record of the caller's (device addresses; e.g. the record of one step of a time-varying law written by
+ * dompc_lqr_tv_device): the handle's own law, options and batch are not read.  Refused: an incomplete record, ld < B. */
+int dompc_asmpc_step_law_device(dompc_asmpc* h, const dompc_affine_law* law, int32_t B, const double* x, double* u, int32_t* status,
+                                void* stream);
 /* Event-triggered re-solves of some loops of the law.
  * dompc_asmpc_select_device: idx[0 .. count[0]) = the loops b with status[b] & mask != 0 in ascending order of b (status [B]: what a
  * step wrote; idx [B], count [1]; entries of idx beyond count are not written).  An ordered compaction: list and count do not depend
